@@ -15,7 +15,14 @@ configs[1] ("lego sparse 100k"; dataset unavailable).  Inputs a
 HBM before the timed region.  Multi-GPU: rays are independent units -- every rank traces its
 own frame (camera rotated per rank), no data-path collective; scaling = weak.
 
-Prints ONE JSON line on rank 0 (see the driver contract): metric/value = whole-job ray-tet
+A plain run (no --full) is the headline alone: set up, warm up, time the --steps steps, write the
+outputs of the last timed step if --dump-outputs DIR is given (see dump_outputs), print the line:
+metric/value = whole-job ray-tet intersections per second, ms_per_step, and `roofline` from the
+HIP-event duration of the timed launches.  Everything else below -- the box write ceiling and
+the serialised breakdown, segments_only, cpu_baseline, configs, render, sharded_render, the DDP
+leg -- runs with --full only (the --no-* options then leave out single legs as before).
+
+With --full, prints ONE JSON line on rank 0 (see the driver contract): metric/value = whole-job ray-tet
 intersections per second, plus `roofline` (dense-output HBM bytes of the dominant kernel over
 its HIP-event duration), `cpu_baseline` (the CPU oracle's BVH path, timing build -O3
 -march=native, on a bounded sample of the same rays, all host cores), and -- single-GPU runs --
@@ -622,6 +629,36 @@ def cpu_baseline(pts, cells, o, d, M, target_s=30.0):
             "sample": f"{n} random rays of the same frame, M={M}, oracle BVH path, {dt:.1f} s"}
 
 
+DUMP_BUDGET = 60 << 20      # bytes of .npy data --dump-outputs writes at most
+DUMP_ROWS = 1024            # rays whose dense rows it writes at most
+DUMP_SEED = 20261016        # the seed of the sample of those rays
+
+
+def dump_outputs(out, directory):
+    """--dump-outputs: what the last timed step returned to its caller (trace_rays' five arrays), one DIR/<name>.npy per
+    array -- integer arrays as float64 (exact), float arrays as float32.  num_visited_cells is written whole; the dense
+    rows (R x M slots, 17 GB at the headline size) of a fixed sample of rays: DUMP_ROWS of them drawn with DUMP_SEED
+    (fewer if M is large), in ray order -- the same rays whatever the build computes, so two builds compare array for
+    array.  At most DUMP_BUDGET bytes in all."""
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    R = out["num_visited_cells"].shape[0]
+    rows = ("visited_cells", "barycentric_coordinates", "hit_distances", "vertex_indices")
+    per_ray = sum(out[k][0].numel() * (4 if out[k].is_floating_point() else 8) for k in rows)
+    counts_whole = 8 * R <= DUMP_BUDGET // 4
+    k = int(min(R, DUMP_ROWS, (DUMP_BUDGET - (8 * R if counts_whole else 0)) // (per_ray + 8)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(R, size=k, replace=False))
+    idx_dev = torch.from_numpy(idx).to(out["num_visited_cells"].device)
+    total = 0
+    for name in ("num_visited_cells",) + rows:
+        t = out[name] if (name == "num_visited_cells" and counts_whole) else out[name].index_select(0, idx_dev)
+        a = t.float().cpu().numpy() if t.is_floating_point() else t.double().cpu().numpy()
+        np.save(directory / f"{name}.npy", a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET, total
+    return {"dir": str(directory), "bytes": total, "sampled_rays": k}
+
+
 def _get(dct, *path):
     for k in path:
         if not isinstance(dct, dict) or k not in dct:
@@ -722,7 +759,16 @@ def main():
                          "short line (<= 4 KB) whose `roofline.secondary` holds every graded fraction")
     ap.add_argument("--no-calibration", action="store_true",
                     help="skip the box write-ceiling measurement and the serialised breakdown (rocprofv3 PMC passes: only the bench launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (box write ceiling, breakdown, segments_only, cpu_baseline, "
+                         "configs, render, sharded_render, DDP); without it a run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run: the headline alone, every secondary leg off
+        args.no_cpu_baseline = args.no_render = args.no_configs = args.no_ddp = args.no_c6 = args.no_calibration = True
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the HIP path has no CPU fallback)")
@@ -759,7 +805,7 @@ def main():
     tracer = tn.TetrahedraTracer(dev)
     x_dev, c_dev = torch.from_numpy(pts).to(dev), torch.from_numpy(cells).to(dev)
     load_s = 0.0
-    for _ in range(2):   # the second call is the steady-state figure (the first one loads the build kernels)
+    for _ in range(2 if args.full else 1):   # --full: the second call is the steady-state figure (the first loads the build kernels)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         tracer.load_tetrahedra(x_dev, c_dev)
@@ -769,14 +815,13 @@ def main():
     d = torch.from_numpy(d_np).to(dev)
 
     def step():
-        out = tracer.trace_rays(o, d, M)
-        return out["num_visited_cells"]
+        return tracer.trace_rays(o, d, M)
 
     inter = 0
     for _ in range(max(args.warmup, 0)):
-        inter = int(step().sum())
+        inter = int(step()["num_visited_cells"].sum())
     if args.warmup <= 0:
-        inter = int(step().sum())
+        inter = int(step()["num_visited_cells"].sum())
     stats = tracer.trace_stats()
     reasons = {str(k): v for k, v in tracer.flag_reasons().items()}   # why the walk handed rays over (include/tetranerf_hip.h)
     xcheck = cross_check(tracer)
@@ -787,15 +832,20 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for k in range(args.steps):
+        last = None             # the previous step's outputs go back to the allocator before the next call
         ev[k][0].record()
-        step()
+        last = step()
         ev[k][1].record()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, args.dump_outputs)
+    last = None
 
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     tot_inter = float(inter)
@@ -863,27 +913,32 @@ def main():
             "certification_cross_check": xcheck,
             "load_tetrahedra_s": load_s,
         }
+        if not args.full:   # a plain run measures neither the box write ceiling nor a steady-state load (see --full)
+            for k in ("box_write_ceiling_GBps", "box_write_ceiling", "frac_of_box_write_ceiling", "breakdown_ms_serialised"):
+                del line["roofline"][k]
+            del line["box_write_ceiling_GBps_per_rank"], line["load_tetrahedra_s"]
         # secondary figure of SURVEY.md 8(d): the same launch without the constant tails of the dense
         # reference layout ("dense_tails" = 0; rows valid through num_visited only) -- what a
         # non-materialising consumer (find_visited_cells, the render path) needs
-        def step_compact():
-            return tracer.trace_rays(o, d, M, compact_rows=True)["num_visited_cells"]
+        if args.full:
+            def step_compact():
+                return tracer.trace_rays(o, d, M, compact_rows=True)["num_visited_cells"]
 
-        step_compact()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.steps):
             step_compact()
-        e1.record()
-        torch.cuda.synchronize()
-        seg_ms = e0.elapsed_time(e1) / args.steps
-        seg_bytes = 28 * R + 52 * inter
-        line["segments_only"] = {"ms_per_step": seg_ms, "rays_per_s": R / (seg_ms * 1e-3),
-                                 "intersections_per_s": inter / (seg_ms * 1e-3),
-                                 "algorithmic_bytes_per_launch": seg_bytes,
-                                 "achieved_GBps": seg_bytes / (seg_ms * 1e-3) / 1e9,
-                                 "note": "per-call flag TN_TRACE_COMPACT_ROWS (no reference counterpart): 28 B/ray + 52 B/segment; instruction-issue-bound walk"}
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.steps):
+                step_compact()
+            e1.record()
+            torch.cuda.synchronize()
+            seg_ms = e0.elapsed_time(e1) / args.steps
+            seg_bytes = 28 * R + 52 * inter
+            line["segments_only"] = {"ms_per_step": seg_ms, "rays_per_s": R / (seg_ms * 1e-3),
+                                     "intersections_per_s": inter / (seg_ms * 1e-3),
+                                     "algorithmic_bytes_per_launch": seg_bytes,
+                                     "achieved_GBps": seg_bytes / (seg_ms * 1e-3) / 1e9,
+                                     "note": "per-call flag TN_TRACE_COMPACT_ROWS (no reference counterpart): 28 B/ray + 52 B/segment; instruction-issue-bound walk"}
         if not args.no_render and world == 1:   # secondary legs: single-GPU runs only (rank 0 alone would hold the job)
             line["render"] = render_leg(tn, tracer, len(pts), o, d, M, dev)
     # the sharded render: a collective leg, every rank takes part

@@ -32,7 +32,7 @@ def _free_port():
 def test_bench_gpus_2_starts_two_ranks(device, tmp_path):
     env = dict(os.environ, TETRANERF_BENCH_BACKEND="gloo", TETRANERF_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-configs",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-configs",
                         "--no-cpu-baseline", "--width", "320", "--height", "200", "--mesh-points", "3000",
                         "--full-json", str(tmp_path / "full.json")],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
