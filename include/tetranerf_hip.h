@@ -253,8 +253,10 @@ int tn_trace_cross_check(tn_tracer_t tracer, uint64_t out[8]);
 int tn_trace_timings(tn_tracer_t tracer, float ms[8]);
 
 /* The constant tails of the dense reference rows (py_binding.cpp:53-57: torch::zeros / full(-1) of the five outputs) for slots
- * [first_slot & ~31, M) of EVERY row: visited / verts = 0xFFFFFFFF, bary / dist = 0.  The tracer's own tail-fill kernel as a
- * stand-alone op: what a caller that traced with TN_TRACE_COMPACT_ROWS runs if it later needs dense rows, and what bench.py
+ * [first_slot, M) of EVERY row: visited / verts = 0xFFFFFFFF, bary / dist = 0.  first_slot must be a multiple of 32 (a 128-byte
+ * line boundary in all four arrays); any other value fails rather than being rounded down over written segments.  The kernel is
+ * k_fill_linear (csrc/tn_fill.hip: one linear stream per array, no per-row lookups; the tracer's own tail fill with option
+ * "fill_blocks" = -2): what a caller that traced with TN_TRACE_COMPACT_ROWS runs if it later needs dense rows, and what bench.py
  * times to learn the write rate THIS box sustains (the ceiling of a trace_rays call, whose bytes are 88 % constant tails). */
 int tn_fill_rows(size_t num_rays, uint32_t max_ray_triangles, uint32_t first_slot, uint32_t *visited, float *bary, float *dist,
                  uint32_t *verts, void *stream);
@@ -275,7 +277,7 @@ int tn_fill_rows(size_t num_rays, uint32_t max_ray_triangles, uint32_t first_slo
  *   "spec_fill"  1 = the last quarter / half of every row (slots no ray, or hardly any ray, of this mesh reaches) is filled
  *             beside the walk on a stream of its own (the schedule of rounds 2-5); 0 (default since round 6) = the whole
  *             tail fill after the segment writer.  "spec_k0" = first speculatively filled slot (multiple of 32; 0 = the
- *             rule of tn_api.hip) -- tests force it low so that rays of every class overwrite speculatively filled slots;
+ *             rule of csrc/tn_api_tracer.hip: spec_fill_first_slot) -- tests force it low so that rays of every class overwrite speculatively filled slots;
  *             "spec_blocks" (512) = grid of that fill, "walk_lds_kb" (26) = dynamic LDS reserved per walk block beside it
  *   "fill_blocks"  grid of the tail fill: -1 (default) = one block per row (k_fill_rows_fine), -2 = one linear stream per
  *             array with one store per thread (k_fill_linear: what tn_fill_rows uses), n > 0 = n blocks of persistent waves

@@ -45,6 +45,28 @@ inline void allow_dynamic_lds(const void *kernel, size_t bytes) {
     TN_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
 }
 
+// Slots of the tracer's 64-bit statistics array of the last trace call (TraceParams::stats).  Host and device code address
+// it by these names only.
+constexpr int STAT_WALK = 0;            // [0..4) tn_trace_stats: rays the walk certified and ...
+constexpr int STAT_OTHER = 1;           //        ... all other rays (both derived on the host from the device-side counts)
+constexpr int STAT_LITERAL_BRANCH = 2;  //        rays whose post-process ran the serial literal branch
+constexpr int STAT_OVERFLOW = 3;        //        rays with more than M - 1 hits
+constexpr int STAT_REASON = 4;          // [4..20) tn_trace_flag_reasons: STAT_REASON + reason (the walk's 1..12, REASON_* below)
+constexpr int STAT_DIAG_NODES = 22;     // [20..24) diagnostics of the BVH path: nodes visited, ...
+constexpr int STAT_DIAG_LEAVES = 23;    //          ... leaves tested
+constexpr int STAT_RISK_HULL = 24;      // [24..28) tn_trace_cross_check: certified rays inside the wide band of a hull edge (only), ...
+constexpr int STAT_RISK_THIN = 25;      //          ... of an edge of a thin-neighbourhood tet,
+constexpr int STAT_RISK_CHECKED = 26;   //          risk rays re-counted (those not already in the blind sample), ...
+constexpr int STAT_RISK_BAD = 27;       //          ... and those whose count differed
+constexpr int N_STATS = 32;
+static_assert(STAT_RISK_THIN == STAT_RISK_HULL + 1, "k_trace_walk indexes the two risk classes from STAT_RISK_HULL");
+// the hand-over reasons that are addressed individually (include/tetranerf_hip.h lists all sixteen)
+constexpr int N_REASONS = 16;
+constexpr int REASON_ORDER = 7;         // sound chain whose order is not certified
+constexpr int REASON_LITERAL_PAIRED = 13; // ... of those, rays paired from their logged hits (k_postprocess_log)
+constexpr int REASON_VERIFY_BAD = 14;   // blind sample of the count cross-check: mismatches
+constexpr int REASON_VERIFY_CHECKED = 15; // ... rays checked
+
 constexpr int WIDE = 64;            // BVH branching factor = wavefront width
 constexpr int STACK_CAP = 64 * 6;   // traversal stack entries per wave
 

@@ -4,6 +4,22 @@
 
 namespace tn {
 
+// The five output arrays of a trace call.  Rows::at is the only place on the host where the dwords per slot of the row
+// arrays (cells 1, bary 6, dist 2, verts 4) are written: every parameter block and the fill launcher take their row
+// pointers from a Rows.
+struct Rows {
+    uint32_t *num;             // [R] (null where no kernel of the launch reads or writes it)
+    uint32_t *cells;           // [R,M]
+    float *bary;               // [R,M,2,3]
+    float *dist;               // [R,M,2]
+    uint32_t *verts;           // [R,M,4] or null
+    uint32_t M;
+    Rows at(size_t base) const {   // the rows from ray `base` on
+        return Rows{num ? num + base : nullptr, cells + base * M, bary + base * M * 6, dist + base * M * 2,
+                    verts ? verts + base * M * 4 : nullptr, M};
+    }
+};
+
 struct TraceParams {
     const float *origins;      // [R,3]
     const float *dirs;         // [R,3]
@@ -85,7 +101,7 @@ void launch_verify_counts(const TraceParams &p, uint32_t stride, uint32_t *walk_
 
 // hit log -> rows of the rays the walk certified (walk_n[ray] != TN_EMPTY): k_write_segments writes the segment records
 // + the tail constants up to the next multiple of 32 slots (a 128-byte line boundary in all four row arrays);
-// k_fill_range streams the rest of the constant tails.  Every byte is written once.
+// the tail fill (launch_fill below) streams the rest of the constant tails.  Every byte is written once.
 struct WriteParams {
     size_t num_rays;
     uint32_t M;
@@ -100,12 +116,15 @@ struct WriteParams {
     uint32_t *out_verts;       // nullable
 };
 void launch_write_segments(const WriteParams &q, hipStream_t stream, unsigned max_blocks = 0);
-// all_rows: slots [k_split, M) of every row; otherwise slots [ceil32(out_num[r]), k_split) of the certified rows
-constexpr unsigned FILL_FINE = 0xFFFFFFFFu;   // max_blocks value: one block per row (k_fill_rows_fine)
-constexpr unsigned FILL_LINEAR = 0xFFFFFFFEu; // max_blocks value: one linear stream per array, one store per thread (k_fill_linear)
-void launch_fill_range(size_t num_rays, uint32_t M, bool all_rows, const uint32_t *walk_n, const uint32_t *out_num,
-                       uint32_t *out_cells, float *out_bary, float *out_dist, uint32_t *out_verts, hipStream_t stream,
-                       uint32_t k_split, bool nontemporal, unsigned max_blocks = 0);
+// The constant tails (tn_fill.hip).  all_rows: slots [k_split, M) of every row; otherwise slots [ceil32(rows.num[r]), k_split)
+// of the certified rows (walk_n[r] != TN_EMPTY).  Three kernels write the same bytes:
+enum class FillKind {
+    Spans,        // k_fill_range: persistent waves that own spans of rows; grid = `blocks` (0: 2048 for all_rows, else 512)
+    RowPerBlock,  // k_fill_rows_fine: one short-lived block per row
+    Linear,       // k_fill_linear: one linear stream per array, one store per thread
+};
+struct FillRange { bool all_rows; uint32_t k_split; bool nontemporal; FillKind kind; unsigned blocks; };   // blocks: Spans only
+void launch_fill(const Rows &rows, size_t num_rays, const uint32_t *walk_n, const FillRange &f, hipStream_t stream);
 
 // sample -> segment matching (tn_match.hip)
 void launch_find_matched_cells(size_t R, size_t S, size_t M, const uint32_t *num_visited,
@@ -140,7 +159,7 @@ struct MlpWeights {
     const float *wr, *br;  // [3,128],   [3]     rgb head (+ sigmoid)
 };
 // The packed forms of one set of weights (tn_mlp_set_weights packs them once per parameter version) + the scratch the
-// kernels need beside them.  Everything is device memory owned by the tn_mlp handle (tn_api.hip).
+// kernels need beside them.  Everything is device memory owned by the tn_mlp handle (tn_api_mlp.hip).
 struct MlpPacks {
     const float *pk_plain;     // fp32 MFMA forward, layer-1 K order of a [64, n] feature-major input
     const float *pk_gather;    // the same with layer-1 K order of the fused gather (forward, render pass, backward)

@@ -130,7 +130,7 @@ __device__ void postprocess_and_write(const WaveSmem &s, uint32_t nh, uint32_t M
         //    on, and keeps going while the current slot is anomalous or at or below the highest slot a swap has touched;
         //    every other step takes the plain result computed by all lanes in parallel.
         // Same results as running both phases over all slots (round 2a did: ~260 serial iterations x 2 per ray).
-        if (stats && lane == 0) atomicAdd(&stats[2], 1ull);
+        if (stats && lane == 0) atomicAdd(&stats[STAT_LITERAL_BRANCH], 1ull);
         auto Tk = [](uint64_t k) { return __uint_as_float((uint32_t)(k >> 32)); };
         auto T = [&](uint32_t j) { return Tk(s.key[j]); };
         auto ID = [&](uint32_t j) { return (uint32_t)s.key[j]; };
@@ -418,7 +418,7 @@ __device__ uint32_t collect_hits(const WideBvh &bvh, WaveSmem &s, uint32_t M, ui
         auto run_leaves = [&]() {
             wave_sync();
             if (nleaf == 0) return;
-            if (lane == 0 && stats) atomicAdd(&stats[23], (unsigned long long)nleaf);
+            if (lane == 0 && stats) atomicAdd(&stats[STAT_DIAG_LEAVES], (unsigned long long)nleaf);
             // one wave instruction tests G = 64 / leaf_w crossed leaves: lane = (leaf of the group, triangle slot)
             const uint32_t LW = bvh.leaf_w, LS = bvh.leaf_shift, G = 64u >> LS;
             const uint32_t sub = (uint32_t)lane >> LS, in = (uint32_t)lane & (LW - 1);
@@ -474,7 +474,7 @@ __device__ uint32_t collect_hits(const WideBvh &bvh, WaveSmem &s, uint32_t M, ui
                 wave_sync();  // everyone has read the top before it can be overwritten
                 load_node(nidx, nbx, nch);
             }
-            if (lane == 0 && stats) atomicAdd(&stats[22], 1ull);
+            if (lane == 0 && stats) atomicAdd(&stats[STAT_DIAG_NODES], 1ull);
             const bool hit = cch != TN_EMPTY && line_box(ox, oy, oz, ix, iy, iz, cbx[0], cbx[1], cbx[2], cbx[3], cbx[4], cbx[5], pad);
             const bool to_leaf = hit && (cch >> 31) != 0, to_node = hit && (cch >> 31) == 0;
             const uint64_t ml = __ballot(to_leaf), mn = __ballot(to_node);
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(64) void k_trace_general(TraceParams p) {
             if (lane == 0) p.overflow_list[atomicAdd(p.overflow_count, 1u)] = (uint32_t)ray;
             continue;
         }
-        if (overflow && lane == 0 && p.stats) atomicAdd(&p.stats[3], 1ull);
+        if (overflow && lane == 0 && p.stats) atomicAdd(&p.stats[STAT_OVERFLOW], 1ull);
 
         sort_hits(s, nh, lane);
 #if TN_WALK_DIAG
@@ -635,7 +635,7 @@ __global__ __launch_bounds__(64) void k_postprocess_log(TraceParams p, const Wal
         postprocess_and_write(s, nh, M, p.faces, p.face_tets, p.out_num + ray, p.out_cells + ray * M,
                               p.out_bary + ray * M * 6, p.out_dist + ray * M * 2,
                               p.out_verts ? p.out_verts + ray * M * 4 : nullptr, p.stats, lane, p.compact_rows != 0);
-        if (lane == 0 && p.stats) atomicAdd(&p.stats[4 + 13], 1ull);
+        if (lane == 0 && p.stats) atomicAdd(&p.stats[STAT_REASON + REASON_LITERAL_PAIRED], 1ull);
         wave_sync();
     }
 }
@@ -648,7 +648,7 @@ __global__ __launch_bounds__(64) void k_postprocess_log(TraceParams p, const Wal
 // BVH finds (count only: no sort, no pairing) must equal the number of hits the walk logged.  A mismatch is counted
 // (reason 14) and the ray is handed to the BVH kernel like any other fallback ray -- the kernels that write rows are
 // launched after this one.  reason 15 counts the rays checked.
-// LATE form (late != 0; the default schedule of a one-chunk call, tn_api.hip): the check runs on a side stream BESIDE
+// LATE form (late != 0; the default schedule of a one-chunk call, tn_api_tracer.hip): the check runs on a side stream BESIDE
 // the segment writer and the tail fill instead of in front of them, so walk_n is left alone (the row of a mismatching ray is
 // written as certified) and the ray goes to a list of its own, which one more BVH launch re-traces -- whole rows -- after
 // everything else of the call has been joined.
@@ -661,7 +661,8 @@ __global__ __launch_bounds__(64) void k_verify_counts(TraceParams p, uint32_t st
     const int lane = threadIdx.x;
     // every stride-th ray (the blind sample), or exactly the rays of a list (the walk's risk list: its count lives on the device)
     const size_t n_checks = ray_list ? (size_t)*list_count : (p.num_items + stride - 1) / stride;
-    const int c_checked = ray_list ? 26 : 4 + 15, c_bad = ray_list ? 27 : 4 + 14;
+    const int c_checked = ray_list ? STAT_RISK_CHECKED : STAT_REASON + REASON_VERIFY_CHECKED,
+              c_bad = ray_list ? STAT_RISK_BAD : STAT_REASON + REASON_VERIFY_BAD;
     for (size_t it = blockIdx.x; it < n_checks; it += gridDim.x) {
         const size_t ray = ray_list ? (size_t)ray_list[it] : it * stride;
         if (ray_list && stride && ray % stride == 0) continue;   // the blind sample checks (and counts) this one
