@@ -97,8 +97,19 @@ int tn_trace_rays(tn_tracer_t tracer, size_t num_rays, uint32_t max_ray_triangle
  * tn_find_matched_cells_indexed): 52 B per segment instead of 52*M B per ray.  A per-call argument rather than a tracer
  * option, so that threads sharing a tracer (nerfstudio's viewer and trainer share the model) cannot see each other's
  * choice.  Calls on ONE tracer handle are serialised inside the library (a per-tracer mutex around the host section: the
- * tracer's scratch buffers, counters, side streams and events are shared state); their kernels queue on the streams. */
+ * tracer's scratch buffers, counters, side streams and events are shared state); their kernels queue on the streams.
+ *
+ * TN_TRACE_BIN_RAYS (combines with TN_TRACE_COMPACT_ROWS): for batches of INCOHERENT rays (random pixels over many cameras).  The
+ * library walks the rays in a locality order of its own -- a stable radix sort on a 30-bit key of (origin, direction, mesh
+ * box): Morton cell of the origin, then Morton cell of the point of the ray's line closest to the centre of the mesh;
+ * stated in tetra-nerf_amd/ray_order.py, computed by csrc/tn_ray_order.hip -- and still writes every output row at the
+ * caller's ray index: the five arrays are bit for bit those of an unbinned call, and tn_trace_stats / tn_trace_flag_reasons /
+ * tn_trace_cross_check report the same numbers.  Eligible is a call that takes the walk path as ONE chunk; a small batch on
+ * the BVH path (below "walk_min_rays") and a call processed in ray chunks ("log_cap_mb") ignore the flag and produce the
+ * same rows.  Costs 20 bytes of scratch per ray + the sort's temporary storage, allocated at the first binned call.
+ * Option "bin_rays" = 1 / TETRANERF_HIP_BIN_RAYS=1 bins every eligible call without the flag. */
 #define TN_TRACE_COMPACT_ROWS 1u
+#define TN_TRACE_BIN_RAYS 2u
 int tn_trace_rays_ex(tn_tracer_t tracer, size_t num_rays, uint32_t max_ray_triangles,
                      const float *origins, const float *directions, uint32_t *num_visited,
                      uint32_t *visited, float *bary, float *dist, uint32_t *verts, uint32_t flags, void *stream);
@@ -249,8 +260,15 @@ int tn_trace_cross_check(tn_tracer_t tracer, uint64_t out[8]);
  * with that option the kernels of a call are enqueued on the CALLER's stream in program order with a timing event after each
  * (a normal call overlaps them on four streams, so its parts do not add up to its duration).  ms[0..7] = speculative tail fill,
  * adjacency walk, BVH re-trace of the fallback rays, count cross-check, segment writer, literal pairing of the logged hits,
- * tail fill, re-trace of cross-check mismatches.  Waits for the call to finish. */
+ * tail fill, re-trace of cross-check mismatches.  A binned call (TN_TRACE_BIN_RAYS) counts its key kernel and its sort in
+ * ms[1], with the hull entry search and the walk.  Waits for the call to finish. */
 int tn_trace_timings(tn_tracer_t tracer, float ms[8]);
+
+/* test / diagnostic aid: the order in which the LAST tn_trace_rays* call on this tracer walked its rays, copied to the host:
+ * order_host[i] = caller index of the i-th walked ray.  *n receives the ray count when that call was binned
+ * (TN_TRACE_BIN_RAYS or option "bin_rays", and eligible) and 0 when it was not; order_host may be NULL (size query).
+ * Waits for the call's stream, like tn_trace_stats. */
+int tn_trace_ray_order(tn_tracer_t tracer, uint32_t *order_host, size_t *n);
 
 /* The constant tails of the dense reference rows (py_binding.cpp:53-57: torch::zeros / full(-1) of the five outputs) for slots
  * [first_slot, M) of EVERY row: visited / verts = 0xFFFFFFFF, bary / dist = 0.  first_slot must be a multiple of 32 (a 128-byte
@@ -261,7 +279,8 @@ int tn_trace_timings(tn_tracer_t tracer, float ms[8]);
 int tn_fill_rows(size_t num_rays, uint32_t max_ray_triangles, uint32_t first_slot, uint32_t *visited, float *bary, float *dist,
                  uint32_t *verts, void *stream);
 
-/* knobs ("walk" and "gpu_build" also through the environment: TETRANERF_HIP_WALK, TETRANERF_HIP_GPU_BUILD):
+/* knobs ("walk", "gpu_build" and "bin_rays" also through the environment, read at tn_tracer_create: TETRANERF_HIP_WALK,
+ * TETRANERF_HIP_GPU_BUILD, TETRANERF_HIP_BIN_RAYS):
  *   "walk"    1 = adjacency-walk fast path with general-path fallback (default),
  *             0 = general all-hits path for every ray, 2 = walk for any batch size
  *   "walk_min_rays"  smallest batch the walk is used for (default 12288; 8192 from 2M tets, 6144 from 4M tets on until
@@ -305,6 +324,7 @@ int tn_fill_rows(size_t num_rays, uint32_t max_ray_triangles, uint32_t first_slo
  *   "verify_risk"  1 (default) = every certified ray of the RISK classes is cross-checked as well (tn_trace_cross_check); 0 = only
  *             the blind sample.  "risk_band" (default 2) = width of the classes' band in units of the guards' own 8 rounding
  *             distances (2: rays between 8 and 16; measured cost in DESIGN.md section 2)
+ *   "bin_rays"  0 (default) / 1 = every eligible tn_trace_rays* call is binned, as if it carried TN_TRACE_BIN_RAYS (see there)
  *   "timing"  1 = serialise the kernels of a one-chunk walk call on the caller's stream with timing events (tn_trace_timings);
  *             0 (default) = the overlapped four-stream schedule
  *   "writer_table"  0 (default) = the segment writer's record table by mesh size (one record per (tet, entry face) below

@@ -26,6 +26,7 @@ SYMBOLS = (
     "tn_mlp_forward", "tn_mlp_forward_gather", "tn_composite", "tn_gather_uint32", "tn_scatter_ema_uint32",
     "tn_mlp_forward_gather_train", "tn_mlp_backward", "tn_mlp_ray_head_grad", "tn_mlp_param_grads", "tn_composite_backward", "tn_sample_coarse", "tn_sample_pdf",
     "tn_trace_timings", "tn_trace_cross_check", "tn_fill_rows", "tn_compact_hits", "tn_render_rays", "tn_render_rays_ex",
+    "tn_trace_ray_order",
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -80,6 +81,7 @@ def load():
     lib.tn_set_option.argtypes = [vp, C.c_char_p, i32]
     lib.tn_trace_timings.argtypes = [vp, C.POINTER(C.c_float * 8)]
     lib.tn_trace_cross_check.argtypes = [vp, C.POINTER(C.c_uint64 * 8)]
+    lib.tn_trace_ray_order.argtypes = [vp, vp, C.POINTER(sz)]
     lib.tn_fill_rows.argtypes = [sz, u32, u32, vp, vp, vp, vp, vp]
     lib.tn_mlp_create.argtypes = [i32, C.POINTER(vp)]
     lib.tn_mlp_destroy.argtypes = [vp]

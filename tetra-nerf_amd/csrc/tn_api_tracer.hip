@@ -66,6 +66,7 @@ struct tn_tracer {
         bool verify_inject = false;          // tests: every cross-checked ray counts as a mismatch
         unsigned literal_sort_passes = 8;    // odd-even passes over a literal ray's hits before the bitonic network (tests: 0, 1)
         int cert_ends = 2;                   // the walk's order test; 2: rules A-C below WALK_TET_MIN_TETS tets, the cluster test above (r06m_sweep*.txt)
+        bool bin_rays = false;               // every eligible call is binned, as if it carried TN_TRACE_BIN_RAYS (TETRANERF_HIP_BIN_RAYS)
         bool timing = false;                 // one-chunk calls serialised on the caller's stream, an event after each kernel (tn_trace_timings)
     } opt;
 
@@ -78,6 +79,9 @@ struct tn_tracer {
         tn::DevBuf<uint4> hit_log;           // walk -> segment writer / literal pairing: 16 B per recorded hit, [rays / 64][M][64]
         tn::DevBuf<uint32_t> verify_list;    // [R] certified rays whose count differed: re-traced by the BVH kernel at the end of the call
         tn::DevBuf<uint32_t> risk_list;      // [R] certified rays inside the wide band of a certification guard (all cross-checked)
+        // binned calls only (tn_ray_order.hip): the sort's input and output, its temporary storage, walk_n in item order
+        tn::DevBuf<uint32_t> ray_keys, ray_iota, ray_keys_sorted, order, walk_n_item;   // [R] each
+        tn::DevBuf<char> sort_temp;
         static constexpr int N_CTR = 2;      // 64-bit words behind the statistics: four uint32 device-side counts
         tn::DevBuf<unsigned long long> stats;   // [tn::N_STATS] counters (tn_common.h: STAT_*) + the four counts (one memset clears all)
         uint32_t *fallback_count() { return reinterpret_cast<uint32_t *>(stats.p + tn::N_STATS); }
@@ -88,6 +92,7 @@ struct tn_tracer {
         // what the counters belong to
         size_t last_num_rays = 0;
         bool last_walk = false;
+        bool last_binned = false;            // the last call walked its rays in the order scratch.order holds (tn_trace_ray_order)
         hipStream_t last_stream = nullptr;
 
         template <typename T>
@@ -96,12 +101,16 @@ struct tn_tracer {
         // the overlapped schedule would synchronise the device there (hipFree / hipMalloc).  Every buffer is guarded by its
         // own size (alloc frees first: after a failed hipMalloc only that buffer is empty, and the next call grows it again).
         // R entries each: the blind sample + the risk classes can, on a degenerate mesh, name every ray.
-        void reserve(size_t R, size_t log_entries, bool verify, bool risk) {
+        void reserve(size_t R, size_t log_entries, bool verify, bool risk, size_t sort_temp_bytes = 0) {
             grow(fallback_list, R);
             if (!log_entries) return;        // small batch: the overflow list only
             grow(walk_n, R); grow(literal_list, R); grow(hull_entry, R); grow(hit_log, log_entries);
             if (verify) grow(verify_list, R);
             if (risk) grow(risk_list, R);
+            if (sort_temp_bytes) {           // binned call
+                grow(ray_keys, R); grow(ray_iota, R); grow(ray_keys_sorted, R); grow(order, R); grow(walk_n_item, R);
+                grow(sort_temp, sort_temp_bytes);
+            }
         }
     } scratch;
 
@@ -199,6 +208,7 @@ struct TraceCall {
     tn::Rows rows;                           // the caller's five outputs
     bool dense_tails;                        // per CALL (TN_TRACE_COMPACT_ROWS), not per tracer
     hipStream_t stream;                      // the caller's
+    bool binned = false;                     // run_overlapped walks the rays in the order of their keys (TN_TRACE_BIN_RAYS)
 
     const tn_tracer::Options &o() const { return t->opt; }
     tn_tracer::Scratch &s() const { return t->scratch; }
@@ -259,6 +269,7 @@ struct TraceCall {
         w.literal_list = o().literal ? s().literal_list.p : nullptr; w.literal_count = s().literal_count();
         w.risk_list = verify_risk() ? s().risk_list.p : nullptr; w.risk_count = s().risk_count();
         w.risk_band = (float)o().risk_band;
+        if (binned) { w.order = s().order.p; w.walk_n_item = s().walk_n_item.p; }
         w.cert_ends = o().cert_ends == 2 ? (m.T >= tn::WALK_TET_MIN_TETS ? 1u : 3u) : (uint32_t)o().cert_ends;
         return w;
     }
@@ -270,6 +281,7 @@ struct TraceCall {
         q.hit_log = s().hit_log.p;
         q.cold = mesh().cold; q.tets = mesh().tets;
         q.out_cells = r.cells; q.out_bary = r.bary; q.out_dist = r.dist; q.out_verts = r.verts;
+        if (binned) { q.walk_n = s().walk_n_item.p; q.order = s().order.p; }   // (one chunk: base == 0)
         return q;
     }
 
@@ -282,7 +294,8 @@ struct TraceCall {
     }
     void pair_literal(size_t base, size_t n, hipStream_t st) const {
         if (!o().literal) return;
-        tn::launch_postprocess_log(trace_params(base, n), mesh().fidt, s().hit_log.p, s().literal_list.p, s().literal_count(), n, st);
+        tn::launch_postprocess_log(trace_params(base, n), mesh().fidt, s().hit_log.p, s().literal_list.p, s().literal_count(), n, st,
+                                   binned ? s().order.p : nullptr);
     }
     void trace_listed(const uint32_t *list, const uint32_t *count, size_t max_items, hipStream_t st) const {   // BVH kernel: whole rows
         tn::TraceParams q = trace_params(0, max_items);
@@ -321,6 +334,9 @@ struct TraceCall {
     // Everything that writes rows is ordered behind the speculative fill, so a ray with more than K0 segments (or a
     // literal / fallback row) simply overwrites its slots.  Option "timing": the same kernels, serialised on the caller's
     // stream with a timing event (mark) after each.  Orders that were measured and lost: last section of profiles/HISTORY.md.
+    // A binned call puts the key kernel and the sort in front of the walk (same stream; counted with the walk under "timing")
+    // and hands `order` to the walk, the writer and the literal pairing; every other launch sees rows and lists in the
+    // caller's order and is the same launch as in an unbinned call.
     void run_overlapped() const {
         tn_tracer::Schedule &c = t->sched;
         const bool timing = o().timing;
@@ -340,6 +356,9 @@ struct TraceCall {
             TN_HIP(hipEventRecord(c.ev_pre, s_pre));
         }
         mark();                                                   // 1: speculative fill
+        if (binned)
+            tn::launch_ray_order(R, origins, dirs, tn::ray_key_box(mesh().box_lo, mesh().box_hi), s().ray_keys.p, s().ray_iota.p,
+                                 s().ray_keys_sorted.p, s().order.p, s().sort_temp.p, s().sort_temp.n, stream);
         // beside a speculative fill the walk's occupancy is limited, so that both stay resident (Options::walk_lds_kb)
         tn::launch_trace_walk(walk_params(0, R), stream, K0 && !timing ? (size_t)o().walk_lds_kb * 1024 : 0);
         mark();                                                   // 2: walk
@@ -442,6 +461,7 @@ int tn_tracer_create(int device, tn_tracer_t *out) {
         t->device = device;
         t->opt.use_walk = tn::env_flag("TETRANERF_HIP_WALK", true) ? 1 : 0;
         t->opt.gpu_build = tn::env_flag("TETRANERF_HIP_GPU_BUILD", true);
+        t->opt.bin_rays = tn::env_flag("TETRANERF_HIP_BIN_RAYS", false);
         t->scratch.stats.alloc(tn::N_STATS + tn_tracer::Scratch::N_CTR);
         TN_HIP(hipMemset(t->scratch.stats.p, 0, tn_tracer::Scratch::stats_bytes()));
         tn_tracer::Schedule &c = t->sched;
@@ -521,6 +541,7 @@ int tn_load_tetrahedra(tn_tracer_t tracer, size_t V, size_t T, const float *xyz,
         m.hull_nodes = reinterpret_cast<const float4 *>(b.hull_nodes.p);
         m.hull_tris = reinterpret_cast<const float4 *>(b.hull_tris.p);
         m.n_hull_nodes = (uint32_t)n.n_hull_nodes;
+        tn::mesh_box(V, T, xyz, cells, m.box_lo, m.box_hi, stream);   // one kernel for both builds: the same six numbers
         b.loaded = true;
     });
 }
@@ -601,7 +622,7 @@ int tn_trace_rays_ex(tn_tracer_t tracer, size_t R, uint32_t M, const float *orig
     return guarded([&] {
         tn_tracer *t = checked(tracer);
         std::lock_guard<std::mutex> lock(t->mu);
-        if (flags & ~(uint32_t)TN_TRACE_COMPACT_ROWS) throw tn::Error("unknown trace flag");
+        if (flags & ~(uint32_t)(TN_TRACE_COMPACT_ROWS | TN_TRACE_BIN_RAYS)) throw tn::Error("unknown trace flag");
         check_pow2_M(M);
         check_loaded(t->mesh.loaded);
         if (M > 4096) throw tn::Error("max_ray_triangles larger than 4096 is not supported");
@@ -611,16 +632,20 @@ int tn_trace_rays_ex(tn_tracer_t tracer, size_t R, uint32_t M, const float *orig
             throw tn::Error("null ray / output pointer");
         DeviceGuard g(t->device);
         // dense_tails per CALL, not per tracer: a viewer thread and a trainer sharing one tracer may ask for different row forms
-        const TraceCall call{t, R, origins, directions, tn::Rows{num_visited, visited, bary, dist, verts, M},
+        TraceCall call{t, R, origins, directions, tn::Rows{num_visited, visited, bary, dist, verts, M},
                              t->opt.dense_tails && !(flags & TN_TRACE_COMPACT_ROWS), (hipStream_t)stream_};
         tn_tracer::Scratch &s = t->scratch;
         TN_HIP(hipMemsetAsync(s.stats.p, 0, tn_tracer::Scratch::stats_bytes(), call.stream));
         s.last_stream = call.stream;
         s.last_num_rays = R;
         s.last_walk = call.use_walk();
+        s.last_binned = false;
         if (s.last_walk) {
             const size_t chunk = call.log_chunk();
-            s.reserve(R, (chunk + 255) / 256 * 256 * (size_t)M, t->opt.verify_stride != 0, call.verify_risk());
+            // binned: only a call that walks all its rays as one chunk (the BVH path and chunked calls ignore the flag)
+            call.binned = s.last_binned = ((flags & TN_TRACE_BIN_RAYS) || t->opt.bin_rays) && chunk >= R;
+            s.reserve(R, (chunk + 255) / 256 * 256 * (size_t)M, t->opt.verify_stride != 0, call.verify_risk(),
+                      call.binned ? tn::ray_order_temp_bytes(R) : 0);
             if (chunk >= R) call.run_overlapped();
             else call.run_chunked(chunk);
         } else {
@@ -749,6 +774,20 @@ int tn_trace_cross_check(tn_tracer_t tracer, uint64_t out[8]) {
     });
 }
 
+int tn_trace_ray_order(tn_tracer_t tracer, uint32_t *order_host, size_t *n) {
+    return guarded([&] {
+        tn_tracer *t = checked(tracer);
+        std::lock_guard<std::mutex> lock(t->mu);
+        if (!n) throw tn::Error("n is null");
+        const tn_tracer::Scratch &s = t->scratch;
+        *n = s.last_binned ? s.last_num_rays : 0;
+        if (!order_host || !*n) return;
+        DeviceGuard g(t->device);
+        TN_HIP(hipStreamSynchronize(s.last_stream));
+        TN_HIP(hipMemcpy(order_host, s.order.p, *n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    });
+}
+
 int tn_trace_timings(tn_tracer_t tracer, float ms[8]) {
     return guarded([&] {
         tn_tracer *t = checked(tracer);
@@ -792,6 +831,7 @@ int tn_set_option(tn_tracer_t tracer, const char *name, int value) {
         };
         const std::string k = name ? name : "";
         if (k == "gpu_build") o.gpu_build = value != 0;
+        else if (k == "bin_rays") o.bin_rays = value != 0;
         else if (k == "timing") { o.timing = value != 0; t->sched.tev_valid = false; }
         else if (k == "leaf_width") {
             if (value != 16 && value != 32 && value != 64) throw tn::Error("leaf_width must be 16, 32 or 64");

@@ -194,6 +194,7 @@ struct DeviceMesh {
     const float4 *hull_tris = nullptr;   // 3 float4 per hull face
     uint32_t n_hull_nodes = 0;
     uint32_t n_hull = 0;
+    float box_lo[3] = {0.f, 0.f, 0.f}, box_hi[3] = {0.f, 0.f, 0.f};   // min / max of the referenced vertices (the key of a binned call)
 };
 
 // host-side build products (tn_mesh.cpp)

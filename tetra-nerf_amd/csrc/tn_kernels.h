@@ -1,6 +1,7 @@
 // tn_kernels.h -- host-callable launchers of the HIP kernels.
 #pragma once
 #include "tn_common.h"
+#include "tn_ray_key.h"
 
 namespace tn {
 
@@ -82,13 +83,19 @@ struct WalkParams {
     uint32_t *risk_count;      // [1]          them is cross-checked (k_verify_counts); null: not collected
     float risk_band;           // width of that band in units of the guards' own 8 delta (tn option "risk_band")
     uint32_t cert_ends;        // the order test: 0 round 5's pairwise test, 3 the same + the end-of-chain rules A-C, 1 round 6's cluster test (A-D)
+    // binned call (launch_ray_order below): item i of the launch is the caller's ray order[i].  The hit log, hull_entry,
+    // literal_list and walk_n_item are indexed by ITEM; origins / dirs, the rows, out_num, walk_n and the fallback / risk
+    // lists by the caller's RAY index.  null: item == ray
+    const uint32_t *order;     // [num_items]
+    uint32_t *walk_n_item;     // [num_items] walk_n in item order, for the segment writer (binned calls only)
 };
 // lds_reserve: bytes of (unused) dynamic LDS per block = an occupancy limit (160 KB / lds_reserve blocks per CU), 0 = none
 void launch_trace_walk(const WalkParams &p, hipStream_t stream, size_t lds_reserve = 0);
 // literal sort + pairing of the logged hits of the rays in literal_list (tn_trace_general.hip); rows of launch item i
 // are p.out_*[i] (the TraceParams of the same walk launch)
+// order (nullable): binned call -- the log is read by item, the rows are those of ray order[item]
 void launch_postprocess_log(const TraceParams &p, const WalkFid *fidt, const uint4 *hit_log, const uint2 *literal_list,
-                            const uint32_t *literal_count, size_t max_items, hipStream_t stream);
+                            const uint32_t *literal_count, size_t max_items, hipStream_t stream, const uint32_t *order = nullptr);
 
 // count-only BVH cross-check of every stride-th certified ray (tn_trace_general.hip: k_verify_counts); p = the
 // TraceParams of the walk launch; mismatching rays are appended to the fallback list (global ids: ray_base + index)
@@ -114,6 +121,7 @@ struct WriteParams {
     float *out_bary;
     float *out_dist;
     uint32_t *out_verts;       // nullable
+    const uint32_t *order;     // binned call: walk_n and the log are in item order, item i writes the row of ray order[i]; null: item == ray
 };
 void launch_write_segments(const WriteParams &q, hipStream_t stream, unsigned max_blocks = 0);
 // The constant tails (tn_fill.hip).  all_rows: slots [k_split, M) of every row; otherwise slots [ceil32(rows.num[r]), k_split)
@@ -125,6 +133,16 @@ enum class FillKind {
 };
 struct FillRange { bool all_rows; uint32_t k_split; bool nontemporal; FillKind kind; unsigned blocks; };   // blocks: Spans only
 void launch_fill(const Rows &rows, size_t num_rays, const uint32_t *walk_n, const FillRange &f, hipStream_t stream);
+
+// The locality order of a binned trace_rays call (tn_ray_order.hip).  The key -- RAY_KEY_BITS bits from (origin, direction, mesh
+// box) -- is stated in tetra-nerf_amd/ray_order.py and computed by tn_ray_key.h (ray_key, RayKeyBox, ray_key_box).
+// min / max of the coordinates of the vertices that cells references (device buffers; blocking: load time)
+void mesh_box(size_t V, size_t T, const float *xyz, const uint32_t *cells, float lo[3], float hi[3], hipStream_t stream);
+// keys -> stable radix sort of (key, caller index): order[i] = caller index of the i-th ray in key order.  keys, iota,
+// keys_sorted, order: [R] each; temp: ray_order_temp_bytes(R) bytes.  Two launches + the sort's, no synchronisation.
+size_t ray_order_temp_bytes(size_t R);
+void launch_ray_order(size_t R, const float *origins, const float *dirs, const RayKeyBox &box, uint32_t *keys, uint32_t *iota,
+                      uint32_t *keys_sorted, uint32_t *order, void *temp, size_t temp_bytes, hipStream_t stream);
 
 // sample -> segment matching (tn_match.hip)
 void launch_find_matched_cells(size_t R, size_t S, size_t M, const uint32_t *num_visited,

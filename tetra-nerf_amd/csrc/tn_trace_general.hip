@@ -588,10 +588,13 @@ __global__ __launch_bounds__(64) void k_postprocess_hits(TraceParams p, const ui
 // (exit code 3: the entry hull face, id in the low bits).  The chain's faces are the ray's all-hits set (two hull
 // crossings, two crossed faces per tet, no zero edge function), so this equals the BVH path -- sort on (t, face id),
 // then the reference's phases literally (optix_trace_rays.cu:110-266) -- without a traversal.
+// BINNED: the list names ITEMS (= log rows) of a binned call; the row written is that of ray order[item].
+template <bool BINNED>
 __global__ __launch_bounds__(64) void k_postprocess_log(TraceParams p, const WalkFid *__restrict__ fidt,
                                                         const uint4 *__restrict__ hit_log,
                                                         const uint2 *__restrict__ literal_list,
-                                                        const uint32_t *__restrict__ literal_count) {
+                                                        const uint32_t *__restrict__ literal_count,
+                                                        const uint32_t *__restrict__ order) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     WaveSmem s = carve(smem, p.M);
     const int lane = threadIdx.x;
@@ -599,9 +602,10 @@ __global__ __launch_bounds__(64) void k_postprocess_log(TraceParams p, const Wal
     const size_t n_items = *literal_count;
     for (size_t it = blockIdx.x; it < n_items; it += gridDim.x) {
         const uint2 ent = literal_list[it];
-        const size_t ray = ent.x;
+        const size_t item = ent.x;
+        const size_t ray = BINNED ? (size_t)order[item] : item;
         const uint32_t nh = ent.y < M ? ent.y : M - 1;
-        const uint4 *lg = hit_log + (ray >> 6) * (size_t)M * 64 + (ray & 63);
+        const uint4 *lg = hit_log + (item >> 6) * (size_t)M * 64 + (item & 63);
         // two dependent random reads per hit (log entry -> face id of its variant): a lane's eight log entries are
         // requested together, then its eight face ids, then everything goes to LDS
         for (uint32_t base = 0; base < nh; base += 512) {
@@ -823,12 +827,16 @@ void launch_verify_counts(const TraceParams &p, uint32_t stride, uint32_t *walk_
 }
 
 void launch_postprocess_log(const TraceParams &p, const WalkFid *fidt, const uint4 *hit_log, const uint2 *literal_list,
-                            const uint32_t *literal_count, size_t max_items, hipStream_t stream) {
+                            const uint32_t *literal_count, size_t max_items, hipStream_t stream, const uint32_t *order) {
     if (max_items == 0) return;
     const size_t max_blocks = 256 * 16;
     const unsigned grid = (unsigned)(max_items < max_blocks ? max_items : max_blocks);
-    hipLaunchKernelGGL(k_postprocess_log, dim3(grid), dim3(64), wave_smem(k_postprocess_log, p.M), stream, p, fidt, hit_log,
-                       literal_list, literal_count);
+    if (order)
+        hipLaunchKernelGGL(k_postprocess_log<true>, dim3(grid), dim3(64), wave_smem(k_postprocess_log<true>, p.M), stream, p, fidt,
+                           hit_log, literal_list, literal_count, order);
+    else
+        hipLaunchKernelGGL(k_postprocess_log<false>, dim3(grid), dim3(64), wave_smem(k_postprocess_log<false>, p.M), stream, p, fidt,
+                           hit_log, literal_list, literal_count, order);
 }
 
 void launch_postprocess_hits(const TraceParams &p, const uint32_t *hit_count, const uint32_t *hit_ids,

@@ -294,6 +294,8 @@ struct OrderR6 {
 //   x = variant (record, entry face) the walk starts in, y = face id of the entry hull face,
 //   z = triangle slot of that face | first flag reason << 24 | hull near-miss risk << 28 | state << 29 (0 miss, 1 walk, 2 hand over),
 //   w = t of the OTHER crossed hull face (the chain must end there, bit for bit).
+// BINNED (p.order, tn_kernels.h): the launch index is an ITEM, the ray it reads is order[item]; the entry is stored by item.
+template <bool BINNED>
 __global__ __launch_bounds__(WALK_BLOCK) void k_hull_entry(WalkParams p) {
     const TraceParams &t = p.t;
 
@@ -308,7 +310,7 @@ __global__ __launch_bounds__(WALK_BLOCK) void k_hull_entry(WalkParams p) {
     if (lb >= nblk) return;
     const size_t ray = (size_t)lb * WALK_BLOCK + threadIdx.x;
     const bool active = ray < t.num_items;
-    const size_t rr = active ? ray : 0;
+    const size_t rr = active ? (BINNED ? (size_t)p.order[ray] : ray) : 0;
 
     const float ox = t.origins[3 * rr], oy = t.origins[3 * rr + 1], oz = t.origins[3 * rr + 2];
     const float dx = t.dirs[3 * rr], dy = t.dirs[3 * rr + 1], dz = t.dirs[3 * rr + 2];
@@ -450,7 +452,9 @@ __global__ __launch_bounds__(WALK_BLOCK) void k_hull_entry(WalkParams p) {
     }
 }
 
-template <typename Order>
+// BINNED: `ray` below is the ITEM (the log position, hull_entry, literal_list and walk_n_item are by item); everything a later
+// kernel reads by row -- out_num, walk_n, the fallback and risk lists -- takes the caller's index order[item].
+template <typename Order, bool BINNED>
 __global__ __launch_bounds__(WALK_BLOCK) void k_trace_walk(WalkParams p) {
     const TraceParams &t = p.t;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -467,7 +471,7 @@ __global__ __launch_bounds__(WALK_BLOCK) void k_trace_walk(WalkParams p) {
     if (lb >= nblk) return;
     const size_t ray = (size_t)lb * WALK_BLOCK + threadIdx.x;
     const bool active = ray < t.num_items;
-    const size_t rr = active ? ray : 0;
+    const size_t rr = active ? (BINNED ? (size_t)p.order[ray] : ray) : 0;
 
     const float ox = t.origins[3 * rr], oy = t.origins[3 * rr + 1], oz = t.origins[3 * rr + 2];
     const float dx = t.dirs[3 * rr], dy = t.dirs[3 * rr + 1], dz = t.dirs[3 * rr + 2];
@@ -662,11 +666,14 @@ __global__ __launch_bounds__(WALK_BLOCK) void k_trace_walk(WalkParams p) {
     const uint32_t nseg = nhits ? nhits - 1 - nshort - (drop2 ? 1u : 0u) : 0;
     const uint32_t wflag = drop2 ? 1u : 0u;
     if (active) {
+        const size_t cray = BINNED ? (size_t)p.order[ray] : ray;   // the caller's index
+        const uint32_t wn = (flag || !order_ok) ? TN_EMPTY : (nhits | (wflag << 30));
+        if constexpr (BINNED) p.walk_n_item[ray] = wn;
         if (flag || (!order_ok && !p.literal_list)) {
             const uint32_t slot = atomicAdd(p.fallback_count, 1u);
-            p.fallback_list[slot] = (uint32_t)(p.ray_base + ray);
+            p.fallback_list[slot] = (uint32_t)(p.ray_base + cray);
             if (t.stats) atomicAdd(&t.stats[STAT_REASON + (flag ? why : (uint32_t)REASON_ORDER)], 1ull);
-            p.walk_n[ray] = TN_EMPTY;   // the BVH kernel writes the whole row
+            p.walk_n[cray] = TN_EMPTY;   // the BVH kernel writes the whole row
         } else if (!order_ok) {
 #if TN_WALK_DIAG
             atomicAdd(&g_walk_diag[0], 1ull);
@@ -678,12 +685,12 @@ __global__ __launch_bounds__(WALK_BLOCK) void k_trace_walk(WalkParams p) {
             if (t.stats) atomicAdd(&t.stats[STAT_REASON + REASON_ORDER], 1ull);
             const uint32_t slot = atomicAdd(p.literal_count, 1u);
             p.literal_list[slot] = make_uint2((uint32_t)ray, nhits);   // index within this walk launch (= log row)
-            p.walk_n[ray] = TN_EMPTY;   // k_postprocess_log writes the whole row
+            p.walk_n[cray] = TN_EMPTY;   // k_postprocess_log writes the whole row
         } else {
-            p.walk_n[ray] = nhits | (wflag << 30);   // hits in the log (0 for a miss); bit 30: rule C (drop hit 2's segment)
-            t.out_num[ray] = nseg;
+            p.walk_n[cray] = nhits | (wflag << 30);   // hits in the log (0 for a miss); bit 30: rule C (drop hit 2's segment)
+            t.out_num[cray] = nseg;
             if (risk && p.risk_list) {  // certified, but inside the wide band of a guard: cross-checked, every one of them
-                p.risk_list[atomicAdd(p.risk_count, 1u)] = (uint32_t)ray;
+                p.risk_list[atomicAdd(p.risk_count, 1u)] = (uint32_t)cray;
                 if (t.stats) atomicAdd(&t.stats[STAT_RISK_HULL + ((risk >> 1) & 1u)], 1ull);   // hull near-miss (only) | STAT_RISK_THIN: thin neighbourhood
             }
         }
@@ -741,9 +748,16 @@ __device__ __forceinline__ void wave_lds_fence() {
 }
 }  // namespace
 
-template <int U, bool PER_TET>
+//
+// BINNED (q.order): the groups are groups of 8 consecutive ITEMS -- q.walk_n and the log are in item order, so every load above
+// stays what it is -- but the 8 rows of a group are those of rays order[8g + a], anywhere in the caller's arrays: the scalar
+// row base + 32-bit lane offsets become a 64-bit slot index per lane (the ray of a2 comes from lane a2 through a shuffle).
+// A template parameter, so that the instantiations of an unbinned call keep their addressing and their registers.
+template <int U, bool PER_TET, bool BINNED>
 __global__ __launch_bounds__(256, 2) void k_write_segments(WriteParams q) {
     using W = SW<U>;
+    using Off = std::conditional_t<BINNED, size_t, uint32_t>;   // slot index relative to g_cells / g_dist / g_bary / g_verts
+    constexpr Off NONE = ~(Off)0;
     __shared__ __attribute__((aligned(16))) uint32_t smem[4 * W::TOTAL];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -757,6 +771,10 @@ __global__ __launch_bounds__(256, 2) void k_write_segments(WriteParams q) {
     auto hits_of = [&](size_t g) -> uint32_t {             // walk_n of ray 8g + a (TN_EMPTY: not this kernel's row)
         const size_t r = 8 * g + a;
         return (g < G && r < q.num_rays) ? q.walk_n[r] : TN_EMPTY;
+    };
+    auto ray_of = [&](size_t g) -> uint32_t {              // BINNED: the caller's index of item 8g + a
+        const size_t r = 8 * g + a;
+        return (g < G && r < q.num_rays) ? q.order[r] : 0u;
     };
     auto log_of = [&](size_t g) -> const uint4 * {         // (scalar) entry k of ray 8g + a at [k * 64 + a]
         const size_t r0 = 8 * g;
@@ -776,6 +794,8 @@ __global__ __launch_bounds__(256, 2) void k_write_segments(WriteParams q) {
     size_t g_next = g + nwaves, g_next2 = G;
     uint32_t nh_raw = hits_of(g);
     uint32_t nh_next_raw = hits_of(g_next);                // in flight during the whole first group
+    uint32_t my_ray = 0, ray_next = 0;
+    if constexpr (BINNED) { my_ray = ray_of(g); ray_next = ray_of(g_next); }
     uint4 e[U];
     load_entries(e, log_of(g), nh_raw == TN_EMPTY ? 0u : (nh_raw & 0x3FFFFFFFu), 0);
     for (; g < G; g = g_next, g_next = g_next2) {
@@ -791,16 +811,22 @@ __global__ __launch_bounds__(256, 2) void k_write_segments(WriteParams q) {
         mx = __builtin_amdgcn_readfirstlane(mx);
         const uint4 *lg = log_of(g);
         // rows of the group: scalar bases (first slot of ray 8g) + 32-bit lane offsets (< 8 M slots)
-        const size_t row0 = 8 * g * (size_t)M;
+        const size_t row0 = BINNED ? 0 : 8 * g * (size_t)M;
+        auto row_of = [&](uint32_t a2) -> Off {             // first slot of the row of the group's ray a2 (every lane calls it)
+            if constexpr (BINNED) return (Off)(uint32_t)__shfl((int)my_ray, (int)a2) * M;
+            else return a2 * M;
+        };
         uint32_t *const g_cells = q.out_cells + row0;
         float *const g_dist = q.out_dist + 2 * row0;
         float *const g_bary = q.out_bary + 6 * row0;
         uint32_t *const g_verts = q.out_verts ? q.out_verts + 4 * row0 : nullptr;
-        const uint32_t row = a * M;
+        const Off row = BINNED ? (Off)my_ray * M : (Off)(a * M);
         // the group after the next: its hit counts are requested now, needed one group later
         g_next2 = g_next + nwaves;
         const uint32_t nh_next = nh_next_raw == TN_EMPTY ? 0u : (nh_next_raw & 0x3FFFFFFFu);
         const uint32_t nh_next2_raw = hits_of(g_next2);
+        uint32_t ray_next2 = 0;
+        if constexpr (BINNED) ray_next2 = ray_of(g_next2);
         uint32_t nseg = 0;
         uint4 carry = make_uint4(0u, 0u, 0u, 0u);   // hit c0 - 1 of ray a
         uint32_t c0 = 0;
@@ -886,7 +912,8 @@ __global__ __launch_bounds__(256, 2) void k_write_segments(WriteParams q) {
                 //      alone -15 % (C2 0.72 -> 0.61 ms, C4 0.95 -> 0.80 ms: profiles/r06c_lib_ab.txt)
                 constexpr uint32_t RPI = 64 / W::SLOTS;       // rays per instruction for the one-unit-per-slot arrays
                 constexpr uint32_t NQ = 8 / RPI;
-                uint32_t s_sl[NQ], s_cell[NQ];
+                Off s_sl[NQ];
+                uint32_t s_cell[NQ];
                 float2 s_dist[NQ];
                 uint4 s_vert[NQ];
 #pragma unroll
@@ -894,27 +921,29 @@ __global__ __launch_bounds__(256, 2) void k_write_segments(WriteParams q) {
                     const uint32_t a2 = RPI * qd + (uint32_t)lane / W::SLOTS, d = (uint32_t)lane % W::SLOTS;
                     const uint2 meta = *reinterpret_cast<const uint2 *>(L + W::META + 2 * a2);
                     const uint32_t at = a2 * W::STRIDE + d;
-                    s_sl[qd] = d < meta.x ? a2 * M + meta.y + d : TN_EMPTY;
+                    const Off r2 = row_of(a2);
+                    s_sl[qd] = d < meta.x ? r2 + meta.y + d : NONE;
                     s_cell[qd] = L[W::CELLS + at];
                     s_dist[qd] = *reinterpret_cast<const float2 *>(L + W::DIST + 2 * at);
                     s_vert[qd] = *reinterpret_cast<const uint4 *>(L + W::VERTS + 4 * at);
                 }
                 constexpr uint32_t UB = 3 * W::SLOTS;         // barycentrics: 3 x 8 B per slot
                 constexpr uint32_t NB = 8 * UB / 64;
-                uint32_t b_off[NB];
+                Off b_off[NB];
                 float2 b_val[NB];
 #pragma unroll
                 for (uint32_t qd = 0; qd < NB; ++qd) {
                     const uint32_t gi = 64u * qd + (uint32_t)lane;
                     const uint32_t a2 = gi / UB, d = gi - UB * a2;
                     const uint2 meta = *reinterpret_cast<const uint2 *>(L + W::META + 2 * a2);
-                    b_off[qd] = d < 3u * meta.x ? 6u * (a2 * M + meta.y) + 2u * d : TN_EMPTY;
+                    const Off r2 = row_of(a2);
+                    b_off[qd] = d < 3u * meta.x ? 6u * (r2 + meta.y) + 2u * d : NONE;
                     b_val[qd] = *reinterpret_cast<const float2 *>(L + W::BARY + 6 * (a2 * W::STRIDE) + 2 * d);
                 }
                 wave_lds_fence();                             // the staging region is free for the next iteration
 #pragma unroll
                 for (uint32_t qd = 0; qd < NQ; ++qd) {
-                    if (s_sl[qd] != TN_EMPTY) {
+                    if (s_sl[qd] != NONE) {
                         g_cells[s_sl[qd]] = s_cell[qd];
                         *reinterpret_cast<float2 *>(g_dist + 2u * s_sl[qd]) = s_dist[qd];
                         if (g_verts) *reinterpret_cast<uint4 *>(g_verts + 4u * s_sl[qd]) = s_vert[qd];
@@ -922,7 +951,7 @@ __global__ __launch_bounds__(256, 2) void k_write_segments(WriteParams q) {
                 }
 #pragma unroll
                 for (uint32_t qd = 0; qd < NB; ++qd)
-                    if (b_off[qd] != TN_EMPTY) *reinterpret_cast<float2 *>(g_bary + b_off[qd]) = b_val[qd];
+                    if (b_off[qd] != NONE) *reinterpret_cast<float2 *>(g_bary + b_off[qd]) = b_val[qd];
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) e[u] = en[u];
@@ -933,7 +962,7 @@ __global__ __launch_bounds__(256, 2) void k_write_segments(WriteParams q) {
             uint32_t n32 = (nseg + 31u) & ~31u;
             if (n32 > M) n32 = M;
             for (uint32_t sl = nseg + h; sl < n32; sl += 8) {
-                const uint32_t slot = row + sl;
+                const Off slot = row + sl;
                 g_cells[slot] = TN_EMPTY;
                 *reinterpret_cast<float2 *>(g_dist + 2u * slot) = make_float2(0.f, 0.f);
                 float2 *bp = reinterpret_cast<float2 *>(g_bary + 6u * slot);
@@ -943,6 +972,7 @@ __global__ __launch_bounds__(256, 2) void k_write_segments(WriteParams q) {
         }
         nh_raw = nh_next_raw;
         nh_next_raw = nh_next2_raw;
+        if constexpr (BINNED) { my_ray = ray_next; ray_next = ray_next2; }
     }
 }
 
@@ -952,8 +982,11 @@ void launch_write_segments(const WriteParams &q, hipStream_t stream, unsigned ma
     // grid = what is resident at once (2 blocks per CU at 192 VGPRs): the groups are dealt round-robin over it
     const size_t cap = max_blocks ? max_blocks : (size_t)256 * 2;
     if (blocks > cap) blocks = cap;
-    if (q.tets) hipLaunchKernelGGL((k_write_segments<4, true>), dim3((unsigned)blocks), dim3(256), 0, stream, q);
-    else hipLaunchKernelGGL((k_write_segments<4, false>), dim3((unsigned)blocks), dim3(256), 0, stream, q);
+    if (q.order) {
+        if (q.tets) hipLaunchKernelGGL((k_write_segments<4, true, true>), dim3((unsigned)blocks), dim3(256), 0, stream, q);
+        else hipLaunchKernelGGL((k_write_segments<4, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, q);
+    } else if (q.tets) hipLaunchKernelGGL((k_write_segments<4, true, false>), dim3((unsigned)blocks), dim3(256), 0, stream, q);
+    else hipLaunchKernelGGL((k_write_segments<4, false, false>), dim3((unsigned)blocks), dim3(256), 0, stream, q);
 }
 
 // 64-byte build records -> the three consumer tables (tn_common.h: WalkHot / WalkCold / WalkFid)
@@ -1022,14 +1055,22 @@ void launch_trace_walk(const WalkParams &p, hipStream_t stream, size_t lds_reser
     const size_t need = p.n_hull_leaves ? (size_t)(p.n_hull_groups + p.n_hull_leaves) * 32 + (size_t)p.n_hull * 48 : 0;
     // above 64 KB of dynamic LDS only by opt-in, per device (a process may hold tracers on several): set whenever it is needed
     if (need > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hull_entry), hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute(p.order ? reinterpret_cast<const void *>(&k_hull_entry<true>) : reinterpret_cast<const void *>(&k_hull_entry<false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)((HULL_FLAT_MAX / 2 + HULL_FLAT_MAX / 16) * 32 + HULL_FLAT_MAX * 48)) != hipSuccess)
         throw Error("k_hull_entry: the device refused " + std::to_string(need) + " bytes of dynamic LDS");
-    hipLaunchKernelGGL(k_hull_entry, dim3(grid), dim3(WALK_BLOCK), need, stream, p);
     if (lds_reserve > 64 * 1024) lds_reserve = 64 * 1024;
-    if (p.cert_ends == 1u) hipLaunchKernelGGL(k_trace_walk<OrderR6>, dim3(grid), dim3(WALK_BLOCK), lds_reserve, stream, p);
-    else if (p.cert_ends == 3u) hipLaunchKernelGGL(k_trace_walk<OrderR5e>, dim3(grid), dim3(WALK_BLOCK), lds_reserve, stream, p);
-    else hipLaunchKernelGGL(k_trace_walk<OrderR5>, dim3(grid), dim3(WALK_BLOCK), lds_reserve, stream, p);
+    if (p.order) {
+        hipLaunchKernelGGL(k_hull_entry<true>, dim3(grid), dim3(WALK_BLOCK), need, stream, p);
+        if (p.cert_ends == 1u) hipLaunchKernelGGL((k_trace_walk<OrderR6, true>), dim3(grid), dim3(WALK_BLOCK), lds_reserve, stream, p);
+        else if (p.cert_ends == 3u) hipLaunchKernelGGL((k_trace_walk<OrderR5e, true>), dim3(grid), dim3(WALK_BLOCK), lds_reserve, stream, p);
+        else hipLaunchKernelGGL((k_trace_walk<OrderR5, true>), dim3(grid), dim3(WALK_BLOCK), lds_reserve, stream, p);
+        return;
+    }
+    hipLaunchKernelGGL(k_hull_entry<false>, dim3(grid), dim3(WALK_BLOCK), need, stream, p);
+    if (p.cert_ends == 1u) hipLaunchKernelGGL((k_trace_walk<OrderR6, false>), dim3(grid), dim3(WALK_BLOCK), lds_reserve, stream, p);
+    else if (p.cert_ends == 3u) hipLaunchKernelGGL((k_trace_walk<OrderR5e, false>), dim3(grid), dim3(WALK_BLOCK), lds_reserve, stream, p);
+    else hipLaunchKernelGGL((k_trace_walk<OrderR5, false>), dim3(grid), dim3(WALK_BLOCK), lds_reserve, stream, p);
 }
 
 }  // namespace tn

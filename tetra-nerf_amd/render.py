@@ -349,8 +349,13 @@ class TetraRenderer:
                  max_ray_triangles: int = 512, fused: bool = True, far_plane: float = 1000.0,
                  num_fine_samples: int = 0, biased: bool = False, dense_tails: bool = False, fused_pass="auto",
                  mlp_mode: str = "fp32", background=1.0, cache_field: bool = True, device_samplers: bool = True,
-                 interpolate_values=None, sync_free_train: bool = True, sync_free_min_hits: float = None):
+                 interpolate_values=None, sync_free_train: bool = True, sync_free_min_hits: float = None,
+                 bin_rays: bool = False):
         from . import tetranerf_cpp_extension as cpp
+
+        # incoherent batches (random pixels over many cameras): the tracer walks the rays in a locality order of its own
+        # and still writes row r for ray r (trace_rays(bin_rays=True): the same rows, bit for bit)
+        self.bin_rays = bool(bin_rays)
 
         # render_train without a host synchronisation (see there); False: compact the hitting rays with torch.nonzero
         self.sync_free_train = bool(sync_free_train)
@@ -400,9 +405,12 @@ class TetraRenderer:
         """trace_rays; compact rows (a PER-CALL flag of the op: the tracer may be shared with other threads) unless this
         renderer was asked for the dense reference rows."""
         o, d = origins.contiguous(), directions.contiguous()
+        kw = {}
         if not self.dense_tails and getattr(self.tracer, "supports_compact_rows", False):
-            return self.tracer.trace_rays(o, d, self.M, compact_rows=True)
-        return self.tracer.trace_rays(o, d, self.M)
+            kw["compact_rows"] = True
+        if self.bin_rays and getattr(self.tracer, "supports_bin_rays", False):
+            kw["bin_rays"] = True
+        return self.tracer.trace_rays(o, d, self.M, **kw)
 
     @staticmethod
     def _background_rows(R, bg, dev):

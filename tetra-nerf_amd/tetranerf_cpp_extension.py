@@ -147,11 +147,15 @@ class TetrahedraTracer:
             self._h, xyz.numel() // 3, cells.numel() // 4, _ptr(xyz), _ptr(cells), _stream(self._device)))
 
     supports_compact_rows = True
+    supports_bin_rays = True
 
-    def trace_rays(self, ray_origins, ray_directions, max_ray_triangles, compact_rows: bool = False):
+    def trace_rays(self, ray_origins, ray_directions, max_ray_triangles, compact_rows: bool = False, bin_rays: bool = False):
         """PyTetrahedraTracer::trace_rays (py_binding.cpp:41-76).  compact_rows (no reference counterpart; per call):
         slots >= num_visited_cells are left unwritten (tn_trace_rays_ex + TN_TRACE_COMPACT_ROWS) for consumers that read
-        the rows only through num_visited_cells (the samplers, find_visited_cells(ray_index=...), render_rays)."""
+        the rows only through num_visited_cells (the samplers, find_visited_cells(ray_index=...), render_rays).
+        bin_rays (no reference counterpart; per call; for INCOHERENT batches): the library walks the rays in a locality
+        order of its own (TN_TRACE_BIN_RAYS; the key is ray_order.ray_keys) and writes every row at the caller's index:
+        the same five arrays, bit for bit.  Small batches on the BVH path and chunked calls ignore it (ray_order())."""
         M = int(max_ray_triangles)
         if M <= 0 or (M & (M - 1)) != 0:
             raise RuntimeError("max_ray_triangles must be a power of 2.")
@@ -169,7 +173,7 @@ class TetrahedraTracer:
             _lib.check(self._lib.tn_trace_rays_ex(
                 self._h, R, M, _ptr(ray_origins), _ptr(ray_directions), _ptr(num_visited_cells),
                 _ptr(visited_cells), _ptr(barycentric_coordinates), _ptr(hit_distances),
-                _ptr(vertex_indices), 1 if compact_rows else 0, _stream(dev)))
+                _ptr(vertex_indices), (1 if compact_rows else 0) | (2 if bin_rays else 0), _stream(dev)))
         return {
             "num_visited_cells": num_visited_cells,
             "visited_cells": visited_cells,
@@ -296,6 +300,18 @@ class TetrahedraTracer:
         return {"stride": int(arr[0]), "checked": int(arr[1]), "mismatches": int(arr[2]),
                 "risk": {"hull_near_miss_rays": int(arr[3]), "thin_neighbourhood_rays": int(arr[4]), "checked": int(arr[5]),
                          "mismatches": int(arr[6])}}
+
+    def ray_order(self):
+        """The order in which the last trace_rays call walked its rays (tn_trace_ray_order): int64 numpy array, entry i =
+        caller index of the i-th walked ray; empty when that call was not binned.  Test / diagnostic aid (synchronises)."""
+        import numpy as np
+
+        n = C.c_size_t(0)
+        _lib.check(self._lib.tn_trace_ray_order(self._h, None, C.byref(n)))
+        out = np.empty(n.value, np.uint32)
+        if n.value:
+            _lib.check(self._lib.tn_trace_ray_order(self._h, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out.astype(np.int64)
 
     TIMING_KEYS = ("speculative_fill", "walk", "bvh_fallback", "cross_check", "segment_writer", "literal_pairing", "tail_fill",
                    "cross_check_retrace")
