@@ -213,6 +213,37 @@ int tn_interpolate_values_backward_vm_det(uint32_t interpolation_dim, uint32_t n
                                           uint32_t field_dim, const uint32_t *vertex_indices, const float *barycentric,
                                           const float *grad_rows, float *field_grad_vm, void *stream);
 
+/* ---- position gradients (additions) -----------------------------------------------------------
+ * What the reference leaves open: "TODO: implement grad computation wrt barycentric coords for pose optimisation"
+ * (src/py_binding.cpp:354), and the one link it does ship as a batched PyTorch solve, add_barycentrics_grad
+ * (tetranerf/utils/extension/__init__.py:45-68).  These two entry points complete both.  Tet membership, the sample
+ * distances t, near / far and the sampler draws are constants of these gradients.
+ *
+ * (A) tn_interpolate_values_backward_bary_vm: the gather's adjoint w.r.t. the barycentrics.  With
+ *       phi = b0 F[v1] + b1 F[v2] + ... + (1 - (b0 + b1 + ...)) F[v0]      (D - 1 barycentrics, D in {2,3,4,6})
+ *     and grad_rows f32 [n,F] = dL/dphi as sample-major rows, field_vm f32 [V,F] the vertex-major field:
+ *       grad_bary[s,k] = sum_c grad_rows[s,c] (F[v_{k+1},c] - F[v_0,c]),  k = 0 .. D-2;  f32 [n,D-1], every element written.
+ *     The row of an EMPTY id (0xFFFFFFFF) is a zero row. */
+int tn_interpolate_values_backward_bary_vm(uint32_t interpolation_dim, uint32_t num_values, uint32_t field_dim,
+                                           const uint32_t *vertex_indices, const float *grad_rows, const float *field_vm,
+                                           float *grad_bary, void *stream);
+/* (B) tn_sample_positions_backward: the adjoint of the sample position (D = 4).  Sample s of ray r (row r * S + s of
+ *     vertex_indices u32 [R*S,4], barycentric / grad_bary f32 [R*S,3]) lies in the tetrahedron with vertex positions x_0..x_3
+ *     (rows of vertices f32 [V,3]).  With e_k = x_k - x_0, T = rows (e_1, e_2, e_3) and g = the sample's grad_bary row,
+ *     p - x_0 = T^T b, so dL/dp = m where T m = g, in closed form
+ *       m = (g_0 (e_2 x e_3) + g_1 (e_3 x e_1) + g_2 (e_1 x e_2)) / (e_1 . (e_2 x e_3)).
+ *       grad_points     f32 [R*S,3]  m per sample                                              (written)
+ *       grad_vertices   f32 [V,3]    vertex v_k receives -w_k m, w = (1 - (b0+b1+b2), b0, b1, b2)   (ACCUMULATED into, atomics)
+ *       grad_origins    f32 [R,3]    sum_s m            (p = o + t d with t held constant)      (written, one writer per ray)
+ *       grad_directions f32 [R,3]    sum_s t_s m,  t = distances f32 [R,S] (the sample distances handed to the matcher)
+ *     A sample with an EMPTY or out-of-range id, a zero determinant or a non-finite m contributes exact zeros everywhere.
+ *     Each of the four outputs may be null; distances may be null unless grad_directions is asked for. */
+int tn_sample_positions_backward(size_t num_rays, uint32_t samples_per_ray, uint32_t num_vertices,
+                                 const uint32_t *vertex_indices, const float *barycentric, const float *grad_bary,
+                                 const float *distances, const float *vertices,
+                                 float *grad_points, float *grad_origins, float *grad_directions,
+                                 float *grad_vertices, void *stream);
+
 /* Test aid: run only the dedupe / pairing / tail-fill stage
  * (post_process_tetrahedra, src/optix/optix_trace_rays.cu:110-266) on caller-supplied
  * sorted hit rows: hit_count u32 [R], hit_ids u32 [R,M], hit_t f32 [R,M], hit_uv f32 [R,M,2]. */

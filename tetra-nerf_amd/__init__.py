@@ -25,9 +25,10 @@ scatter_ema_uint32_ = cpp.scatter_ema_uint32
 
 
 class _GatherField(torch.autograd.Function):
-    """field[64,V] -> per-sample features; gradient flows to the field only, exactly like
-    _InterpolateValuesFunction (extension/__init__.py:29-42): no gradient for indices or
-    barycentrics (py_binding.cpp:354 leaves that as a TODO)."""
+    """field[64,V] -> per-sample features; gradient flows to the field like
+    _InterpolateValuesFunction (extension/__init__.py:29-42) and, when they require it, to the
+    barycentrics (py_binding.cpp:354 leaves that as a TODO; tn_interpolate_values_backward_bary_vm).
+    The vertex indices -- tet membership -- are constants of the gradient."""
 
     @staticmethod
     def forward(ctx, vertex_indices, barycentric_coordinates, field):
@@ -37,9 +38,13 @@ class _GatherField(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         vertex_indices, barycentric_coordinates, field = ctx.saved_tensors
-        grad_field = cpp.interpolate_values_backward(
-            vertex_indices, barycentric_coordinates, field, grad_out.contiguous())
-        return None, None, grad_field
+        grad_out = grad_out.contiguous()
+        grad_field = grad_bary = None
+        if ctx.needs_input_grad[2]:
+            grad_field = cpp.interpolate_values_backward(vertex_indices, barycentric_coordinates, field, grad_out)
+        if ctx.needs_input_grad[1]:
+            grad_bary = cpp.interpolate_values_backward_barycentrics(vertex_indices, field, grad_out)
+        return None, grad_bary, grad_field
 
 
 def interpolate_values(vertex_indices, barycentric_coordinates, field):
@@ -78,5 +83,39 @@ def add_barycentrics_grad(barycentrics, vertices, points):
     return _BarycentricsGrad.apply(barycentrics, vertices, points)
 
 
+class _SamplePositionsGrad(torch.autograd.Function):
+    """Identity on the barycentrics of ray samples whose backward is tn_sample_positions_backward: the barycentric
+    gradient passes through unchanged and is also routed to the mesh vertices and to the rays the samples sit on
+    (the statement: geometry.sample_positions_backward)."""
+
+    @staticmethod
+    def forward(ctx, barycentrics, vertex_indices, vertices, origins, directions, distances):
+        ctx.save_for_backward(barycentrics, vertex_indices, vertices, distances)
+        return barycentrics.view_as(barycentrics)
+
+    @staticmethod
+    def backward(ctx, grad_bary):
+        barycentrics, vertex_indices, vertices, distances = ctx.saved_tensors
+        _, need_v, need_o, need_d = ctx.needs_input_grad[1:5]
+        grad_v = grad_o = grad_d = None
+        if need_v or need_o or need_d:
+            _, grad_o, grad_d, grad_v = cpp.sample_positions_backward(
+                vertex_indices, barycentrics, grad_bary.contiguous(), vertices.detach(), distances,
+                want_origins=need_o, want_directions=need_d, want_vertices=need_v)
+        return grad_bary, None, grad_v, grad_o, grad_d, None
+
+
+def sample_positions_grad(barycentrics, vertex_indices, vertices, origins, directions, distances):
+    """Identity on `barycentrics` f32 [R, S, 3] that makes them differentiable w.r.t. where the samples sit: in the
+    backward pass the barycentric gradient g of a sample becomes m = T^-1 g (T = rows x_k - x_0 of its tetrahedron
+    `vertex_indices` i32 [R, S, 4] in `vertices` f32 [V, 3]), the gradient w.r.t. the sample point p = o + t d, and
+        vertices [V,3] receive -w_k m (w = (1 - sum b, b0, b1, b2)),  origins [R,3] sum_s m,  directions [R,3] sum_s t_s m
+    with t = `distances` f32 [R, S], the sample distances handed to find_visited_cells.  One HIP kernel
+    (tn_sample_positions_backward); the role of add_barycentrics_grad for whole ray batches.  Tet membership, t, near / far
+    and the sampler draws are CONSTANTS of the gradient; after the vertices moved the tracer must be reloaded
+    (load_tetrahedra).  Under cpp.deterministic_gradients() the vertex sum is taken without float atomics."""
+    return _SamplePositionsGrad.apply(barycentrics, vertex_indices, vertices, origins, directions, distances)
+
+
 __all__ = ["TetrahedraTracer", "triangulate", "gather_uint32", "scatter_ema_uint32_",
-           "interpolate_values", "add_barycentrics_grad", "cpp"]
+           "interpolate_values", "add_barycentrics_grad", "sample_positions_grad", "cpp"]

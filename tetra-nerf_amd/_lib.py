@@ -27,6 +27,7 @@ SYMBOLS = (
     "tn_mlp_forward_gather_train", "tn_mlp_backward", "tn_mlp_ray_head_grad", "tn_mlp_param_grads", "tn_composite_backward", "tn_sample_coarse", "tn_sample_pdf",
     "tn_trace_timings", "tn_trace_cross_check", "tn_fill_rows", "tn_compact_hits", "tn_render_rays", "tn_render_rays_ex",
     "tn_trace_ray_order",
+    "tn_interpolate_values_backward_bary_vm", "tn_sample_positions_backward",
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -74,6 +75,8 @@ def load():
     lib.tn_interpolate_values_vm.argtypes = [u32, u32, u32, vp, vp, vp, vp, vp]
     lib.tn_interpolate_values_backward_vm.argtypes = [u32, u32, u32, vp, vp, vp, vp, vp]
     lib.tn_interpolate_values_backward_vm_det.argtypes = [u32, u32, u32, u32, vp, vp, vp, vp, vp]
+    lib.tn_interpolate_values_backward_bary_vm.argtypes = [u32, u32, u32, vp, vp, vp, vp, vp]
+    lib.tn_sample_positions_backward.argtypes = [sz, u32, u32] + [vp] * 10
     lib.tn_postprocess_hits.argtypes = [vp, sz, u32] + [vp] * 10
     lib.tn_postprocess_hits_tables.argtypes = [i32, sz, u32] + [vp] * 12
     lib.tn_trace_stats.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]

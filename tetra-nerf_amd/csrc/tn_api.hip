@@ -112,6 +112,33 @@ int tn_interpolate_values_backward_vm_det(uint32_t D, uint32_t V, uint32_t n, ui
     });
 }
 
+/* position gradients (tn_position_grad.hip): what py_binding.cpp:354 leaves as a TODO and extension/__init__.py:45-68 states in
+ * PyTorch; the expressions are in include/tetranerf_hip.h */
+int tn_interpolate_values_backward_bary_vm(uint32_t D, uint32_t n, uint32_t Fd, const uint32_t *vi, const float *grad_rows,
+                                           const float *field_vm, float *grad_bary, void *stream_) {
+    return guarded([&] {
+        if (n == 0) return;
+        if (!vi || !grad_bary || (Fd && (!grad_rows || !field_vm))) throw tn::Error("null pointer");
+        tn::launch_interpolate_values_backward_bary_vm(D, n, Fd, vi, grad_rows, field_vm, grad_bary, (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_sample_positions_backward(size_t R, uint32_t S, uint32_t V, const uint32_t *vi, const float *bc, const float *grad_bary,
+                                 const float *distances, const float *vertices, float *grad_points, float *grad_origins,
+                                 float *grad_directions, float *grad_vertices, void *stream_) {
+    return guarded([&] {
+        if (R == 0 || S == 0) return;
+        if (!grad_points && !grad_origins && !grad_directions && !grad_vertices) return;
+        if (!vi || !bc || !grad_bary || !vertices) throw tn::Error("null pointer");
+        if (grad_directions && !distances) throw tn::Error("sample_positions backward: grad_directions needs the sample distances");
+        if (R > 0xFFFFFFFFull / S) throw tn::Error("sample_positions backward: too many samples");
+        tn::launch_sample_positions_backward(R, S, V, vi, bc, grad_bary, distances, vertices, grad_points, grad_origins,
+                                             grad_directions, grad_vertices, (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
 int tn_gather_uint32(int elem_size, uint32_t num_values, uint32_t num_indices, const uint32_t *indices,
                      const void *values, void *result, void *stream_) {
     return guarded([&] {

@@ -167,6 +167,16 @@ void launch_interpolate_values_backward_vm_det(uint32_t D, uint32_t V, uint32_t 
 void launch_interpolate_values_backward_vm(uint32_t D, uint32_t n, uint32_t Fd, const uint32_t *vi, const float *bc,
                                            const float *grad_rows, float *gradT, hipStream_t stream);
 
+// position gradients (tn_position_grad.hip; the statement is in that file's header and in tetra-nerf_amd/geometry.py)
+// (A) the gather's adjoint w.r.t. the barycentrics on a vertex-major field: grad_bary [n, D-1] is WRITTEN; throws on unsupported D
+void launch_interpolate_values_backward_bary_vm(uint32_t D, uint32_t n, uint32_t Fd, const uint32_t *vi, const float *grad_rows,
+                                                const float *fieldT, float *grad_bary, hipStream_t stream);
+// (B) the sample position's adjoint: vi [R*S,4], bc / grad_bary [R*S,3], dist [R,S] (needed for grad_d), verts [V,3];
+// grad_points [R*S,3], grad_o [R,3], grad_d [R,3] are written, grad_v [V,3] is ACCUMULATED into (atomics); each output nullable
+void launch_sample_positions_backward(size_t R, uint32_t S, uint32_t V, const uint32_t *vi, const float *bc, const float *grad_bary,
+                                      const float *dist, const float *verts, float *grad_points, float *grad_o, float *grad_d,
+                                      float *grad_v, hipStream_t stream);
+
 // shallow MLP + heads (tn_mlp.hip); all weights in nn.Linear layout [out, in] row-major, fp32
 struct MlpWeights {
     const float *w1, *b1;  // [128,64],  [128]   mlp_base layer 0

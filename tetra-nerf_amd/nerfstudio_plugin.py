@@ -241,8 +241,13 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
         # the reference's samplers stratify and its RGB renderer skips the clamp whenever `self.training` is set, with
         # or without autograd (model.py:169; nerfstudio RGBRenderer.forward); render_train skips the activation saves
         # when no graph is being recorded
+        kw = {}
+        if getattr(model.config, "position_gradients", False):
+            # opt-in (no such field in the reference's config): gradients for ray bundles whose origins / directions require
+            # them (nerfstudio's camera optimiser) and for a vertex table that does; see TetraRenderer.render_train
+            kw["position_gradients"] = True
         return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
-                               ray_head_bias=hb)
+                               ray_head_bias=hb, **kw)
     return rd.render(o, d, background=bg, ray_head_bias=hb)
 
 

@@ -278,7 +278,8 @@ class _FusedMlpFunction(torch.autograd.Function):
     """gather + MLP + heads as ONE autograd node: forward = tn_mlp_forward_gather_train (fp32; saves the layer inputs and the
     ReLU masks, 2.3 KB per sample), backward = tn_mlp_backward + tn_mlp_param_grads + tn_interpolate_values_backward (dX
     chain and weight gradients on the fp32 matrix cores, nothing recomputed).  Gradients flow to the field and the 12
-    weight tensors."""
+    weight tensors, and -- when they require it -- to the barycentrics (tn_interpolate_values_backward_bary_vm on the same
+    d x0 rows; the vertex indices are constants) and to the view directions (through the head layer's per-ray term)."""
 
     @staticmethod
     def forward(ctx, vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray, ray_head_bias, *weights):
@@ -301,11 +302,22 @@ class _FusedMlpFunction(torch.autograd.Function):
 
         vi, bc, field, dirs, sigma, rgb, *weights = ctx.saved_tensors
         saved = ctx.saved          # (kept: a second backward through a retained graph reads the same activations)
+        need_bary, need_dirs = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
         res = cpp.mlp_backward(saved, vi, bc, field, dirs, list(weights), sigma, rgb, d_sigma.contiguous(), d_rgb.contiguous(),
-                               want_ray_head_grad=ctx.has_bias)
+                               want_ray_head_grad=ctx.has_bias or need_dirs, want_bary_grad=need_bary)
         grad_field, grads = res[0], res[1]
         # the per-ray head bias (appearance embedding): its gradient = per-ray sums of the head pre-activation's gradient
-        return (None, None, grad_field, None, None, res[2] if ctx.has_bias else None, *grads)
+        d_head = res[2] if (ctx.has_bias or need_dirs) else None
+        grad_bary = res[-1].view_as(bc) if need_bary else None
+        grad_dirs = None
+        if need_dirs:
+            # the view direction enters through the head layer's per-ray term Wh[:, :27] enc(dir): the same per-ray sums times
+            # those columns, chained through the Jacobian of the encoding (recomputed: 27 values per ray)
+            g_enc = d_head @ weights[8][:, :DIR_ENC]
+            with torch.enable_grad():
+                d_leaf = dirs.detach().requires_grad_(True)
+                (grad_dirs,) = torch.autograd.grad(direction_encoding(d_leaf), d_leaf, g_enc)
+        return (None, grad_bary, grad_field, grad_dirs, None, d_head if ctx.has_bias else None, *grads)
 
 
 class _FusedCompositeFunction(torch.autograd.Function):
@@ -554,7 +566,8 @@ class TetraRenderer:
     def render_train(self, origins: torch.Tensor, directions: torch.Tensor, gradient_scaling: bool = False,
                      generator: Optional[torch.Generator] = None, rand: Optional[Dict[str, torch.Tensor]] = None,
                      fused: bool = True, capture: Optional[dict] = None, background=None,
-                     ray_head_bias: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                     ray_head_bias: Optional[torch.Tensor] = None, position_gradients: bool = False,
+                     vertices: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
         (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches
         them), gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) --
@@ -565,7 +578,14 @@ class TetraRenderer:
         against and what tests/test_reference_model.py pins with the reference's own get_outputs.  `rand` may carry the
         uniform draws ("coarse" [r,S+1], "fine" [r,S_fine+1] over the hitting rays) so that two calls see the same
         samples; without it they are drawn from `generator` / torch's global generator in the reference's order and
-        shapes (coarse first, then fine), so the same seed gives the reference body and this path the same draws."""
+        shapes (coarse first, then fine), so the same seed gives the reference body and this path the same draws.
+        position_gradients (opt-in; off: nothing below changes): the gradient also reaches WHERE the samples sit -- the
+        `origins` and `directions` handed in (camera pose refinement) and `vertices` f32 [V, 3] (default: the tracer's vertex
+        table; it receives a gradient when it requires one).  The final pass's barycentrics go through
+        sample_positions_grad before the MLP node (fused) or the gather (fused=False), and the view directions of the head
+        layer are differentiable too.  Tet membership, the sample distances t, near / far and the sampler draws are
+        CONSTANTS of that gradient: the coarse pass and the samplers stay under no_grad, nothing flows through the
+        tracer's hit distances.  After the vertices moved, the tracer must be reloaded (load_tetrahedra)."""
         cpp, S = self.cpp, self.S
         R, dev = origins.shape[0], origins.device
         rand = rand or {}
@@ -676,14 +696,23 @@ class TetraRenderer:
                     edges = edges.contiguous()
                 traced = locate(edges)
                 S = edges.shape[1] - 1
-        dirs = directions[idx].contiguous()
+        dirs = directions[idx].contiguous()      # (a differentiable index: the view term of position_gradients)
         # per-ray bias of the head layer (appearance embedding; fused path only): differentiable w.r.t. the caller's tensor
         hb = None if ray_head_bias is None else ray_head_bias.index_select(0, idx).contiguous()
         if hb is not None and not fused:
             raise RuntimeError("ray_head_bias is an input of the fused kernels; the PyTorch statement takes the model's own modules")
         vi, bc = traced["vertex_indices"], traced["barycentric_coordinates"]
+        if position_gradients and torch.is_grad_enabled():
+            from . import sample_positions_grad
+
+            if vertices is None:
+                vertices = self.tracer.tetrahedra_vertices
+            dist = ((edges[:, 1:] + edges[:, :-1]) / 2).contiguous()      # the distances `locate` matched: held constant
+            bc = sample_positions_grad(bc, vi, vertices.reshape(-1, 3), origins[idx], dirs, dist)
+            if capture is not None:
+                capture["barycentric_positions"] = bc
         if capture is not None:   # the (non-differentiable) sample placement, for tests that restate the rest in float64
-            capture.update(idx=idx, vertex_indices=vi, barycentric_coordinates=bc, edges=edges, dirs=dirs,
+            capture.update(idx=idx, vertex_indices=vi, barycentric_coordinates=traced["barycentric_coordinates"], edges=edges, dirs=dirs,
                            near=near_r, far=far_r, samples_per_ray=S)
         if record:
             # the node keeps 2.3 KB per sample from forward to backward (and its backward writes as much again): batches

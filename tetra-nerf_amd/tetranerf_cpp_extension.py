@@ -537,6 +537,75 @@ def interpolate_values_backward(vertex_indices, barycentric_coordinates, field, 
     return grad_field_out
 
 
+def _bary_adjoint_vm(lib, D, n, Fd, vi, rows, field_vm, stream):
+    """tn_interpolate_values_backward_bary_vm on checked arguments -> grad_bary f32 [n, D-1]"""
+    grad_bary = _empty((n, D - 1), dtype=torch.float32, device=rows.device)
+    _lib.check(lib.tn_interpolate_values_backward_bary_vm(D, n, Fd, _ptr(vi), _ptr(rows), _ptr(field_vm), _ptr(grad_bary), stream))
+    return grad_bary
+
+
+def interpolate_values_backward_barycentrics(vertex_indices, field, grad_in):
+    """The gather's adjoint w.r.t. the barycentrics (tn_interpolate_values_backward_bary_vm; the gradient py_binding.cpp:354
+    leaves as a TODO): grad_bary[..., k] = sum_c grad_in[..., c] (field[c, v_{k+1}] - field[c, v_0]), f32 [..., D-1]; the
+    row of an EMPTY id is a zero row.  vertex_indices i32 [..., D], field f32 [F, V], grad_in f32 [..., F].  The vertex ids
+    (tet membership) are constants of this gradient."""
+    for x, name in ((vertex_indices, "vertex_indices"), (field, "field"), (grad_in, "grad_in")):
+        _check_input(x, name)
+    _check(vertex_indices.dtype == torch.int32, "vertex_indices must be a tensor of type int32")
+    _check(field.dtype == torch.float32, "field must be a tensor of type float32")
+    _check(grad_in.dtype == torch.float32, "grad_in must be a tensor of type float32")
+    D = vertex_indices.size(-1)
+    _check(D in (2, 3, 4, 6), f"Unsupported interpolation dimension with value {D}")
+    n = vertex_indices.numel() // D
+    Fd = field.size(0)
+    _check(grad_in.size(-1) == Fd and grad_in.numel() == n * Fd, "grad_in must have shape [..., field_dim]")
+    ft = field_vertex_major(field)
+    with _on(field.device):
+        grad_bary = _bary_adjoint_vm(_lib.load(), D, n, Fd, vertex_indices, grad_in, ft, _stream(field.device))
+    return grad_bary.view(tuple(vertex_indices.shape[:-1]) + (D - 1,))
+
+
+def sample_positions_backward(vertex_indices, barycentric_coordinates, grad_bary, vertices, distances=None, want_points=False,
+                              want_origins=False, want_directions=False, want_vertices=False):
+    """The adjoint of the sample position (tn_sample_positions_backward; completes add_barycentrics_grad,
+    extension/__init__.py:45-68, as one kernel).  vertex_indices i32 [R, S, 4], barycentric_coordinates / grad_bary
+    f32 [R, S, 3], vertices f32 [V, 3], distances f32 [R, S] (the sample distances t handed to find_visited_cells; needed
+    for want_directions).  With T = rows (x_k - x_0) of the sample's tetrahedron, m = T^-1 grad_bary is dL/d(sample point):
+        points [R,S,3] = m;  origins [R,3] = sum_s m;  directions [R,3] = sum_s t_s m   (p = o + t d, t held constant);
+        vertices [V,3]: vertex v_k receives -w_k m, w = (1 - (b0+b1+b2), b0, b1, b2)
+    -- summed with float atomics, or, under deterministic_gradients(), by one writer per element in a fixed order (-m
+    through tn_interpolate_values_backward_vm_det with field_dim = 3).  Samples with an EMPTY id, a zero determinant or a
+    non-finite m contribute exact zeros.  Tet membership, t, near / far and the sampler draws are constants of the
+    gradient.  Returns (points, origins, directions, vertices), None where not asked for."""
+    for x, name in ((vertex_indices, "vertex_indices"), (barycentric_coordinates, "barycentric_coordinates"),
+                    (grad_bary, "grad_bary"), (vertices, "vertices")) + (() if distances is None else ((distances, "distances"),)):
+        _check_input(x, name)
+    _check(vertex_indices.dtype == torch.int32 and vertex_indices.dim() == 3 and vertex_indices.size(-1) == 4,
+           "vertex_indices must be i32 [R,S,4]")
+    R, S = vertex_indices.size(0), vertex_indices.size(1)
+    for x, name in ((barycentric_coordinates, "barycentric_coordinates"), (grad_bary, "grad_bary")):
+        _check(x.dtype == torch.float32 and tuple(x.shape) == (R, S, 3), f"{name} must be f32 [R,S,3]")
+    _check(vertices.dtype == torch.float32 and vertices.dim() == 2 and vertices.size(1) == 3, "vertices must be f32 [V,3]")
+    _check(distances is None or (distances.dtype == torch.float32 and tuple(distances.shape) == (R, S)), "distances must be f32 [R,S]")
+    _check(distances is not None or not want_directions, "want_directions needs the sample distances")
+    dev, V = vertices.device, vertices.size(0)
+    det = want_vertices and deterministic_gradients()
+    points = _empty((R, S, 3), dtype=torch.float32, device=dev) if (want_points or det) else None
+    origins = _empty((R, 3), dtype=torch.float32, device=dev) if want_origins else None
+    directions = _empty((R, 3), dtype=torch.float32, device=dev) if want_directions else None
+    grad_v = torch.zeros((V, 3), dtype=torch.float32, device=dev) if want_vertices else None
+    lib = _lib.load()
+    with _on(dev):
+        stream = _stream(dev)
+        _lib.check(lib.tn_sample_positions_backward(R, S, V, _ptr(vertex_indices), _ptr(barycentric_coordinates), _ptr(grad_bary),
+                                                    _ptr(distances), _ptr(vertices), _ptr(points), _ptr(origins), _ptr(directions),
+                                                    None if det else _ptr(grad_v), stream))
+        if det and R * S:
+            _lib.check(lib.tn_interpolate_values_backward_vm_det(4, V, R * S, 3, _ptr(vertex_indices), _ptr(barycentric_coordinates),
+                                                                 _ptr(points.neg()), _ptr(grad_v), stream))
+    return (points if want_points else None), origins, directions, grad_v
+
+
 class _MlpWeightsStruct(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "wd", "bd", "wh", "bh", "wr", "br")]
 
@@ -930,13 +999,16 @@ def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dir
 
 
 def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, weights, sigma, rgb, d_sigma, d_rgb,
-                 want_ray_head_grad=False):
+                 want_ray_head_grad=False, want_bary_grad=False, return_dx0=False):
     """Adjoint of mlp_forward_gather_train (addition; the reference leaves this to PyTorch autograd, model.py:602-630):
     given the forward's outputs sigma [n] / rgb [n,3], dL/dsigma [n] and dL/drgb [n,3] returns (grad_field [64,V], [12 weight
     gradients in the order of `weights`]).
     tn_mlp_backward -- the dX chain on the fp32 matrix cores from the saved ReLU masks, nothing recomputed -- then
     tn_mlp_param_grads -- the twelve parameter gradients as sample-streaming fp32-MFMA GEMMs over the saved layer inputs,
-    summed without atomics (bit-reproducible) -- then the gather's adjoint.  2.1 KB of gradient buffers per sample."""
+    summed without atomics (bit-reproducible) -- then the gather's adjoint.  2.1 KB of gradient buffers per sample.
+    Appended to the result, in this order: want_ray_head_grad: the per-ray sums of the head pre-activation's gradient [rays, 128];
+    want_bary_grad: dL/d barycentric_coordinates [n, 3], the gather's adjoint w.r.t. the barycentrics on the same d x0 rows
+    (tn_interpolate_values_backward_bary_vm; tet membership is a constant of it); return_dx0: those rows, d x0 [n, 64]."""
     mh = fused_mlp(weights)
     keep = [w.detach() for w in weights]
     n, S = saved.n, saved.S
@@ -978,9 +1050,15 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
         _gather_adjoint_vm(lib, 4, V, n, 64, vi, bc, rows, grad_vm, stream)
         grad_field = _empty((64, V), dtype=torch.float32, device=dev)
         _lib.check(lib.tn_transpose_f32(V, 64, _ptr(grad_vm), _ptr(grad_field), stream))
+        grad_bary = _bary_adjoint_vm(lib, 4, n, 64, vi, rows, field_vertex_major(field), stream) if want_bary_grad else None
+    res = (grad_field, grads)
     if want_ray_head_grad:
-        return grad_field, grads, d_ray_bias
-    return grad_field, grads
+        res += (d_ray_bias,)
+    if want_bary_grad:
+        res += (grad_bary,)
+    if return_dx0:
+        res += (rows,)
+    return res
 
 
 def composite_backward(sigma, rgb, edges, d_out_rgb, d_out_acc, background=1.0):
