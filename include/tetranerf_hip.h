@@ -512,6 +512,14 @@ typedef struct tn_mlp_backward_buffers {
 int tn_mlp_forward_gather_train(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
                                 const float *barycentric, const float *field_vm, const float *dirs, float *sigma, float *rgb,
                                 const tn_mlp_backward_buffers *buffers, const float *ray_head_bias, void *stream);
+/* The same with the arithmetic of the forward chosen per call: mode as in tn_mlp_forward_gather (0 fp32 MFMA =
+ * tn_mlp_forward_gather_train, 1 bf16x3 MFMA).  Mode 1: sigma / rgb are bit for bit those of tn_mlp_forward_gather(mode 1), and
+ * x0, h1..h4 and masks are saved in the same layouts, so tn_mlp_backward / tn_mlp_ray_head_grad / tn_mlp_param_grads run
+ * unchanged (fp32) on them: the gradient is the exact fp32 adjoint at the bf16x3 forward's activations and ReLU decisions.
+ * (Only the forward runs on the bf16 matrix cores; the dX chain and the weight-gradient GEMMs have no such mode.) */
+int tn_mlp_forward_gather_train_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
+                                   const float *barycentric, const float *field_vm, const float *dirs, int mode, float *sigma,
+                                   float *rgb, const tn_mlp_backward_buffers *buffers, const float *ray_head_bias, void *stream);
 int tn_mlp_backward(tn_mlp_t mlp, size_t n, const float *sigma, const float *rgb, const float *d_sigma, const float *d_rgb,
                     const tn_mlp_backward_buffers *buffers, void *stream);
 /* gradient of the per-ray head bias after tn_mlp_backward: d_ray_head_bias f32 [n / samples_per_ray, 128] = the sum over

@@ -203,8 +203,16 @@ tn::MlpBackwardBuffers training_buffers(const tn_mlp_backward_buffers *b) {
 int tn_mlp_forward_gather_train(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
                                 const float *barycentric, const float *field_vm, const float *dirs, float *sigma, float *rgb,
                                 const tn_mlp_backward_buffers *b, const float *ray_head_bias, void *stream_) {
+    return tn_mlp_forward_gather_train_ex(mlp, n, samples_per_ray, vertex_indices, barycentric, field_vm, dirs, 0, sigma, rgb, b,
+                                          ray_head_bias, stream_);
+}
+
+int tn_mlp_forward_gather_train_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
+                                   const float *barycentric, const float *field_vm, const float *dirs, int mode, float *sigma,
+                                   float *rgb, const tn_mlp_backward_buffers *b, const float *ray_head_bias, void *stream_) {
     return guarded([&] {
         tn_mlp *m = checked_mlp(mlp);
+        check_mode(mode);
         if (n == 0) return;
         if (!vertex_indices || !barycentric || !field_vm || !dirs || !sigma || !rgb || !b) throw tn::Error("null pointer");
         if (!b->x0 || !b->h1 || !b->h2 || !b->h3 || !b->h4 || !b->masks) throw tn::Error("null pointer");
@@ -213,8 +221,9 @@ int tn_mlp_forward_gather_train(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray
         const size_t rays = n / samples_per_ray;
         tn::MlpPacks pk = m->packs(rays);
         pk.ray_bias = ray_head_bias;
-        tn::launch_mlp_forward_train(n, samples_per_ray, rays, vertex_indices, barycentric, field_vm, dirs, pk, sigma, rgb,
-                                     training_buffers(b), (hipStream_t)stream_);
+        (mode ? tn::launch_mlp_forward_x3_train : tn::launch_mlp_forward_train)(
+            n, samples_per_ray, rays, vertex_indices, barycentric, field_vm, dirs, pk, sigma, rgb, training_buffers(b),
+            (hipStream_t)stream_);
         TN_HIP(hipGetLastError());
     });
 }

@@ -234,6 +234,12 @@ struct MlpBackwardBuffers {
 void launch_mlp_forward_train(size_t n, uint32_t samples_per_ray, size_t num_rays, const uint32_t *vi, const float *bc,
                               const float *fieldT, const float *dirs, const MlpPacks &w, float *sigma, float *rgb,
                               const MlpBackwardBuffers &save, hipStream_t stream);
+void launch_dir_encoding32(size_t num_rays, const float *dirs, float *enc, hipStream_t stream);   // tn_mlp_x3.hip: [rays][32]
+// the same in bf16x3 (tn_mlp_x3_train.hip): sigma / rgb are launch_mlp_forward_x3's bits, `save` is filled in the same layouts -- the
+// adjoint kernels below run unchanged (fp32) on what it saved
+void launch_mlp_forward_x3_train(size_t n, uint32_t samples_per_ray, size_t num_rays, const uint32_t *vi, const float *bc,
+                                 const float *fieldT, const float *dirs, const MlpPacks &w, float *sigma, float *rgb,
+                                 const MlpBackwardBuffers &save, hipStream_t stream);
 // dX chain from the saved masks and the forward's OUTPUTS sigma [n] / rgb [n, 3] (softplus' = 1 - exp(-sigma),
 // sigmoid' = rgb (1 - rgb)); d_sigma [n], d_rgb [n, 3]; fills d1..d4, dhead, dx0
 void launch_mlp_backward(size_t n, const float *sigma, const float *rgb, const MlpPacks &w, const float *d_sigma, const float *d_rgb,

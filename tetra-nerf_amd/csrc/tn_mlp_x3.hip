@@ -1,7 +1,7 @@
 // tn_mlp_x3.hip -- the shallow MLP + heads on the bf16 matrix cores at fp32 accuracy ("bf16x3").
 //
-// Optional mode of tn_mlp_forward / tn_mlp_forward_gather (tn_mlp_set_mode(1)); the default stays the
-// exact fp32 MFMA kernel of tn_mlp.hip.  fp32 MFMA runs at the vector rate (157 TFLOP/s); the bf16
+// Optional mode of tn_mlp_forward / tn_mlp_forward_gather (tn_mlp_set_mode(1)) and of the training forward
+// (tn_mlp_forward_gather_train_ex: tn_mlp_x3_train.hip); the default stays the exact fp32 MFMA kernel of tn_mlp.hip.  fp32 MFMA runs at the vector rate (157 TFLOP/s); the bf16
 // MFMA (v_mfma_f32_32x32x16_bf16) is 16x faster.  Every fp32 operand is split into three bf16 pieces
 //     x = x_hi + x_mid + x_lo,   x_hi = bf16(x), x_mid = bf16(x - x_hi), x_lo = bf16(x - x_hi - x_mid)
 // (both subtractions are exact in fp32; the three pieces carry 24+ significant bits), and a product is
@@ -173,6 +173,12 @@ void launch_mlp_forward_x3(size_t n, uint32_t samples_per_ray, size_t num_rays, 
     else if (density_only) TN_X3_LAUNCH(false, true);
     else TN_X3_LAUNCH(false, false);
 #undef TN_X3_LAUNCH
+}
+
+// (for the training forward, tn_mlp_x3_train.hip)
+void launch_dir_encoding32(size_t num_rays, const float *dirs, float *enc, hipStream_t stream) {
+    if (num_rays == 0) return;
+    hipLaunchKernelGGL(k_dir_encoding32, dim3((unsigned)((num_rays + 255) / 256)), dim3(256), 0, stream, num_rays, dirs, enc);
 }
 
 }  // namespace tn

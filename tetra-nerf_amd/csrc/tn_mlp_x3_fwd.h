@@ -4,6 +4,7 @@
 #pragma once
 #include "tn_device.h"
 #include "tn_kernels.h"
+#include "tn_mlp_common.h"
 
 namespace tn {
 namespace x3 {
@@ -106,6 +107,40 @@ static __device__ __forceinline__ void x3_steps(f32x16 (&acc)[TILES], const uint
     }
 }
 
+// TRAIN (k_mlp_forward_x3_train): x3_steps that also SAVES its B operand in the layout of the fp32 training forward
+// (tn_mlp_common.h: quad-major [F / 4][n][4]; gemm_steps_store) -- step q consumes bin[8 q .. 8 q + 7] = two quads, which
+// leave in the scheduling region of that step's MFMAs, and (MASK: the operand is a ReLU output) eight bits of its mask
+// word ride along.  p: this lane's first quad; qstride: distance of consecutive quads in float4 units (2 n in accumulator
+// order, n for x0).  The stored values are the fp32 activations themselves, not their bf16 pieces: the fp32 adjoint
+// kernels read them unchanged.
+struct TrainSave { float *x0, *h1, *h2, *h3, *h4; unsigned long long *masks; };
+template <int STEPS, int NT, int TILES, bool MASK>
+static __device__ __forceinline__ void x3_steps_store(f32x16 (&acc)[TILES], const uint4 *wl, const float (&bin)[64], int lane,
+                                                      float4 *__restrict__ p, size_t qstride,
+                                                      unsigned long long *__restrict__ mask_out = nullptr) {
+    B3 cur, nxt;
+    uint32_t lo = 0, hi = 0;
+    split8(bin, cur.h, cur.m, cur.l);
+#pragma unroll
+    for (int q = 0; q < STEPS; ++q) {
+        if (q + 1 < STEPS) split8(bin + 8 * (q + 1), nxt.h, nxt.m, nxt.l);
+        x3_mma<NT>(acc, wl + (size_t)q * NT * 192, cur, lane);
+        p[0] = make_float4(bin[8 * q], bin[8 * q + 1], bin[8 * q + 2], bin[8 * q + 3]);
+        p[qstride] = make_float4(bin[8 * q + 4], bin[8 * q + 5], bin[8 * q + 6], bin[8 * q + 7]);
+        p += 2 * qstride;
+        if constexpr (MASK) {
+#pragma unroll
+            for (int j = 8 * q; j < 8 * q + 8; ++j) {
+                if (j < 32) lo |= mlp::relu_bit(bin[j], j);
+                else hi |= mlp::relu_bit(bin[j], j);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        cur = nxt;
+    }
+    if constexpr (MASK) *mask_out = ((unsigned long long)hi << 32) | lo;
+}
+
 template <int TILES>
 static __device__ __forceinline__ void init_bias(f32x16 (&acc)[TILES], const uint4 *bias, int h) {
 #pragma unroll
@@ -163,12 +198,21 @@ static __device__ __forceinline__ void stage_wait() {
 // One group: samples g * 256 + wave * 32 + (lane & 31) of n; lds: MAX_STAGE_U4 uint4.  enc f32 [rays][32]: the direction encoding
 // of the sample's ray (ray = sample / samples_per_ray), ray_bias f32 [rays][128] or null; blob: k_mlp_pack_x3's.  All 512 threads
 // of the block call it together (block barriers inside).
-template <bool GATHER, bool DENSITY_ONLY>
+// TRAIN (with GATHER, not DENSITY_ONLY): x0, h1..h4 and the four ReLU mask words of every sample go to `sv`, byte-compatible with
+// what mlp::mlp_forward_group<.., TRAIN> saves -- in gather mode both kernels hold x0 in bin[0..31] = features 32 h + i, and
+// every hidden layer in bin[16 t + r] = feature 32 t + acc_feature(r, h), the slot order of mlp::acc_k.  Lanes beyond n store
+// their duplicate of sample n - 1 where its owner stores it.  h4 and its mask, which have no GEMM of their own group to leave
+// under, are stored right behind the head layer: carried in registers into the next group's layer-1 GEMM, as the fp32 kernel
+// does (mlp::FwdCarry), they cost this kernel -- which has no register to spare: 256 VGPRs at 2 waves per SIMD -- 30 spilled
+// registers and measured 3 % SLOWER (1.83 against 1.78 ms at 2.1 M samples, alternating processes).  The arithmetic, and so sigma / rgb, are those of
+// TRAIN = false.
+template <bool GATHER, bool DENSITY_ONLY, bool TRAIN = false>
 static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_t n, uint32_t samples_per_ray, const float *__restrict__ feats,
                                                      const uint32_t *__restrict__ vi, const float *__restrict__ bc,
                                                      const float *__restrict__ fieldT, const float *__restrict__ enc,
                                                      const uint4 *__restrict__ blob, float *__restrict__ sigma, float *__restrict__ rgb,
-                                                     const float *__restrict__ ray_bias) {
+                                                     const float *__restrict__ ray_bias, const TrainSave *sv = nullptr) {
+    static_assert(!TRAIN || (GATHER && !DENSITY_ONLY), "the training forward is the gathering, full network");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     constexpr size_t GROUP = (X3_BLOCK / 64) * 32;
     const size_t s = g * GROUP + (size_t)wave * 32 + (lane & 31);
@@ -206,9 +250,11 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
     {
         f32x16 acc[4];
         init_bias(acc, lds + wu4(4, 4), h);
-        x3_steps<4, 4>(acc, lds, bin, lane);
+        if constexpr (TRAIN) x3_steps_store<4, 4, 4, false>(acc, lds, bin, lane, mlp::quad_ptr_x0(sv->x0, n, sc, h), n);
+        else x3_steps<4, 4>(acc, lds, bin, lane);
         relu_to_bin(acc, bin);
     }
+    auto mask_ptr = [&](int layer) { return sv->masks + ((size_t)layer * n + sc) * 2 + h; };   // TRAIN only
     // ---- layers 2, 3
 #pragma unroll
     for (int l = 0; l < 2; ++l) {
@@ -217,7 +263,8 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
         stage_wait();
         f32x16 acc[4];
         init_bias(acc, lds + wu4(8, 4), h);
-        x3_steps<8, 4>(acc, lds, bin, lane);
+        if constexpr (TRAIN) x3_steps_store<8, 4, 4, true>(acc, lds, bin, lane, mlp::quad_ptr(l == 0 ? sv->h1 : sv->h2, n, sc, h), 2 * n, mask_ptr(l));
+        else x3_steps<8, 4>(acc, lds, bin, lane);
         relu_to_bin(acc, bin);
     }
     {
@@ -245,7 +292,8 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
             ev[8 * q + 4] = e1.x; ev[8 * q + 5] = e1.y; ev[8 * q + 6] = e1.z; ev[8 * q + 7] = e1.w;
         }
         x3_steps<2, 4>(acc, lds, ev, lane);
-        x3_steps<8, 4>(acc, lds + wu4(2, 4), bin, lane);
+        if constexpr (TRAIN) x3_steps_store<8, 4, 4, true>(acc, lds + wu4(2, 4), bin, lane, mlp::quad_ptr(sv->h3, n, sc, h), 2 * n, mask_ptr(2));
+        else x3_steps<8, 4>(acc, lds + wu4(2, 4), bin, lane);
         if (ray_bias) {   // per-ray head bias (appearance embedding; tn_mlp_common.h: add_ray_bias), wave-uniform test
             const float *row = ray_bias + (sc / samples_per_ray) * HID;
 #pragma unroll
@@ -257,6 +305,10 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
                 }
         }
         relu_to_bin(acc, bin);
+    }
+    if constexpr (TRAIN) {
+        mlp::store_bin(sv->h4, n, sc, bin, h);
+        *mask_ptr(3) = mlp::mask_of(bin);
     }
     {
         // rgb head 128 -> 3 + sigmoid on the VALU, fp32

@@ -246,6 +246,11 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
             # opt-in (no such field in the reference's config): gradients for ray bundles whose origins / directions require
             # them (nerfstudio's camera optimiser) and for a vertex table that does; see TetraRenderer.render_train
             kw["position_gradients"] = True
+        train_mode = getattr(model.config, "train_mlp_mode", None)
+        if train_mode is not None:
+            # opt-in as well (an absent field: fp32): "bf16x3" = the forward kernels of a training iteration in the split-operand
+            # bf16 arithmetic, fp32 adjoints (TetraRenderer.render_train: mlp_mode)
+            kw["mlp_mode"] = str(train_mode)
         return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
                                ray_head_bias=hb, **kw)
     return rd.render(o, d, background=bg, ray_head_bias=hb)

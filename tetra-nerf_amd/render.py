@@ -275,8 +275,8 @@ class GradientScaler(torch.autograd.Function):
 
 
 class _FusedMlpFunction(torch.autograd.Function):
-    """gather + MLP + heads as ONE autograd node: forward = tn_mlp_forward_gather_train (fp32; saves the layer inputs and the
-    ReLU masks, 2.3 KB per sample), backward = tn_mlp_backward + tn_mlp_param_grads + tn_interpolate_values_backward (dX
+    """gather + MLP + heads as ONE autograd node: forward = tn_mlp_forward_gather_train_ex (`mode`: "fp32" or "bf16x3"; saves the
+    layer inputs and the ReLU masks, 2.3 KB per sample), backward = tn_mlp_backward + tn_mlp_param_grads + tn_interpolate_values_backward (dX
     chain and weight gradients on the fp32 matrix cores, nothing recomputed).  Gradients flow to the field and the 12
     weight tensors, and -- when they require it -- to the barycentrics (tn_interpolate_values_backward_bary_vm on the same
     d x0 rows; the vertex indices are constants) and to the view directions (through the head layer's per-ray term)."""
@@ -285,9 +285,13 @@ class _FusedMlpFunction(torch.autograd.Function):
     def forward(ctx, vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray, ray_head_bias, *weights):
         from . import tetranerf_cpp_extension as cpp
 
+        # weights: the 12 tensors, optionally followed by the forward's mode ("fp32" when absent)
+        ctx.has_mode = len(weights) == 13
+        mode = weights[12] if ctx.has_mode else "fp32"
+        weights = weights[:12]
         ctx.has_bias = ray_head_bias is not None
         sigma, rgb, saved = cpp.mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dirs, list(weights),
-                                                         int(samples_per_ray), ray_head_bias=ray_head_bias)
+                                                         int(samples_per_ray), ray_head_bias=ray_head_bias, mode=mode)
         # the outputs go through save_for_backward (which knows how to hold a node's own outputs); `saved` must not
         # reference them: node -> saved -> output -> grad_fn -> node is a cycle no collector sees through, i.e. 5 GB
         # leaked per iteration
@@ -317,7 +321,7 @@ class _FusedMlpFunction(torch.autograd.Function):
             with torch.enable_grad():
                 d_leaf = dirs.detach().requires_grad_(True)
                 (grad_dirs,) = torch.autograd.grad(direction_encoding(d_leaf), d_leaf, g_enc)
-        return (None, grad_bary, grad_field, grad_dirs, None, d_head if ctx.has_bias else None, *grads)
+        return (None, grad_bary, grad_field, grad_dirs, None, d_head if ctx.has_bias else None, *grads, *((None,) if ctx.has_mode else ()))
 
 
 class _FusedCompositeFunction(torch.autograd.Function):
@@ -362,7 +366,7 @@ class TetraRenderer:
                  num_fine_samples: int = 0, biased: bool = False, dense_tails: bool = False, fused_pass="auto",
                  mlp_mode: str = "fp32", background=1.0, cache_field: bool = True, device_samplers: bool = True,
                  interpolate_values=None, sync_free_train: bool = True, sync_free_min_hits: float = None,
-                 bin_rays: bool = False):
+                 bin_rays: bool = False, train_mlp_mode: str = "fp32"):
         from . import tetranerf_cpp_extension as cpp
 
         # incoherent batches (random pixels over many cameras): the tracer walks the rays in a locality order of its own
@@ -384,9 +388,13 @@ class TetraRenderer:
         # tests pass the reference's einsum definition so that the statement runs next to the reference model's body
         self._interpolate_values = interpolate_values
         # arithmetic of the fused forward kernels, per renderer (not process-wide): "fp32" = exact fp32 MFMA chain (what
-        # the parity tests pin), "bf16x3" = split-operand bf16 MFMA (opt-in; inference only -- the training forward is
-        # always fp32: tn_mlp_forward_gather_train has no bf16x3 mode)
+        # the parity tests pin), "bf16x3" = split-operand bf16 MFMA (opt-in).  mlp_mode is render()'s; render_train has a
+        # switch of its own, train_mlp_mode (so that a renderer built with mlp_mode="bf16x3" before the training forward had
+        # that mode keeps training in fp32): the forward kernels of a training iteration -- the coarse density pass and the
+        # fine forward, saving or not -- run in it; the adjoint kernels are fp32 in both
         self.mlp_mode = mlp_mode
+        self.train_mlp_mode = train_mlp_mode
+        cpp._mode(train_mlp_mode)      # (an unknown mode fails here, not in the first training call)
         self.train_node_samples = 1 << 22      # render_train: samples per autograd node of the fused MLP (see there)
         # RGBRenderer background: grey level (1.0 white = default config, 0.0 black) or an (r, g, b) triple; render() /
         # render_train() take a per-call override (nerfstudio's BACKGROUND_COLOR_OVERRIDE, model.py:504-518)
@@ -567,7 +575,7 @@ class TetraRenderer:
                      generator: Optional[torch.Generator] = None, rand: Optional[Dict[str, torch.Tensor]] = None,
                      fused: bool = True, capture: Optional[dict] = None, background=None,
                      ray_head_bias: Optional[torch.Tensor] = None, position_gradients: bool = False,
-                     vertices: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                     vertices: Optional[torch.Tensor] = None, mlp_mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
         (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches
         them), gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) --
@@ -585,8 +593,14 @@ class TetraRenderer:
         sample_positions_grad before the MLP node (fused) or the gather (fused=False), and the view directions of the head
         layer are differentiable too.  Tet membership, the sample distances t, near / far and the sampler draws are
         CONSTANTS of that gradient: the coarse pass and the samplers stay under no_grad, nothing flows through the
-        tracer's hit distances.  After the vertices moved, the tracer must be reloaded (load_tetrahedra)."""
+        tracer's hit distances.  After the vertices moved, the tracer must be reloaded (load_tetrahedra).
+        mlp_mode (fused path; None: the renderer's train_mlp_mode, "fp32" unless chosen otherwise): "bf16x3" runs the forward
+        kernels of this call -- the coarse density pass, the recorded fine node and the no-graph fine forward -- in the
+        split-operand bf16 arithmetic (same 1e-5 bar against fp32 as in render()); the adjoints stay fp32 kernels and give
+        the exact fp32 gradient at that forward's activations and ReLU decisions."""
         cpp, S = self.cpp, self.S
+        mode = self.train_mlp_mode if mlp_mode is None else mlp_mode
+        cpp._mode(mode)
         R, dev = origins.shape[0], origins.device
         rand = rand or {}
         # SYNC-FREE form (default for the fused path): the reference compacts the hitting rays with boolean indexing
@@ -670,7 +684,7 @@ class TetraRenderer:
             if self.S_fine > 0:
                 if fused:
                     sigma_c = cpp.mlp_forward_gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field,
-                                                     None, w, S).view(-1, S)
+                                                     None, w, S, mode=mode).view(-1, S)
                     weights_c = cpp.composite(sigma_c, None, edges)
                 else:       # model.py:577-582 in PyTorch
                     gather = self._interpolate_values or cpp.interpolate_values
@@ -719,15 +733,15 @@ class TetraRenderer:
             # beyond 2^22 samples (nerfstudio trains on 4096 rays) go through several nodes, one per block of rays
             rays_per_node = max(1, int(self.train_node_samples) // S)
             if r <= rays_per_node:
-                sigma, col = _FusedMlpFunction.apply(vi, bc, self.field, dirs, S, hb, *w)
+                sigma, col = _FusedMlpFunction.apply(vi, bc, self.field, dirs, S, hb, *w, mode)
             else:
                 parts = [_FusedMlpFunction.apply(vi[a:a + rays_per_node], bc[a:a + rays_per_node], self.field,
-                                                 dirs[a:a + rays_per_node], S, None if hb is None else hb[a:a + rays_per_node], *w)
+                                                 dirs[a:a + rays_per_node], S, None if hb is None else hb[a:a + rays_per_node], *w, mode)
                          for a in range(0, r, rays_per_node)]
                 sigma, col = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
             sigma, col = sigma.view(-1, S), col.view(-1, S, 3)
         elif fused:               # no graph: the plain forward kernel, nothing saved
-            sigma, col = cpp.mlp_forward_gather(vi, bc, self.field, dirs, w, S, ray_head_bias=hb)
+            sigma, col = cpp.mlp_forward_gather(vi, bc, self.field, dirs, w, S, mode=mode, ray_head_bias=hb)
             sigma, col = sigma.view(-1, S), col.view(-1, S, 3)
         else:
             interpolate_values = self._interpolate_values
@@ -771,7 +785,8 @@ class TetraNerfModule(torch.nn.Module):
     after nerfstudio_plugin.install()."""
 
     def __init__(self, tracer, num_vertices: int, num_samples: int = 256, max_ray_triangles: int = 512,
-                 num_fine_samples: int = 256, biased: bool = False, gradient_scaling: bool = False, **renderer_kw):
+                 num_fine_samples: int = 256, biased: bool = False, gradient_scaling: bool = False,
+                 train_mlp_mode: str = "fp32", **renderer_kw):
         super().__init__()
         field = (torch.rand(FIELD_DIM, num_vertices) * 2 - 1) * 1e-4      # model.py:269-271
         field[1:4] = torch.rand(3, num_vertices) * 2 - 1                  # colours, model.py:379-386
@@ -780,7 +795,8 @@ class TetraNerfModule(torch.nn.Module):
         self.gradient_scaling = bool(gradient_scaling)
         self._tracer = tracer
         self._renderer_args = (int(num_samples), int(max_ray_triangles))
-        self._renderer_kw = dict(num_fine_samples=int(num_fine_samples), biased=bool(biased), **renderer_kw)
+        self._renderer_kw = dict(num_fine_samples=int(num_fine_samples), biased=bool(biased), train_mlp_mode=train_mlp_mode,
+                                 **renderer_kw)
         self._renderer = None
 
     def renderer(self) -> "TetraRenderer":

@@ -965,9 +965,13 @@ class MlpSaved:
     __slots__ = ("acts", "masks", "sigma", "rgb", "n", "S")
 
 
-def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray, ray_head_bias=None):
-    """mlp_forward_gather (fp32) for training: returns (sigma [n], rgb [n,3], saved) -- `saved` holds 2.3 KB per sample for
-    mlp_backward, which then recomputes nothing."""
+def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray, ray_head_bias=None,
+                             mode="fp32"):
+    """mlp_forward_gather for training: returns (sigma [n], rgb [n,3], saved) -- `saved` holds 2.3 KB per sample for
+    mlp_backward, which then recomputes nothing.  mode: "fp32" (default) or "bf16x3" (tn_mlp_forward_gather_train_ex): sigma /
+    rgb are then mlp_forward_gather(mode="bf16x3")'s bits and `saved` holds that forward's activations and ReLU masks in the
+    same layouts; mlp_backward is the same fp32 adjoint in both modes."""
+    mode = _mode(mode)
     for x, name in ((vertex_indices, "vertex_indices"), (barycentric_coordinates, "barycentric_coordinates"),
                     (field, "field"), (dirs, "dirs")):
         _check_input(x, name)
@@ -991,10 +995,13 @@ def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dir
     a = sv.acts
     bs = _MlpBackwardBuffers(a[0:64].data_ptr(), a[64:192].data_ptr(), a[192:320].data_ptr(), a[320:448].data_ptr(),
                              a[448:576].data_ptr(), sv.masks.data_ptr(), None, None, None, None, None, None)
+    head = (m.handle, n, S, _ptr(vertex_indices), _ptr(barycentric_coordinates), _ptr(field_vm), _ptr(dirs.contiguous()))
+    tail = (_ptr(sv.sigma), _ptr(sv.rgb), C.byref(bs), _ptr(_ray_bias(ray_head_bias, n // S, dev)), _stream(dev))
     with _on(dev):
-        _lib.check(_lib.load().tn_mlp_forward_gather_train(m.handle, n, S, _ptr(vertex_indices), _ptr(barycentric_coordinates),
-                                                           _ptr(field_vm), _ptr(dirs.contiguous()), _ptr(sv.sigma), _ptr(sv.rgb),
-                                                           C.byref(bs), _ptr(_ray_bias(ray_head_bias, n // S, dev)), _stream(dev)))
+        if mode == 0:       # the default goes through the entry it always went through
+            _lib.check(_lib.load().tn_mlp_forward_gather_train(*head, *tail))
+        else:
+            _lib.check(_lib.load().tn_mlp_forward_gather_train_ex(*head, mode, *tail))
     return sv.sigma, sv.rgb, sv
 
 
