@@ -43,6 +43,10 @@ tn_mlp *checked_mlp(tn_mlp_t m) {
 void check_mode(int mode) {
     if (mode != 0 && mode != 1) throw tn::Error("mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA)");
 }
+tn::MlpBackwardBuffers training_buffers(const tn_mlp_backward_buffers *b) {
+    return tn::MlpBackwardBuffers{{b->x0, b->h1, b->h2, b->h3, b->h4, (unsigned long long *)b->masks},
+                                  b->d1, b->d2, b->d3, b->d4, b->dhead, b->dx0};
+}
 }  // namespace
 
 extern "C" {
@@ -192,13 +196,6 @@ int tn_render_rays_ex(tn_mlp_t mlp, uint32_t M, const uint32_t *num_visited, con
         }
     });
 }
-
-namespace {
-tn::MlpBackwardBuffers training_buffers(const tn_mlp_backward_buffers *b) {
-    return tn::MlpBackwardBuffers{b->x0, b->h1, b->h2, b->h3, b->h4, (unsigned long long *)b->masks,
-                                  b->d1, b->d2, b->d3, b->d4, b->dhead, b->dx0};
-}
-}  // namespace
 
 int tn_mlp_forward_gather_train(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
                                 const float *barycentric, const float *field_vm, const float *dirs, float *sigma, float *rgb,

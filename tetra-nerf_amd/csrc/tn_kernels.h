@@ -222,10 +222,12 @@ void launch_mlp_forward_x3(size_t n, uint32_t samples_per_ray, size_t num_rays, 
 // the layer inputs and the ReLU masks; the backward kernel runs the reverse network from the masks alone (no recompute);
 // the parameter-gradient GEMMs contract the saved inputs with the gradients it leaves.  Device memory owned by the caller;
 // the [F, n] tensors are QUAD-major, [F / 4][n][4] floats (tn_mlp_common.h).
-struct MlpBackwardBuffers {
+struct MlpFwdSave {            // what a training forward saves (the kernels of both arithmetics take it by value)
     float *x0;                 // [64, n]   gathered features (layer-1 input)                              forward -> grads
     float *h1, *h2, *h3, *h4;  // [128, n]  layer outputs after ReLU (inputs of the next layer)             forward -> grads
     unsigned long long *masks; // [4, n, 2] ReLU masks of h1..h4: bit j of word (layer, sample, half) = slot j   forward -> backward
+};
+struct MlpBackwardBuffers : MlpFwdSave {
     float *d1, *d2, *d3, *d4;  // [128, n]  gradients w.r.t. the pre-activations of layers 1, 2, 3 and the head layer   backward -> grads
     float *dhead;              // [4, n]    d sigma_raw, d rgb_raw[0..2]                                   backward -> grads
     float *dx0;                // [n, 64]   gradient w.r.t. the gathered features, sample-major rows       backward -> gather adjoint
@@ -234,7 +236,6 @@ struct MlpBackwardBuffers {
 void launch_mlp_forward_train(size_t n, uint32_t samples_per_ray, size_t num_rays, const uint32_t *vi, const float *bc,
                               const float *fieldT, const float *dirs, const MlpPacks &w, float *sigma, float *rgb,
                               const MlpBackwardBuffers &save, hipStream_t stream);
-void launch_dir_encoding32(size_t num_rays, const float *dirs, float *enc, hipStream_t stream);   // tn_mlp_x3.hip: [rays][32]
 // the same in bf16x3 (tn_mlp_x3_train.hip): sigma / rgb are launch_mlp_forward_x3's bits, `save` is filled in the same layouts -- the
 // adjoint kernels below run unchanged (fp32) on what it saved
 void launch_mlp_forward_x3_train(size_t n, uint32_t samples_per_ray, size_t num_rays, const uint32_t *vi, const float *bc,

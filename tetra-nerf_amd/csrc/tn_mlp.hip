@@ -72,25 +72,6 @@ __global__ void k_mlp_pack(MlpWeights w, float *__restrict__ pk, int gather_l1) 
     pk[i] = v;
 }
 
-// direction encoding per ray (padded to 28): NeRFEncoding(3, 4 freqs 2^linspace(0,4,4), include_input)
-__global__ void k_dir_encoding(size_t R, const float *__restrict__ dirs, float *__restrict__ enc) {
-    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= R) return;
-    const float two_pi = 6.283185307179586f, half_pi = 1.5707963267948966f;
-    const float freqs[4] = {1.0f, 2.5198421478271484f, 6.349603652954102f, 16.0f};  // fp32(2**(4*i/3))
-    float *e = enc + r * ENC_PAD;
-    for (int c = 0; c < 3; ++c) {
-        const float x = two_pi * dirs[3 * r + c];
-        for (int f = 0; f < 4; ++f) {
-            const float s = x * freqs[f];
-            e[c * 4 + f] = sinf(s);
-            e[12 + c * 4 + f] = sinf(s + half_pi);
-        }
-        e[24 + c] = dirs[3 * r + c];
-    }
-    e[27] = 0.f;
-}
-
 // the encoding's 27 columns of mlp_head, [128][ENC_PAD] (column 27 zero): the operand of head_ray_term
 __global__ void k_pack_wenc(MlpWeights w, float *__restrict__ wenc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -163,6 +144,8 @@ __global__ __launch_bounds__(64) void k_composite(size_t R, uint32_t S, const fl
     }
 }
 
+constexpr size_t FWD_SMEM = MAX_STAGE_FLOATS * sizeof(float);   // the largest staged layer
+
 size_t mlp_pack_floats() { return PACK_FLOATS + 1024; }   // + slack: the training kernel copies whole 4 KB passes (tn_mlp_bwd.hip)
 
 
@@ -170,9 +153,12 @@ void launch_mlp_pack(const MlpWeights &w, float *pk, bool gather_l1, hipStream_t
     hipLaunchKernelGGL(k_mlp_pack, dim3((unsigned)((PACK_FLOATS + 255) / 256)), dim3(256), 0, stream, w, pk, gather_l1 ? 1 : 0);
 }
 
-void launch_dir_encoding(size_t num_rays, const float *dirs, float *enc, hipStream_t stream) {
+void launch_dir_encoding(size_t num_rays, const float *dirs, float *enc, int padded, hipStream_t stream) {
     if (num_rays == 0) return;
-    hipLaunchKernelGGL(k_dir_encoding, dim3((unsigned)((num_rays + 255) / 256)), dim3(256), 0, stream, num_rays, dirs, enc);
+    if (padded != ENC_PAD && padded != ENC32) throw Error("launch_dir_encoding: padded width must be 28 or 32");
+    const dim3 grid((unsigned)((num_rays + 255) / 256));
+    if (padded == ENC_PAD) hipLaunchKernelGGL(k_dir_encoding<ENC_PAD>, grid, dim3(256), 0, stream, num_rays, dirs, enc);
+    else hipLaunchKernelGGL(k_dir_encoding<ENC32>, grid, dim3(256), 0, stream, num_rays, dirs, enc);
 }
 
 void launch_pack_wenc(const MlpWeights &w, float *wenc, hipStream_t stream) {
@@ -182,7 +168,7 @@ void launch_pack_wenc(const MlpWeights &w, float *wenc, hipStream_t stream) {
 // the head layer's per-ray term of a call: direction encodings (w.enc) -> w.hterm (+ w.ray_bias)
 void launch_head_ray_term(size_t num_rays, const float *dirs, const MlpPacks &w, hipStream_t stream) {
     if (num_rays == 0) return;
-    hipLaunchKernelGGL(k_dir_encoding, dim3((unsigned)((num_rays + 255) / 256)), dim3(256), 0, stream, num_rays, dirs, w.enc);
+    launch_dir_encoding(num_rays, dirs, w.enc, ENC_PAD, stream);
     hipLaunchKernelGGL(k_head_ray_term, dim3((unsigned)((num_rays * HID + 255) / 256)), dim3(256), 0, stream, num_rays, w.enc, w.wenc,
                        w.ray_bias, w.hterm);
 }
@@ -199,25 +185,10 @@ void launch_mlp_forward(size_t n, uint32_t samples_per_ray, size_t num_rays, con
     const float *pk = gather ? w.pk_gather : w.pk_plain;
     launch_head_ray_term(num_rays, dirs, w, stream);
     // one 8-wave block per CU (4-wave blocks, two per CU, measured neutral: profiles/r02o_mlp_block.txt)
-    const size_t smem = MAX_STAGE_FLOATS * sizeof(float);  // the largest staged layer
-    static PerDeviceOnce lds_attr;
-    lds_attr.run([&] {
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward<false, false>), smem);
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward<true, false>), smem);
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward<false, true>), smem);
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward<true, true>), smem);
+    dispatch_gather_density(gather, density_only, [&](auto G, auto D) {
+        launch_group_kernel<k_mlp_forward<decltype(G)::value, decltype(D)::value>, MLP_BLOCK>(
+            n, FWD_SMEM, stream, n, samples_per_ray, feats, vi, bc, fieldT, (const float *)w.hterm, pk, sigma, rgb, FwdSave{}, count);
     });
-    const size_t group = (MLP_BLOCK / 64) * 32;
-    const size_t ngroups = (n + group - 1) / group;
-    const unsigned grid = (unsigned)(ngroups < 256 ? ngroups : 256);
-#define TN_MLP_LAUNCH(G, D)                                                                                         \
-    hipLaunchKernelGGL((k_mlp_forward<G, D>), dim3(grid), dim3(MLP_BLOCK), smem, stream, n, samples_per_ray, feats, vi, bc, \
-                       fieldT, w.hterm, pk, sigma, rgb, FwdSave{}, count)
-    if (gather && density_only) TN_MLP_LAUNCH(true, true);
-    else if (gather) TN_MLP_LAUNCH(true, false);
-    else if (density_only) TN_MLP_LAUNCH(false, true);
-    else TN_MLP_LAUNCH(false, false);
-#undef TN_MLP_LAUNCH
 }
 
 void launch_mlp_forward_train(size_t n, uint32_t samples_per_ray, size_t num_rays, const uint32_t *vi, const float *bc,
@@ -225,15 +196,9 @@ void launch_mlp_forward_train(size_t n, uint32_t samples_per_ray, size_t num_ray
                               const MlpBackwardBuffers &save, hipStream_t stream) {
     if (n == 0) return;
     launch_head_ray_term(num_rays, dirs, w, stream);
-    const size_t smem = MAX_STAGE_FLOATS * sizeof(float);
-    static PerDeviceOnce lds_attr;
-    lds_attr.run([&] { allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward<true, false, MLP_BLOCK, true>), smem); });
-    const size_t group = (MLP_BLOCK / 64) * 32;
-    const size_t ngroups = (n + group - 1) / group;
-    const unsigned grid = (unsigned)(ngroups < 256 ? ngroups : 256);
-    hipLaunchKernelGGL((k_mlp_forward<true, false, MLP_BLOCK, true>), dim3(grid), dim3(MLP_BLOCK), smem, stream, n, samples_per_ray,
-                       (const float *)nullptr, vi, bc, fieldT, w.hterm, w.pk_gather, sigma, rgb,
-                       FwdSave{save.x0, save.h1, save.h2, save.h3, save.h4, save.masks}, (const uint32_t *)nullptr);
+    launch_group_kernel<k_mlp_forward<true, false, MLP_BLOCK, true>, MLP_BLOCK>(
+        n, FWD_SMEM, stream, n, samples_per_ray, (const float *)nullptr, vi, bc, fieldT, (const float *)w.hterm, w.pk_gather, sigma, rgb,
+        FwdSave(save), (const uint32_t *)nullptr);
 }
 
 void launch_composite(size_t R, uint32_t S, const float *sigma, const float *rgb, const float *edges, Background background,

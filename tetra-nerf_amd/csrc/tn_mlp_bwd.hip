@@ -314,14 +314,9 @@ void launch_mlp_pack_t(const MlpWeights &w, float *pt, hipStream_t stream) {
 void launch_mlp_backward(size_t n, const float *sigma, const float *rgb, const MlpPacks &w, const float *d_sigma, const float *d_rgb,
                          const MlpBackwardBuffers &b, hipStream_t stream) {
     if (n == 0) return;
-    const size_t smem = (BUF_A + BUF_B) * sizeof(float);
-    static PerDeviceOnce lds_attr;
-    lds_attr.run([&] { allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_backward), smem); });
-    const size_t group = (BWD_BLOCK / 64) * 32;
-    const size_t ngroups = (n + group - 1) / group;
-    const unsigned grid = (unsigned)(ngroups < 256 ? ngroups : 256);  // one 4-wave block per CU
-    hipLaunchKernelGGL(k_mlp_backward, dim3(grid), dim3(BWD_BLOCK), smem, stream, n,
-                       BwdIn{b.masks, sigma, rgb, d_sigma, d_rgb}, w.pt, BwdOut{b.d1, b.d2, b.d3, b.d4, b.dhead, b.dx0});
+    // (one 4-wave block per CU)
+    launch_group_kernel<k_mlp_backward, BWD_BLOCK>(n, (BUF_A + BUF_B) * sizeof(float), stream, n, BwdIn{b.masks, sigma, rgb, d_sigma, d_rgb},
+                                                   w.pt, BwdOut{b.d1, b.d2, b.d3, b.d4, b.dhead, b.dx0});
 }
 
 // Gradient of the per-ray head bias (tn_mlp_common.h: add_ray_bias; the appearance embedding of model.py:608-620):

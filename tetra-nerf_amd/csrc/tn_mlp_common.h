@@ -1,6 +1,9 @@
-// tn_mlp_common.h -- geometry of the packed MLP layers and the device helpers shared by the forward kernels
-// (tn_mlp.hip) and the training kernels (tn_mlp_bwd.hip).  See the header of tn_mlp.hip for the dataflow.
+// tn_mlp_common.h -- geometry of the packed MLP layers and the ONE definition of every device helper the fused MLP kernels
+// share: the fp32 forward (tn_mlp_fwd.h), the bf16x3 forward (tn_mlp_x3_fwd.h), their training variants, the persistent render
+// kernel (tn_render_rays.hip) and the training kernels (tn_mlp_bwd.hip).  See the header of tn_mlp.hip for the dataflow.
 #pragma once
+#include <type_traits>
+
 #include "tn_device.h"
 #include "tn_kernels.h"
 
@@ -13,11 +16,14 @@ constexpr int HID = 128;          // hidden width
 constexpr int FD = 64;            // field dim
 constexpr int ENC = 27;           // direction encoding width
 constexpr int ENC_PAD = 28;       // padded to an even K
+constexpr int ENC32 = 32;         // padded to two K = 16 steps of the bf16x3 head layer (tn_mlp_x3_fwd.h)
 constexpr int KS1 = FD / 2;       // k-steps of layer 1
 constexpr int KSH = HID / 2;      // k-steps over 128 features held in accumulators
 constexpr int KSE = ENC_PAD / 2;  // k-steps over the direction encoding
 constexpr int OT = HID / 32;      // output tiles of a hidden layer
 constexpr int MLP_BLOCK = 512;    // 8 waves share one staged layer: 256 samples per group
+
+using FwdSave = MlpFwdSave;       // where a TRAIN forward leaves x0, h1..h4 and the ReLU masks (tn_kernels.h)
 
 // One staged layer = [k-steps + 1][tiles][64 lanes] floats; the extra last k-step carries the bias
 // (A = bias for the lower half-wave, 0 for the upper; B = 1.0), so the bias add is part of the GEMM.
@@ -50,14 +56,14 @@ __host__ __device__ constexpr int acc_feature(int r, int h) { return (r & 3) + 8
 // k index consumed by k-step `ks` (0..63) of a layer whose input lives in accumulators, half h
 __host__ __device__ constexpr int acc_k(int ks, int h) { return 32 * (ks >> 4) + acc_feature(ks & 15, h); }
 
-// Packed layer -> LDS with the async global->LDS path (global_load_lds_dwordx4: no staging registers, all
-// of a thread's loads in flight at once; a load-wait-write loop exposes one L2 latency per 8 KB).  The LDS
+// Packed layer (n16 units of 16 bytes) -> LDS with the async global->LDS path (global_load_lds_dwordx4: no staging
+// registers, all of a thread's loads in flight at once; a load-wait-write loop exposes one L2 latency per 8 KB).  The LDS
 // destination of a wave is uniform base + lane * 16, which is exactly a linear copy.
 template <int BLOCK = MLP_BLOCK>
-static __device__ __forceinline__ void stage_weights(float *lds, const float *__restrict__ src, size_t n_floats) {
-    const float4 *s4 = reinterpret_cast<const float4 *>(src);
-    float4 *d4 = reinterpret_cast<float4 *>(lds);
-    const uint32_t n16 = (uint32_t)(n_floats / 4), lane = threadIdx.x & 63;
+static __device__ __forceinline__ void stage(void *lds, const void *__restrict__ src, uint32_t n16) {
+    const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
+    uint4 *d4 = reinterpret_cast<uint4 *>(lds);
+    const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u);
     for (uint32_t base = wave0; base < n16; base += BLOCK) {
         const uint32_t i = base + lane;
@@ -76,6 +82,9 @@ static __device__ __forceinline__ void stage_wait() {
 // itself the compiler reads them into the same registers right before their use, and a wave that is alone on its SIMD
 // (the training kernel) then idles for one LDS latency per k-step (round 3: the dX kernel ran at 52 % of the MFMA rate).
 // The sched_barrier keeps the scheduler from hoisting hundreds of reads (register blow-up) or sinking these.
+// (The two storing forms below repeat this loop on purpose: written as one loop that takes the stores as a callable, the fp32
+//  training forward came out with another register allocation -- 249 VGPRs for 248, 24 more instructions -- and measured 1.2 %
+//  slower; profiles/mlp_forward_dedupe.txt.)
 template <int KS, int KS0, int TILES, int BIN0 = 0>
 static __device__ __forceinline__ void gemm_steps(f32x16 (&acc)[TILES], const float (&bin)[KSH], const float *lds, int lane) {
     float a[TILES], an[TILES];
@@ -116,6 +125,9 @@ static __device__ __forceinline__ void gemm_steps(f32x16 (&acc)[TILES], const fl
 static __device__ __forceinline__ uint32_t relu_bit(float v, int j) {
     const uint32_t b = __float_as_uint(v);      // a ReLU output is >= +0: "positive" = "bit pattern not zero"
     return (b < 1u ? b : 1u) << (j & 31);
+}
+static __device__ __forceinline__ float4 quad_of(const float (&v)[KSH], int g) {   // slots 4g .. 4g + 3
+    return make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
 }
 template <int KS, int KS0, int TILES, int NST, bool MASK = false>
 static __device__ __forceinline__ void gemm_steps_store(f32x16 (&acc)[TILES], const float (&bin)[KSH], const float *lds, int lane,
@@ -265,13 +277,82 @@ static __device__ __forceinline__ void relu_to_bin(const f32x16 (&acc)[TILES], f
         for (int r = 0; r < 16; ++r) bin[t * 16 + r] = fmaxf(acc[t][r], 0.f);
 }
 
+// Fused barycentric gather (interpolate_values<4>, same summation order => same bits as the stand-alone op): the lane
+// produces features 32h .. 32h+31 of sample sc straight into the B-operand registers bin[0..31]; the [64, n] feature
+// buffer never exists.
+static __device__ __forceinline__ void gather_features(float (&bin)[KSH], const uint32_t *__restrict__ vi, const float *__restrict__ bc,
+                                                       const float *__restrict__ fieldT, size_t sc, int h) {
+    const uint4 v4 = *reinterpret_cast<const uint4 *>(vi + 4 * sc);
+    const float b0 = bc[3 * sc], b1 = bc[3 * sc + 1], b2 = bc[3 * sc + 2];
+    const float w0 = 1.0f - ((b0 + b1) + b2);
+    const uint32_t vv[4] = {v4.y, v4.z, v4.w, v4.x};
+    const float ww[4] = {b0, b1, b2, w0};
+#pragma unroll
+    for (int i = 0; i < 32; ++i) bin[i] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (vv[k] != TN_EMPTY) {
+            const float4 *row = reinterpret_cast<const float4 *>(fieldT + (size_t)vv[k] * FD + 32 * h);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const float4 x = row[q];
+                bin[4 * q] += ww[k] * x.x; bin[4 * q + 1] += ww[k] * x.y;
+                bin[4 * q + 2] += ww[k] * x.z; bin[4 * q + 3] += ww[k] * x.w;
+            }
+        }
+    }
+}
+
+// density head 128 -> 1 + softplus on the VALU, fp32.  dv: the staged vector behind layer 3's weights (DVEC floats)
+static __device__ __forceinline__ void density_head(const float *dv, const float (&bin)[KSH], int h, size_t s, size_t n,
+                                                    float *__restrict__ sigma) {
+    const float raw = head_dot(dv + 64 * h, bin) + dv[128];
+    const float sp = raw > 20.0f ? raw : log1pf(expf(raw));  // torch softplus(beta=1, threshold=20)
+    if (h == 0 && s < n) sigma[s] = sp;
+}
+// rgb head 128 -> 3 + sigmoid on the VALU, fp32.  cv: the staged vectors behind the head layer's weights (CVEC floats)
+static __device__ __forceinline__ void rgb_head(const float *cv, const float (&bin)[KSH], int h, size_t s, size_t n,
+                                                float *__restrict__ rgb) {
+    const float c0 = head_dot(cv + 64 * h, bin) + cv[384];
+    const float c1 = head_dot(cv + 128 + 64 * h, bin) + cv[385];
+    const float c2 = head_dot(cv + 256 + 64 * h, bin) + cv[386];
+    if (h == 0 && s < n) {
+        rgb[3 * s] = 1.0f / (1.0f + expf(-c0));
+        rgb[3 * s + 1] = 1.0f / (1.0f + expf(-c1));
+        rgb[3 * s + 2] = 1.0f / (1.0f + expf(-c2));
+    }
+}
+
+// Direction encoding of a ray, NeRFEncoding(3, 4 freqs 2^linspace(0,4,4), include_input): e[4 c + f] = sin(2 pi d[c] freq f),
+// e[12 + 4 c + f] = the cosine (as sin(. + pi/2)), e[24 + c] = d[c], zeros up to the padded width (28: the fp32 kernels'
+// head_ray_term; 32 = two K = 16 steps: the bf16x3 head layer).  dir_sincos is the one expression of an element pair: the
+// kernel below walks (c, f) serially, the persistent render kernel gives each pair a lane.
+static __device__ __forceinline__ void dir_sincos(float d, int f, float &sn, float &cs) {
+    const float two_pi = 6.283185307179586f, half_pi = 1.5707963267948966f;
+    const float x = two_pi * d;
+    const float s = x * (f == 0 ? 1.0f : (f == 1 ? 2.5198421478271484f : (f == 2 ? 6.349603652954102f : 16.0f)));  // fp32(2**(4*f/3))
+    sn = sinf(s);
+    cs = sinf(s + half_pi);
+}
+template <int PAD>
+__global__ void k_dir_encoding(size_t R, const float *__restrict__ dirs, float *__restrict__ enc) {
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    float *e = enc + r * PAD;
+    for (int c = 0; c < 3; ++c) {
+        for (int f = 0; f < 4; ++f) dir_sincos(dirs[3 * r + c], f, e[c * 4 + f], e[12 + c * 4 + f]);
+        e[24 + c] = dirs[3 * r + c];
+    }
+    for (int k = ENC; k < PAD; ++k) e[k] = 0.f;
+}
+
 
 // all 64 values a lane holds of a [128 / 4][n][4] tensor (see above): 16 quads, 2 n float4 apart
 static __device__ __forceinline__ void store_bin(float *__restrict__ dst, size_t n, size_t s, const float (&bin)[KSH], int h) {
     float4 *p = quad_ptr(dst, n, s, h);
 #pragma unroll
     for (int g = 0; g < KSH / 4; ++g) {
-        *p = make_float4(bin[4 * g], bin[4 * g + 1], bin[4 * g + 2], bin[4 * g + 3]);
+        *p = quad_of(bin, g);
         p += 2 * n;
     }
 }
@@ -301,9 +382,34 @@ static __device__ __forceinline__ void masked_to_bin(const f32x16 (&acc)[TILES],
         }
 }
 
+// ---- host side: how every fused kernel over 256- (or 128-) sample groups is launched
+
+// one block per CU, grid-striding over the groups of (block / 64) * 32 samples
+inline unsigned mlp_forward_grid(size_t n, int block) {
+    const size_t group = (size_t)(block / 64) * 32;
+    const size_t ngroups = (n + group - 1) / group;
+    return (unsigned)(ngroups < 256 ? ngroups : 256);
+}
+// launch of a kernel that grid-strides over the groups of n samples (the forwards, the dX kernel), opted into its dynamic LDS
+// (more than 64 KB: the staged weights) once per device
+template <auto KERNEL, int BLOCK, typename... Args>
+void launch_group_kernel(size_t n, size_t smem, hipStream_t stream, Args... args) {
+    static PerDeviceOnce lds_attr;   // (one per KERNEL)
+    lds_attr.run([&] { allow_dynamic_lds(reinterpret_cast<const void *>(KERNEL), smem); });
+    hipLaunchKernelGGL(KERNEL, dim3(mlp_forward_grid(n, BLOCK)), dim3(BLOCK), smem, stream, args...);
+}
+// f(GATHER, DENSITY_ONLY) with the two run-time switches of the inference forwards as std::bool_constant types
+template <typename F>
+void dispatch_gather_density(bool gather, bool density_only, F &&f) {
+    if (gather && density_only) f(std::true_type{}, std::true_type{});
+    else if (gather) f(std::true_type{}, std::false_type{});
+    else if (density_only) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+}
+
 }  // namespace mlp
 
-// packers / encoders of tn_mlp.hip, used by the training path as well
-void launch_dir_encoding(size_t num_rays, const float *dirs, float *enc, hipStream_t stream);
+// direction encodings [rays][padded] of a call, padded = ENC_PAD or ENC32; tn_mlp.hip
+void launch_dir_encoding(size_t num_rays, const float *dirs, float *enc, int padded, hipStream_t stream);
 
 }  // namespace tn

@@ -9,9 +9,8 @@ namespace tn {
 namespace mlp {
 
 // TRAIN: the layer inputs x0, h1..h4 (quad-major [F/4][n][4], what the weight-gradient GEMMs contract) and the ReLU masks (all the
-// dX kernel needs) are saved on the way -- the backward pass recomputes nothing (round 3a recomputed the whole forward
-// inside the dX kernel: 2.2 of its 5 ms).
-struct FwdSave { float *x0, *h1, *h2, *h3, *h4; unsigned long long *masks; };
+// dX kernel needs) are saved on the way (sv: FwdSave) -- the backward pass recomputes nothing (round 3a recomputed the whole
+// forward inside the dX kernel: 2.2 of its 5 ms).
 
 // group g = samples [g * GROUP, (g + 1) * GROUP) of n; every thread of the block calls it (it contains the block barriers of
 // the weight stages).  TRAIN: cy carries h4 and the place of its mask from one group of the block to the next (FwdCarry,
@@ -31,34 +30,11 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
 
     // ---- layer 1: 64 -> 128, B operands straight from the feature-major input [64, n]
     __syncthreads();
-    stage_weights<BLOCK>(lds, pk + OFF_W1, lfloats(KS1, OT));
+    stage<BLOCK>(lds, pk + OFF_W1, lfloats(KS1, OT) / 4);
     if constexpr (!GATHER) {
 #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) bin[ks] = feats[(size_t)(2 * ks + h) * n + sc];
-    } else {
-        // fused barycentric gather (interpolate_values<4>, same summation order => same bits as the
-        // stand-alone op): this lane produces features 32h .. 32h+31 of its sample straight into the
-        // B-operand registers; the [64, n] feature buffer never exists.
-        const uint4 v4 = *reinterpret_cast<const uint4 *>(vi + 4 * sc);
-        const float b0 = bc[3 * sc], b1 = bc[3 * sc + 1], b2 = bc[3 * sc + 2];
-        const float w0 = 1.0f - ((b0 + b1) + b2);
-        const uint32_t vv[4] = {v4.y, v4.z, v4.w, v4.x};
-        const float ww[4] = {b0, b1, b2, w0};
-#pragma unroll
-        for (int ks = 0; ks < KS1; ++ks) bin[ks] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (vv[k] != TN_EMPTY) {
-                const float4 *row = reinterpret_cast<const float4 *>(fieldT + (size_t)vv[k] * FD + 32 * h);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float4 x = row[q];
-                    bin[4 * q] += ww[k] * x.x; bin[4 * q + 1] += ww[k] * x.y;
-                    bin[4 * q + 2] += ww[k] * x.z; bin[4 * q + 3] += ww[k] * x.w;
-                }
-            }
-        }
-    }
+    } else gather_features(bin, vi, bc, fieldT, sc, h);
     stage_wait();
     {
         f32x16 acc[OT];
@@ -77,7 +53,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
     auto mask_ptr = [&](int layer) { return sv.masks + ((size_t)layer * n + sc) * 2 + h; };   // TRAIN only
     // ---- layers 2, 3: 128 -> 128, accumulators fed back as B operands
     __syncthreads();
-    stage_weights<BLOCK>(lds, pk + OFF_W2, lfloats(KSH, OT));
+    stage<BLOCK>(lds, pk + OFF_W2, lfloats(KSH, OT) / 4);
     stage_wait();
     {
         f32x16 acc[OT];
@@ -88,7 +64,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
         relu_to_bin(acc, bin);
     }
     __syncthreads();
-    stage_weights<BLOCK>(lds, pk + OFF_W3, N_W3);
+    stage<BLOCK>(lds, pk + OFF_W3, N_W3 / 4);
     stage_wait();
     {
         f32x16 acc[OT];
@@ -98,18 +74,12 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
         bias_step<KSH, OT>(acc, lds, lane);
         relu_to_bin(acc, bin);  // mlp_base out_activation = ReLU
     }
-    {
-        // density head 128 -> 1 + softplus on the VALU (the vector rides behind layer 3's weights)
-        const float *dv = lds + lfloats(KSH, OT);
-        const float raw = head_dot(dv + 64 * h, bin) + dv[128];
-        const float sp = raw > 20.0f ? raw : log1pf(expf(raw));  // torch softplus(beta=1, threshold=20)
-        if (h == 0 && s < n) sigma[s] = sp;
-    }
+    density_head(lds + lfloats(KSH, OT), bin, h, s, n, sigma);   // (the vector rides behind layer 3's weights)
     if constexpr (DENSITY_ONLY) return;  // coarse pass of the model (model.py:577-581)
     // ---- head [enc(27) | base(128)] -> 128 ReLU: the 128 base columns as a GEMM, the encoding's 27 columns (constant along a
     //      ray) as the per-ray vector the caller made (hterm = Wh[:, :27] enc(dir) + the appearance embedding's bias, if any)
     __syncthreads();
-    stage_weights<BLOCK>(lds, pk + OFF_WHEAD, N_WHEAD);
+    stage<BLOCK>(lds, pk + OFF_WHEAD, N_WHEAD / 4);
     stage_wait();
     {
         f32x16 acc[OT];
@@ -126,18 +96,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
         cy->p = quad_ptr(sv.h4, n, sc, h);
         cy->m = mask_ptr(3);
     }
-    {
-        // rgb head 128 -> 3 + sigmoid on the VALU
-        const float *cv = lds + lfloats(HEAD_KS, OT);
-        const float c0 = head_dot(cv + 64 * h, bin) + cv[384];
-        const float c1 = head_dot(cv + 128 + 64 * h, bin) + cv[385];
-        const float c2 = head_dot(cv + 256 + 64 * h, bin) + cv[386];
-        if (h == 0 && s < n) {
-            rgb[3 * s] = 1.0f / (1.0f + expf(-c0));
-            rgb[3 * s + 1] = 1.0f / (1.0f + expf(-c1));
-            rgb[3 * s + 2] = 1.0f / (1.0f + expf(-c2));
-        }
-    }
+    rgb_head(lds + lfloats(HEAD_KS, OT), bin, h, s, n, rgb);
 }
 
 // after a block's last group: the carried h4 and its mask
@@ -146,7 +105,7 @@ static __device__ __forceinline__ void flush_carry(const FwdCarry &cy, size_t n)
     float4 *p = cy.p;
 #pragma unroll
     for (int g = 0; g < KSH / 4; ++g) {
-        *p = make_float4(cy.h4[4 * g], cy.h4[4 * g + 1], cy.h4[4 * g + 2], cy.h4[4 * g + 3]);
+        *p = quad_of(cy.h4, g);
         p += 2 * n;
     }
     *cy.m = mask_of(cy.h4);

@@ -321,7 +321,7 @@ void launch_mlp_param_grads(size_t n, uint32_t samples_per_ray, const float *dir
                             const MlpParamGrads &g, hipStream_t stream) {
     if (n == 0) return;
     if (n > 0xFFFFFFFFull) throw Error("param_grads: more than 2^32 samples per call");
-    launch_dir_encoding(n / samples_per_ray, dirs, w.enc, stream);
+    launch_dir_encoding(n / samples_per_ray, dirs, w.enc, ENC_PAD, stream);
     float *part = w.grad_scratch;
     // mlp_head: [enc(27) | base(128)] -> 128, and the density head's weight vector
     run_dw<4, true>(n, DwArgs{b.d4, b.h3, w.enc, b.dhead, samples_per_ray, part},

@@ -1,7 +1,8 @@
 // tn_mlp_x3.hip -- the shallow MLP + heads on the bf16 matrix cores at fp32 accuracy ("bf16x3").
 //
-// Optional mode of tn_mlp_forward / tn_mlp_forward_gather (tn_mlp_set_mode(1)) and of the training forward
-// (tn_mlp_forward_gather_train_ex: tn_mlp_x3_train.hip); the default stays the exact fp32 MFMA kernel of tn_mlp.hip.  fp32 MFMA runs at the vector rate (157 TFLOP/s); the bf16
+// Optional mode of tn_mlp_forward / tn_mlp_forward_gather / tn_render_rays_ex (their `mode` argument, TN_MLP_MODE_BF16X3) and of the
+// training forward (tn_mlp_forward_gather_train_ex: tn_mlp_x3_train.hip); the default stays the exact fp32 MFMA kernel of
+// tn_mlp.hip.  fp32 MFMA runs at the vector rate (157 TFLOP/s); the bf16
 // MFMA (v_mfma_f32_32x32x16_bf16) is 16x faster.  Every fp32 operand is split into three bf16 pieces
 //     x = x_hi + x_mid + x_lo,   x_hi = bf16(x), x_mid = bf16(x - x_hi), x_lo = bf16(x - x_hi - x_mid)
 // (both subtractions are exact in fp32; the three pieces carry 24+ significant bits), and a product is
@@ -18,8 +19,6 @@
 // (half-wave, element) -> k assignment, so the packing only has to agree with itself.  The bias is the
 // accumulators' initial value.  Per layer the three weight pieces are staged in LDS
 // ([step][tile][piece][lane] x 16 B, <= 120 KB for the head layer) and shared by the 8 waves of a block.
-#include "tn_device.h"
-#include "tn_kernels.h"
 #include "tn_mlp_x3_fwd.h"
 
 namespace tn {
@@ -100,25 +99,6 @@ __global__ void k_mlp_pack_x3(MlpWeights w, uint4 *__restrict__ blob) {
 }
 constexpr size_t PACK_THREADS = (4 * 4 + 8 * 4 + 8 * 4 + 2 * 4 + 8 * 4) * 64 + 4 * 128 + 132 + 388;
 
-// direction encoding per ray, padded to 32 (same arithmetic as k_dir_encoding of tn_mlp.hip)
-__global__ void k_dir_encoding32(size_t R, const float *__restrict__ dirs, float *__restrict__ enc) {
-    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= R) return;
-    const float two_pi = 6.283185307179586f, half_pi = 1.5707963267948966f;
-    const float freqs[4] = {1.0f, 2.5198421478271484f, 6.349603652954102f, 16.0f};
-    float *e = enc + r * ENC32;
-    for (int c = 0; c < 3; ++c) {
-        const float x = two_pi * dirs[3 * r + c];
-        for (int f = 0; f < 4; ++f) {
-            const float s = x * freqs[f];
-            e[c * 4 + f] = sinf(s);
-            e[12 + c * 4 + f] = sinf(s + half_pi);
-        }
-        e[24 + c] = dirs[3 * r + c];
-    }
-    for (int k = ENC; k < ENC32; ++k) e[k] = 0.f;
-}
-
 }  // namespace
 
 template <bool GATHER, bool DENSITY_ONLY>
@@ -150,35 +130,12 @@ void launch_mlp_forward_x3(size_t n, uint32_t samples_per_ray, size_t num_rays, 
     const bool gather = feats == nullptr;
     const bool density_only = rgb == nullptr;
     if (density_only) num_rays = 0;
-    const uint4 *blob = w.blob;
-    float *enc = w.enc;
-    if (num_rays)
-        hipLaunchKernelGGL(k_dir_encoding32, dim3((unsigned)((num_rays + 255) / 256)), dim3(256), 0, stream, num_rays, dirs, enc);
+    launch_dir_encoding(num_rays, dirs, w.enc, ENC32, stream);
     const size_t smem = MAX_STAGE_U4 * sizeof(uint4);  // head layer: 120 KB of weight pieces + bias + rgb vectors
-    static PerDeviceOnce lds_attr;
-    lds_attr.run([&] {
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward_x3<false, false>), smem);
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward_x3<true, false>), smem);
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward_x3<false, true>), smem);
-        allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward_x3<true, true>), smem);
+    mlp::dispatch_gather_density(gather, density_only, [&](auto G, auto D) {
+        mlp::launch_group_kernel<k_mlp_forward_x3<decltype(G)::value, decltype(D)::value>, X3_BLOCK>(
+            n, smem, stream, n, samples_per_ray, feats, vi, bc, fieldT, (const float *)w.enc, w.blob, sigma, rgb, w.ray_bias, count);
     });
-    const size_t group = (X3_BLOCK / 64) * 32;
-    const size_t ngroups = (n + group - 1) / group;
-    const unsigned grid = (unsigned)(ngroups < 256 ? ngroups : 256);
-#define TN_X3_LAUNCH(G, D)                                                                                            \
-    hipLaunchKernelGGL((k_mlp_forward_x3<G, D>), dim3(grid), dim3(X3_BLOCK), smem, stream, n, samples_per_ray, feats, vi, bc, \
-                       fieldT, enc, blob, sigma, rgb, w.ray_bias, count)
-    if (gather && density_only) TN_X3_LAUNCH(true, true);
-    else if (gather) TN_X3_LAUNCH(true, false);
-    else if (density_only) TN_X3_LAUNCH(false, true);
-    else TN_X3_LAUNCH(false, false);
-#undef TN_X3_LAUNCH
-}
-
-// (for the training forward, tn_mlp_x3_train.hip)
-void launch_dir_encoding32(size_t num_rays, const float *dirs, float *enc, hipStream_t stream) {
-    if (num_rays == 0) return;
-    hipLaunchKernelGGL(k_dir_encoding32, dim3((unsigned)((num_rays + 255) / 256)), dim3(256), 0, stream, num_rays, dirs, enc);
 }
 
 }  // namespace tn

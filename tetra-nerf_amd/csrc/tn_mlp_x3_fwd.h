@@ -1,28 +1,28 @@
 // tn_mlp_x3_fwd.h -- the bf16x3 forward of ONE group of 256 samples (8 waves x 32) as a device function: the loop body of
 // k_mlp_forward_x3 (tn_mlp_x3.hip, where the arithmetic is described) and of the MLP phases of the persistent render kernel in
-// its bf16x3 mode (tn_render_rays.hip, round 6) -- the same code, so the two produce identical bits.
+// its bf16x3 mode (tn_render_rays.hip, round 6) -- the same code, so the two produce identical bits.  Whatever does not depend on
+// the arithmetic (gather, staging, the VALU heads, the per-ray bias, the save layouts) is tn_mlp_common.h's.
 #pragma once
-#include "tn_device.h"
-#include "tn_kernels.h"
 #include "tn_mlp_common.h"
 
 namespace tn {
 namespace x3 {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using mlp::f32x16;
+using mlp::HID; using mlp::FD; using mlp::ENC; using mlp::ENC32; using mlp::KSH;
+using mlp::acc_feature; using mlp::relu_to_bin; using mlp::stage_wait;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int HID = 128, FD = 64, ENC = 27, ENC32 = 32;
-constexpr int X3_BLOCK = 512;
+constexpr int X3_BLOCK = mlp::MLP_BLOCK;
 
 // sizes in 16-byte units
 constexpr size_t wu4(int steps, int tiles) { return (size_t)steps * tiles * 3 * 64; }
 constexpr size_t bu4(int tiles) { return (size_t)tiles * 8; }  // bias: [tile][half][16] floats
 // The narrow heads (density 128 -> 1, rgb 128 -> 3) run on the VALU as in tn_mlp.hip: their fp32 vectors
 // ([half][64] floats in the lane's K order + bias) ride behind the layer that produces their input.
-constexpr size_t DVEC_U4 = (2 * 64 + 4) / 4, CVEC_U4 = (3 * 2 * 64 + 4) / 4;
+constexpr size_t DVEC_U4 = mlp::DVEC / 4, CVEC_U4 = mlp::CVEC / 4;
 constexpr size_t N_L1 = wu4(4, 4) + bu4(4);
 constexpr size_t N_L2 = wu4(8, 4) + bu4(4);
 constexpr size_t N_L3 = N_L2 + DVEC_U4;
@@ -30,7 +30,6 @@ constexpr size_t N_HEAD = wu4(2, 4) + wu4(8, 4) + bu4(4) + CVEC_U4;
 constexpr size_t O_L1 = 0, O_L2 = O_L1 + N_L1, O_L3 = O_L2 + N_L2, O_HEAD = O_L3 + N_L3, N_BLOB = O_HEAD + N_HEAD;
 constexpr size_t MAX_STAGE_U4 = N_HEAD > N_L3 ? N_HEAD : N_L3;
 
-__host__ __device__ constexpr int acc_feature(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 // input feature consumed by K slot (step q, half h, element j) of a layer fed from accumulators
 __host__ __device__ constexpr int acc_k(int q, int h, int j) { return 32 * (q >> 1) + acc_feature(8 * (q & 1) + j, h); }
 
@@ -64,6 +63,9 @@ struct B3 { uint4 h, m, l; };  // the three bf16 pieces of 8 K-values of a lane
 
 // one K = 16 step of NT output tiles: acc[t] += W[t](hi,mid,lo) x B(hi,mid,lo), six partial products,
 // small terms first; two tiles are interleaved so that consecutive MFMAs never share an accumulator
+// (the six-product sequence stays written out for the pair and for the odd tile: behind a helper taking the tiles as an array it
+//  changed the instruction stream of every bf16x3 kernel, and the bf16x3 render measured 0.7 % slower;
+//  profiles/mlp_forward_dedupe.txt)
 template <int NT, int TILES>
 static __device__ __forceinline__ void x3_mma(f32x16 (&acc)[TILES], const uint4 *wl, const B3 &b, int lane) {
 #pragma unroll
@@ -94,17 +96,23 @@ static __device__ __forceinline__ void x3_mma(f32x16 (&acc)[TILES], const uint4 
 // STEPS consecutive K = 16 steps over bin[0 .. 8*STEPS): the operand split of step q+1 (VALU) is issued
 // in the same scheduling region as the MFMAs of step q, so it runs in their shadow; the sched_barrier
 // between regions keeps the A-operand reads of later steps from being hoisted (registers).
-template <int STEPS, int NT, int TILES>
-static __device__ __forceinline__ void x3_steps(f32x16 (&acc)[TILES], const uint4 *wl, const float *bin, int lane) {
+// shadow(q): issued behind the MFMAs of step q, inside their scheduling region (x3_steps_store)
+template <int STEPS, int NT, int TILES, typename Shadow>
+static __device__ __forceinline__ void x3_steps(f32x16 (&acc)[TILES], const uint4 *wl, const float *bin, int lane, Shadow &&shadow) {
     B3 cur, nxt;
     split8(bin, cur.h, cur.m, cur.l);
 #pragma unroll
     for (int q = 0; q < STEPS; ++q) {
         if (q + 1 < STEPS) split8(bin + 8 * (q + 1), nxt.h, nxt.m, nxt.l);
         x3_mma<NT>(acc, wl + (size_t)q * NT * 192, cur, lane);
+        shadow(q);
         __builtin_amdgcn_sched_barrier(0);
         cur = nxt;
     }
+}
+template <int STEPS, int NT, int TILES>
+static __device__ __forceinline__ void x3_steps(f32x16 (&acc)[TILES], const uint4 *wl, const float *bin, int lane) {
+    x3_steps<STEPS, NT>(acc, wl, bin, lane, [](int) {});
 }
 
 // TRAIN (k_mlp_forward_x3_train): x3_steps that also SAVES its B operand in the layout of the fp32 training forward
@@ -113,20 +121,14 @@ static __device__ __forceinline__ void x3_steps(f32x16 (&acc)[TILES], const uint
 // word ride along.  p: this lane's first quad; qstride: distance of consecutive quads in float4 units (2 n in accumulator
 // order, n for x0).  The stored values are the fp32 activations themselves, not their bf16 pieces: the fp32 adjoint
 // kernels read them unchanged.
-struct TrainSave { float *x0, *h1, *h2, *h3, *h4; unsigned long long *masks; };
 template <int STEPS, int NT, int TILES, bool MASK>
-static __device__ __forceinline__ void x3_steps_store(f32x16 (&acc)[TILES], const uint4 *wl, const float (&bin)[64], int lane,
+static __device__ __forceinline__ void x3_steps_store(f32x16 (&acc)[TILES], const uint4 *wl, const float (&bin)[KSH], int lane,
                                                       float4 *__restrict__ p, size_t qstride,
                                                       unsigned long long *__restrict__ mask_out = nullptr) {
-    B3 cur, nxt;
     uint32_t lo = 0, hi = 0;
-    split8(bin, cur.h, cur.m, cur.l);
-#pragma unroll
-    for (int q = 0; q < STEPS; ++q) {
-        if (q + 1 < STEPS) split8(bin + 8 * (q + 1), nxt.h, nxt.m, nxt.l);
-        x3_mma<NT>(acc, wl + (size_t)q * NT * 192, cur, lane);
-        p[0] = make_float4(bin[8 * q], bin[8 * q + 1], bin[8 * q + 2], bin[8 * q + 3]);
-        p[qstride] = make_float4(bin[8 * q + 4], bin[8 * q + 5], bin[8 * q + 6], bin[8 * q + 7]);
+    x3_steps<STEPS, NT>(acc, wl, bin, lane, [&](int q) {
+        p[0] = mlp::quad_of(bin, 2 * q);
+        p[qstride] = mlp::quad_of(bin, 2 * q + 1);
         p += 2 * qstride;
         if constexpr (MASK) {
 #pragma unroll
@@ -135,9 +137,7 @@ static __device__ __forceinline__ void x3_steps_store(f32x16 (&acc)[TILES], cons
                 else hi |= mlp::relu_bit(bin[j], j);
             }
         }
-        __builtin_amdgcn_sched_barrier(0);
-        cur = nxt;
-    }
+    });
     if constexpr (MASK) *mask_out = ((unsigned long long)hi << 32) | lo;
 }
 
@@ -153,47 +153,6 @@ static __device__ __forceinline__ void init_bias(f32x16 (&acc)[TILES], const uin
         }
     }
 }
-
-static __device__ __forceinline__ float head_dot(const float *wl, const float (&bin)[64]) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const float4 w4 = reinterpret_cast<const float4 *>(wl)[i];
-        a0 = __builtin_fmaf(w4.x, bin[4 * i], a0);
-        a1 = __builtin_fmaf(w4.y, bin[4 * i + 1], a1);
-        a2 = __builtin_fmaf(w4.z, bin[4 * i + 2], a2);
-        a3 = __builtin_fmaf(w4.w, bin[4 * i + 3], a3);
-    }
-    const float part = (a0 + a1) + (a2 + a3);
-    return part + __shfl_xor(part, 32);
-}
-
-template <int TILES>
-static __device__ __forceinline__ void relu_to_bin(const f32x16 (&acc)[TILES], float (&bin)[64]) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) bin[t * 16 + r] = fmaxf(acc[t][r], 0.f);
-}
-
-// Layer blob -> LDS with the async global->LDS path (global_load_lds_dwordx4: no staging registers, all
-// of a thread's loads in flight at once; a load-wait-write loop exposes one L2 latency per 8 KB).  The LDS
-// destination of a wave is uniform base + lane * 16, which is exactly a linear copy.
-static __device__ __forceinline__ void stage(uint4 *lds, const uint4 *__restrict__ src, uint32_t n16) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u);
-    for (uint32_t base = wave0; base < n16; base += X3_BLOCK) {
-        const uint32_t i = base + lane;
-        if (i < n16)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + i),
-                                             (__attribute__((address_space(3))) void *)(lds + base), 16, 0, 0);
-    }
-}
-static __device__ __forceinline__ void stage_wait() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-}
-
 
 // One group: samples g * 256 + wave * 32 + (lane & 31) of n; lds: MAX_STAGE_U4 uint4.  enc f32 [rays][32]: the direction encoding
 // of the sample's ray (ray = sample / samples_per_ray), ray_bias f32 [rays][128] or null; blob: k_mlp_pack_x3's.  All 512 threads
@@ -211,41 +170,21 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
                                                      const uint32_t *__restrict__ vi, const float *__restrict__ bc,
                                                      const float *__restrict__ fieldT, const float *__restrict__ enc,
                                                      const uint4 *__restrict__ blob, float *__restrict__ sigma, float *__restrict__ rgb,
-                                                     const float *__restrict__ ray_bias, const TrainSave *sv = nullptr) {
+                                                     const float *__restrict__ ray_bias, const mlp::FwdSave *sv = nullptr) {
     static_assert(!TRAIN || (GATHER && !DENSITY_ONLY), "the training forward is the gathering, full network");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     constexpr size_t GROUP = (X3_BLOCK / 64) * 32;
     const size_t s = g * GROUP + (size_t)wave * 32 + (lane & 31);
     const size_t sc = s < n ? s : n - 1;
-    float bin[64];
+    float bin[KSH];
 
     // ---- layer 1: this lane supplies features 32h .. 32h+31 of its sample
     __syncthreads();
-    stage(lds, blob + O_L1, N_L1);
+    mlp::stage<X3_BLOCK>(lds, blob + O_L1, N_L1);
     if constexpr (!GATHER) {  // B operands straight from the feature-major input [64, n]
 #pragma unroll
         for (int i = 0; i < 32; ++i) bin[i] = feats[(size_t)(32 * h + i) * n + sc];
-    } else {
-        const uint4 v4 = *reinterpret_cast<const uint4 *>(vi + 4 * sc);
-        const float b0 = bc[3 * sc], b1 = bc[3 * sc + 1], b2 = bc[3 * sc + 2];
-        const float w0 = 1.0f - ((b0 + b1) + b2);
-        const uint32_t vv[4] = {v4.y, v4.z, v4.w, v4.x};
-        const float ww[4] = {b0, b1, b2, w0};
-#pragma unroll
-        for (int i = 0; i < 32; ++i) bin[i] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (vv[k] != TN_EMPTY) {
-                const float4 *row = reinterpret_cast<const float4 *>(fieldT + (size_t)vv[k] * FD + 32 * h);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const float4 x = row[q];
-                    bin[4 * q] += ww[k] * x.x; bin[4 * q + 1] += ww[k] * x.y;
-                    bin[4 * q + 2] += ww[k] * x.z; bin[4 * q + 3] += ww[k] * x.w;
-                }
-            }
-        }
-    }
+    } else mlp::gather_features(bin, vi, bc, fieldT, sc, h);
     stage_wait();
     {
         f32x16 acc[4];
@@ -259,7 +198,7 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
 #pragma unroll
     for (int l = 0; l < 2; ++l) {
         __syncthreads();
-        stage(lds, blob + (l == 0 ? O_L2 : O_L3), l == 0 ? N_L2 : N_L3);
+        mlp::stage<X3_BLOCK>(lds, blob + (l == 0 ? O_L2 : O_L3), l == 0 ? N_L2 : N_L3);
         stage_wait();
         f32x16 acc[4];
         init_bias(acc, lds + wu4(8, 4), h);
@@ -267,17 +206,11 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
         else x3_steps<8, 4>(acc, lds, bin, lane);
         relu_to_bin(acc, bin);
     }
-    {
-        // density head 128 -> 1 + softplus on the VALU, fp32 (vector behind layer 3's blob)
-        const float *dv = reinterpret_cast<const float *>(lds + N_L2);
-        const float raw = head_dot(dv + 64 * h, bin) + dv[128];
-        const float sp = raw > 20.0f ? raw : log1pf(expf(raw));
-        if (h == 0 && s < n) sigma[s] = sp;
-    }
+    mlp::density_head(reinterpret_cast<const float *>(lds + N_L2), bin, h, s, n, sigma);   // (vector behind layer 3's blob)
     if constexpr (DENSITY_ONLY) return;
     // ---- head [enc(27) | base(128)] -> 128 ReLU
     __syncthreads();
-    stage(lds, blob + O_HEAD, N_HEAD);
+    mlp::stage<X3_BLOCK>(lds, blob + O_HEAD, N_HEAD);
     stage_wait();
     {
         f32x16 acc[4];
@@ -294,34 +227,14 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
         x3_steps<2, 4>(acc, lds, ev, lane);
         if constexpr (TRAIN) x3_steps_store<8, 4, 4, true>(acc, lds + wu4(2, 4), bin, lane, mlp::quad_ptr(sv->h3, n, sc, h), 2 * n, mask_ptr(2));
         else x3_steps<8, 4>(acc, lds + wu4(2, 4), bin, lane);
-        if (ray_bias) {   // per-ray head bias (appearance embedding; tn_mlp_common.h: add_ray_bias), wave-uniform test
-            const float *row = ray_bias + (sc / samples_per_ray) * HID;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 v = *reinterpret_cast<const float4 *>(row + 32 * t + 8 * q + 4 * h);
-                    acc[t][4 * q] += v.x; acc[t][4 * q + 1] += v.y; acc[t][4 * q + 2] += v.z; acc[t][4 * q + 3] += v.w;
-                }
-        }
+        if (ray_bias) mlp::add_ray_bias(acc, ray_bias + (sc / samples_per_ray) * HID, h);   // (appearance embedding) wave-uniform test
         relu_to_bin(acc, bin);
     }
     if constexpr (TRAIN) {
         mlp::store_bin(sv->h4, n, sc, bin, h);
         *mask_ptr(3) = mlp::mask_of(bin);
     }
-    {
-        // rgb head 128 -> 3 + sigmoid on the VALU, fp32
-        const float *cv = reinterpret_cast<const float *>(lds + wu4(2, 4) + wu4(8, 4) + bu4(4));
-        const float c0 = head_dot(cv + 64 * h, bin) + cv[384];
-        const float c1 = head_dot(cv + 128 + 64 * h, bin) + cv[385];
-        const float c2 = head_dot(cv + 256 + 64 * h, bin) + cv[386];
-        if (h == 0 && s < n) {
-            rgb[3 * s] = 1.0f / (1.0f + expf(-c0));
-            rgb[3 * s + 1] = 1.0f / (1.0f + expf(-c1));
-            rgb[3 * s + 2] = 1.0f / (1.0f + expf(-c2));
-        }
-    }
+    mlp::rgb_head(reinterpret_cast<const float *>(lds + wu4(2, 4) + wu4(8, 4) + bu4(4)), bin, h, s, n, rgb);
 }
 
 }  // namespace x3

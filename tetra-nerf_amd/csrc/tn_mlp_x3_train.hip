@@ -1,8 +1,6 @@
 // tn_mlp_x3_train.hip -- the bf16x3 TRAINING forward (tn_mlp_forward_gather_train_ex, mode 1; the arithmetic is described in
 // tn_mlp_x3.hip).  A translation unit of its own: with this kernel beside them the compiler allocates the registers of the
 // k_mlp_forward_x3 instantiations differently (more scratch, other VGPR counts), and those must keep their code.
-#include "tn_device.h"
-#include "tn_kernels.h"
 #include "tn_mlp_x3_fwd.h"
 
 namespace tn {
@@ -17,7 +15,7 @@ __global__ __launch_bounds__(X3_BLOCK) void k_mlp_forward_x3_train(size_t n, uin
                                                                    const float *__restrict__ bc, const float *__restrict__ fieldT,
                                                                    const float *__restrict__ enc, const uint4 *__restrict__ blob,
                                                                    float *__restrict__ sigma, float *__restrict__ rgb,
-                                                                   const float *__restrict__ ray_bias, TrainSave sv) {
+                                                                   const float *__restrict__ ray_bias, mlp::FwdSave sv) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint4 *lds = reinterpret_cast<uint4 *>(smem);
     constexpr size_t GROUP = (X3_BLOCK / 64) * 32;
@@ -30,16 +28,10 @@ void launch_mlp_forward_x3_train(size_t n, uint32_t samples_per_ray, size_t num_
                                  const float *fieldT, const float *dirs, const MlpPacks &w, float *sigma, float *rgb,
                                  const MlpBackwardBuffers &save, hipStream_t stream) {
     if (n == 0) return;
-    launch_dir_encoding32(num_rays, dirs, w.enc, stream);
-    const size_t smem = MAX_STAGE_U4 * sizeof(uint4);
-    static PerDeviceOnce lds_attr;
-    lds_attr.run([&] { allow_dynamic_lds(reinterpret_cast<const void *>(k_mlp_forward_x3_train), smem); });
-    const size_t group = (X3_BLOCK / 64) * 32;
-    const size_t ngroups = (n + group - 1) / group;
-    const unsigned grid = (unsigned)(ngroups < 256 ? ngroups : 256);
-    hipLaunchKernelGGL((k_mlp_forward_x3_train), dim3(grid), dim3(X3_BLOCK), smem, stream, n, samples_per_ray, vi, bc, fieldT,
-                       (const float *)w.enc, w.blob, sigma, rgb, w.ray_bias,
-                       TrainSave{save.x0, save.h1, save.h2, save.h3, save.h4, save.masks});
+    launch_dir_encoding(num_rays, dirs, w.enc, ENC32, stream);
+    mlp::launch_group_kernel<k_mlp_forward_x3_train, X3_BLOCK>(n, MAX_STAGE_U4 * sizeof(uint4), stream, n, samples_per_ray, vi, bc,
+                                                                 fieldT, (const float *)w.enc, w.blob, sigma, rgb, w.ray_bias,
+                                                                 mlp::FwdSave(save));
 }
 
 }  // namespace tn

@@ -232,16 +232,11 @@ __device__ __forceinline__ void ray_match(uint32_t S, uint32_t M, size_t src, ui
     lds_sync();
 }
 
-// direction encoding of one ray (k_dir_encoding's expressions, lane-parallel): NeRFEncoding(3, 4 freqs 2^linspace(0,4,4), include_input)
+// direction encoding of one ray, k_dir_encoding<ENC_PAD>'s elements (tn_mlp_common.h) one pair per lane
 __device__ __forceinline__ void ray_dir_encoding(const float *__restrict__ d3, float *__restrict__ e, int lane) {
-    const float two_pi = 6.283185307179586f, half_pi = 1.5707963267948966f;
-    const float freqs[4] = {1.0f, 2.5198421478271484f, 6.349603652954102f, 16.0f};  // fp32(2**(4*i/3))
     if (lane < 12) {
         const int c = lane >> 2, f = lane & 3;
-        const float x = two_pi * d3[c];
-        const float s = x * (f == 0 ? freqs[0] : (f == 1 ? freqs[1] : (f == 2 ? freqs[2] : freqs[3])));
-        e[c * 4 + f] = sinf(s);
-        e[12 + c * 4 + f] = sinf(s + half_pi);
+        dir_sincos(d3[c], f, e[c * 4 + f], e[12 + c * 4 + f]);
     } else if (lane < 15) {
         e[24 + (lane - 12)] = d3[lane - 12];
     } else if (lane == 15) {
@@ -288,7 +283,7 @@ __global__ __launch_bounds__(RR_BLOCK, 2) void k_render_rays(RenderRaysParams p)
     float *edges_c = sc, *edges_f = sc + p.o_edges_f, *hterm = sc + p.o_hterm;
     uint32_t *vi = reinterpret_cast<uint32_t *>(sc + p.o_vi);
     float *bc = sc + p.o_bc, *sigma = sc + p.o_sigma, *rgb = sc + p.o_rgb;
-    float *enc_t = sc + p.o_enc;                            // X3: [T][32]
+    float *enc_t = sc + p.o_enc;                            // X3: [T][ENC32]
     float *wl = lds + (size_t)wave * p.region;              // this wave's LDS for the ray phases (aliases the weight stage)
 
     const uint32_t nrays = (uint32_t)(q1 - q0);
@@ -333,12 +328,12 @@ __global__ __launch_bounds__(RR_BLOCK, 2) void k_render_rays(RenderRaysParams p)
             load_bounds(M, ray, nv, p, dv, lane);            // back by the time the matcher wants them
             float *e = edges_c + (size_t)t * (S + 1);
             ray_sample_coarse_nf(S, M, ray, nv, near, far, p.dist, p.lin, nullptr, p.biased, e, el, wl, lane);
-            // the head layer's per-ray term: Wh[:, :27] enc(dir) + the appearance embedding's bias (k_head_ray_term's expression)
+            // the head layer's per-ray term: Wh[:, :27] enc(dir) + the appearance embedding's bias (head_ray_term, as k_head_ray_term)
             ray_dir_encoding(p.dirs + 3 * ray, wl, lane);   // (28 floats of the wave's LDS: the sampler is done with `cum`)
             lds_sync();
             if constexpr (X3) {
-                // the encoding itself, padded to 32 (k_dir_encoding32's layout), and the ray's bias row
-                if (lane < 32) enc_t[(size_t)t * 32 + lane] = lane < 27 ? wl[lane] : 0.f;
+                // the encoding itself, padded to ENC32 (k_dir_encoding<ENC32>'s rows), and the ray's bias row
+                if (lane < ENC32) enc_t[(size_t)t * ENC32 + lane] = lane < ENC ? wl[lane] : 0.f;
                 if (p.ray_bias) {
                     hterm[(size_t)t * HID + lane] = p.ray_bias[ray * HID + lane];
                     hterm[(size_t)t * HID + 64 + lane] = p.ray_bias[ray * HID + 64 + lane];
@@ -423,7 +418,7 @@ size_t render_rays_scratch_floats(size_t r_max, uint32_t S, uint32_t S_fine, boo
     auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };   // 256-byte aligned pieces (and blocks): a group's 4 KB of vertex ids start on a line
     const uint32_t nb = S_fine + 1;
     const uint32_t Sf = S_fine ? S + nb : S;
-    const size_t per_ray = (size_t)(S + 1) + (S_fine ? (size_t)(Sf + 1) : 0) + HID + 32 + (size_t)Sf * 11;
+    const size_t per_ray = (size_t)(S + 1) + (S_fine ? (size_t)(Sf + 1) : 0) + HID + ENC32 + (size_t)Sf * 11;
     const size_t rays_per_block = (r_max + grid - 1) / grid;
     // Scratch budget per block = tile size.  Measured (profiles/r05k_scratch_sweep.txt): a chip-wide working set of 256 x 4 MB
     // costs the coarse-only render 1.4 % against 256 x 0.5 MB (address translation: 256 private windows), but small tiles end in
@@ -445,7 +440,7 @@ size_t render_rays_scratch_floats(size_t r_max, uint32_t S, uint32_t S_fine, boo
     L.o_bc = o; o = al(o + T * Sf * 3);
     L.o_sigma = o; o = al(o + T * Sf);
     L.o_rgb = o; o = al(o + T * Sf * 3);
-    L.o_enc = o; o = al(o + T * 32);                      // (bf16x3 mode)
+    L.o_enc = o; o = al(o + T * ENC32);                   // (bf16x3 mode)
     L.per_block = o;
     return o * grid;
 }

@@ -754,15 +754,17 @@ def _ray_bias(ray_head_bias, rays, dev):
     return ray_head_bias
 
 
-def mlp_forward_gather(vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray, mode="fp32",
-                       ray_head_bias=None, count=None):
-    """interpolate_values + mlp_forward in ONE kernel: the wave gathers its samples' features from the
-    (vertex-major shadow of the) field straight into MFMA operand registers; the [64, n] feature buffer is never
-    written.  vertex_indices i32 [..., 4], barycentric_coordinates f32 [..., 3], field f32 [64, V].
-    dirs=None: density only (the coarse pass of the model, model.py:577-581) -> sigma [n]."""
-    density_only = dirs is None
+def _check_gather_args(field, dirs, samples=None, rays=None):
+    """Argument checks of the calls that gather from `field`.  The gathering forwards pass samples = (vertex_indices,
+    barycentric_coordinates, samples_per_ray) and get (n, S) back; dirs f32 [n / S, 3], or None: density only.  render_rays
+    passes rays = R instead: its `directions` cover ALL rays (and it has checked the tensors themselves)."""
+    if samples is None:
+        _check(dirs.dtype == torch.float32 and tuple(dirs.shape) == (rays, 3), "directions must be f32 [R, 3]")
+        _check(field.dtype == torch.float32 and field.dim() == 2 and field.size(0) == 64, "field must be f32 [64, V]")
+        return None
+    vertex_indices, barycentric_coordinates, samples_per_ray = samples
     for x, name in ((vertex_indices, "vertex_indices"), (barycentric_coordinates, "barycentric_coordinates"),
-                    (field, "field")) + (() if density_only else ((dirs, "dirs"),)):
+                    (field, "field")) + (() if dirs is None else ((dirs, "dirs"),)):
         _check_input(x, name)
     _check(vertex_indices.dtype == torch.int32 and vertex_indices.size(-1) == 4, "vertex_indices must be i32 [...,4]")
     _check(barycentric_coordinates.dtype == torch.float32 and barycentric_coordinates.size(-1) == 3,
@@ -771,8 +773,19 @@ def mlp_forward_gather(vertex_indices, barycentric_coordinates, field, dirs, wei
     n = vertex_indices.numel() // 4
     S = int(samples_per_ray)
     _check(S > 0 and n % S == 0, "n must be a multiple of samples_per_ray")
-    _check(density_only or (dirs.dtype == torch.float32 and tuple(dirs.shape) == (n // S, 3)),
+    _check(dirs is None or (dirs.dtype == torch.float32 and tuple(dirs.shape) == (n // S, 3)),
            "dirs must be f32 [n/samples_per_ray, 3]")
+    return n, S
+
+
+def mlp_forward_gather(vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray, mode="fp32",
+                       ray_head_bias=None, count=None):
+    """interpolate_values + mlp_forward in ONE kernel: the wave gathers its samples' features from the
+    (vertex-major shadow of the) field straight into MFMA operand registers; the [64, n] feature buffer is never
+    written.  vertex_indices i32 [..., 4], barycentric_coordinates f32 [..., 3], field f32 [64, V].
+    dirs=None: density only (the coarse pass of the model, model.py:577-581) -> sigma [n]."""
+    density_only = dirs is None
+    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
     m = fused_mlp(weights)
     dev = field.device
     field_vm = field_vertex_major(field)
@@ -814,8 +827,7 @@ def render_rays(trace_lists, order, count, field, directions, weights, num_sampl
     R, M = dist.size(0), dist.size(1)
     _check(order.dtype == torch.int32 and order.dim() == 1 and order.numel() <= R, "order must be i32 [<= R]")
     _check(count is None or (count.dtype == torch.int32 and count.numel() >= 1 and count.is_cuda), "count must be an i32 device tensor")
-    _check(directions.dtype == torch.float32 and tuple(directions.shape) == (R, 3), "directions must be f32 [R, 3]")
-    _check(field.dtype == torch.float32 and field.dim() == 2 and field.size(0) == 64, "field must be f32 [64, V]")
+    _check_gather_args(field, directions, rays=R)
     S, Sf = int(num_samples), int(num_fine)
     m = fused_mlp(weights)
     dev = field.device
@@ -972,17 +984,8 @@ def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dir
     rgb are then mlp_forward_gather(mode="bf16x3")'s bits and `saved` holds that forward's activations and ReLU masks in the
     same layouts; mlp_backward is the same fp32 adjoint in both modes."""
     mode = _mode(mode)
-    for x, name in ((vertex_indices, "vertex_indices"), (barycentric_coordinates, "barycentric_coordinates"),
-                    (field, "field"), (dirs, "dirs")):
-        _check_input(x, name)
-    _check(vertex_indices.dtype == torch.int32 and vertex_indices.size(-1) == 4, "vertex_indices must be i32 [...,4]")
-    _check(barycentric_coordinates.dtype == torch.float32 and barycentric_coordinates.size(-1) == 3,
-           "barycentric_coordinates must be f32 [...,3]")
-    _check(field.dtype == torch.float32 and field.dim() == 2 and field.size(0) == 64, "field must be f32 [64, V]")
-    n = vertex_indices.numel() // 4
-    S = int(samples_per_ray)
-    _check(S > 0 and n % S == 0, "n must be a multiple of samples_per_ray")
-    _check(dirs.dtype == torch.float32 and tuple(dirs.shape) == (n // S, 3), "dirs must be f32 [n/samples_per_ray, 3]")
+    _check_input(dirs, "dirs")   # (no density-only form: the training forward is the full network)
+    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
     m = fused_mlp(weights)
     dev = field.device
     field_vm = field_vertex_major(field)
