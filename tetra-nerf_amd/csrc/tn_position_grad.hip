@@ -21,6 +21,7 @@
 
 #include "tn_device.h"
 #include "tn_kernels.h"
+#include "tn_ray_ops.h"
 
 namespace tn {
 
@@ -97,12 +98,6 @@ void run_bwd_bary(uint32_t n, uint32_t Fd, const uint32_t *vi, const float *rows
     hipLaunchKernelGGL(k_interp_bwd_bary<D>, dim3(grid), dim3(256), 0, stream, n, Fd, vi, rows, fieldT, grad_bary);
 }
 
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
 // (B).  One wavefront per ray, lane = sample, chunks of 64 samples.  Each lane keeps the sums of m and t m of ITS samples
 // (sample lane, lane + 64, ... in that order); after the last chunk the 64 lane sums are combined by a butterfly
 // (xor 32, 16, ..., 1) and lane 0 writes the ray's two rows: one writer per ray, the same bits on every run.  The twelve vertex
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(256) void k_sample_positions_bwd(size_t R, uint32_t
         }
         if (grad_o || grad_d) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { so[c] = wave_sum(so[c]); sd[c] = wave_sum(sd[c]); }
+            for (int c = 0; c < 3; ++c) { so[c] = rayops::wave_sum(so[c]); sd[c] = rayops::wave_sum(sd[c]); }
             if (lane == 0) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {

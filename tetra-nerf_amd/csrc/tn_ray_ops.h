@@ -1,9 +1,10 @@
-// tn_ray_ops.h -- the per-RAY stages between trace_rays and the frame (coarse sampler, PDF sampler, composite) as wave-level
-// device functions: ONE wavefront works on one ray.  The stand-alone kernels (k_sample_coarse / k_sample_pdf in
-// tn_samplers.hip, k_composite in tn_mlp.hip) and the persistent render kernel (tn_render_rays.hip) call the SAME functions,
-// so a ray's values do not depend on which launch shape produced them.
-// Reference: tetranerf/nerfstudio/model.py:111-192, 531-557, 582-586, 632-662 (+ nerfstudio's UniformSampler / PDFSampler /
-// RaySamples.get_weights / renderers, restated in tetra-nerf_amd/render.py -- those PyTorch statements are the parity definition).
+// tn_ray_ops.h -- the per-RAY stages between trace_rays and the frame (coarse sampler, PDF sampler, matcher, composite) as
+// wave-level device functions: ONE wavefront works on one ray.  The stand-alone kernels (k_sample_coarse / k_sample_pdf in
+// tn_samplers.hip, k_find_matched in tn_match.hip, k_composite in tn_mlp.hip) and the persistent render kernel
+// (tn_render_rays.hip) call the SAME functions, so a ray's values do not depend on which launch shape produced them.
+// Reference: tetranerf/nerfstudio/model.py:111-192, 531-557, 560-567, 582-586, 632-662, src/tetrahedra_tracer.cu:115-160 (+
+// nerfstudio's UniformSampler / PDFSampler / RaySamples.get_weights / renderers, restated in tetra-nerf_amd/render.py -- those
+// PyTorch statements are the parity definition).
 #pragma once
 #include "tn_device.h"
 #include "tn_kernels.h"
@@ -463,6 +464,177 @@ __device__ __forceinline__ void ray_composite(uint32_t S, const float *__restric
     if (S <= 64 * 2) ray_composite_chunks<2>(S, sigma, rgb, e, background, out_rgb3, out_acc, out_depth, out_w, lane);
     else if (S <= 64 * 5) ray_composite_chunks<5>(S, sigma, rgb, e, background, out_rgb3, out_acc, out_depth, out_w, lane);
     else ray_composite_chunks<9>(S, sigma, rgb, e, background, out_rgb3, out_acc, out_depth, out_w, lane);
+}
+
+// global-memory hand-over between two steps of the SAME wave (a lane reads, or overwrites, what another lane of its wave wrote)
+__device__ __forceinline__ void wave_global_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// The matcher (find_visited_cells, src/tetrahedra_tracer.cu:115-160) of one ray: its S sample distances against its n <= M
+// sorted segments, entry / exit barycentrics lerped.  The per-sample two-pointer merge of the reference becomes an independent
+// binary search over the running maximum of t_out (valid because the sample distances ascend: the sequential pointer equals
+// "first segment whose t_out >= d"); rays whose distances do not ascend take the literal serial walk
+// on lane 0.  All outputs are written by consecutive lanes, including the defaults the reference gets from torch::full / zeros
+// (src/py_binding.cpp:188-191).
+// MatchRows: the trace rows (all rays; `src` = this ray's row).  MatchOut: the outputs of THIS ray ([S] / [S] / [S,4] / [S,3]).
+// dist_of(j): distance of sample j (a row of distances in k_find_matched, the centre of bin j of the ray's edges in the render
+// kernel).  FULL: mask and cell ids too (the MLP kernels read vertex ids and barycentrics only).  PRE: dv0 holds the ray's
+// first 512 bounds as load_bounds() requested them (the render kernel issues that ahead of the sampler / composite of the same
+// ray, so that the rows are back when the matcher starts); otherwise they are loaded here, in place.
+// tin / pmax: 2 M floats of LDS owned by the wave alone (hence lds_sync, not a block barrier).
+struct MatchRows { const uint32_t *visited; const float *dist, *bary; const uint32_t *verts; };
+struct MatchOut { uint32_t *cells; uint8_t *mask; uint32_t *verts; float *bary; };
+
+__device__ __forceinline__ void load_bounds(uint32_t M, size_t src, uint32_t n, const float *dist, float2 (&dv)[8], int lane) {
+    if (n > M) n = M;
+    const float2 *drow = reinterpret_cast<const float2 *>(dist) + src * M;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const uint32_t j = 64u * c + lane;
+        dv[c] = make_float2(0.f, -INFINITY);
+        if (j < n) dv[c] = drow[j];
+    }
+}
+
+template <int UM, bool FULL, bool PRE, typename Dist>
+__device__ __forceinline__ void ray_match(uint32_t S, uint32_t M, size_t src, uint32_t n, const MatchRows &rows, Dist dist_of,
+                                          const MatchOut &out, float *tin, float *pmax, int lane, const float2 (&dv0)[8]) {
+    if (n > M) n = M;
+    const float2 *drow = reinterpret_cast<const float2 *>(rows.dist) + src * M;
+    // do the sample distances ascend?  The loads of a whole group of 64 UM samples (with the neighbours the test needs) are
+    // requested together: the wave owns its ray alone and every dependent round trip is exposed.
+    bool bad = false;
+    for (uint32_t base = 0; base + 1 < S; base += 64 * UM) {
+        float a0[UM], a1[UM];
+#pragma unroll
+        for (int u = 0; u < UM; ++u) {
+            const uint32_t j = base + 64 * u + lane;
+            a0[u] = a1[u] = 0.f;
+            if (j + 1 < S) { a0[u] = dist_of(j); a1[u] = dist_of(j + 1); }
+        }
+#pragma unroll
+        for (int u = 0; u < UM; ++u) {
+            const uint32_t j = base + 64 * u + lane;
+            if (j + 1 < S) bad |= !(a0[u] <= a1[u]);
+        }
+    }
+    // stage bounds + inclusive running max of t_out (wave scans over chunks of 64; the rows of up to 8 chunks requested at once,
+    // their scans interleaved: wave_incl_max_multi)
+    float carry = -INFINITY;
+    for (uint32_t base0 = 0; base0 < n; base0 += 512) {
+        float2 dv[8];
+        float mx[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const uint32_t j = base0 + 64u * c + lane;
+            if (PRE && !base0) dv[c] = dv0[c];
+            else { dv[c] = make_float2(0.f, -INFINITY); if (j < n) dv[c] = drow[j]; }   // (PRE: rays with more than 512 segments)
+            mx[c] = dv[c].y;
+        }
+        wave_incl_max_multi<8>(mx, lane);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const uint32_t j = base0 + 64u * c + lane;
+            const float m = fmaxf(mx[c], carry);
+            if (j < n) { tin[j] = dv[c].x; pmax[j] = m; }
+            carry = __shfl(m, 63);
+        }
+    }
+    const bool ascending = (__ballot(bad) == 0ull);
+    lds_sync();
+
+    if (ascending) {
+        // UM sample chunks of 64 per iteration: their searches (LDS) and segment gathers (global) are independent, so the
+        // dependent chain search -> gather -> store is paid once per 64 UM samples
+        uint32_t top = 1;                       // largest power of two <= n (0 for n == 0)
+        while ((top << 1) <= n && (top << 1) != 0) top <<= 1;
+        if (n == 0) top = 0;
+        const uint32_t nlast = n ? n - 1 : 0;
+        for (uint32_t base = 0; base < S; base += 64 * UM) {
+            float cur[UM];
+            uint32_t p[UM];
+#pragma unroll
+            for (int u = 0; u < UM; ++u) {
+                const uint32_t j = base + 64 * u + lane;
+                cur[u] = j < S ? dist_of(j) : 0.f;
+                p[u] = 0;
+            }
+            // p = number of segments whose running-max t_out is below the sample = first p with pmax[p] >= cur.  Straight-line
+            // (clamped reads + selects): the UM reads of a step are issued together
+            for (uint32_t bit = top; bit > 0; bit >>= 1) {
+                float pv[UM];
+#pragma unroll
+                for (int u = 0; u < UM; ++u) { const uint32_t k = p[u] + bit - 1; pv[u] = pmax[k < nlast ? k : nlast]; }
+#pragma unroll
+                for (int u = 0; u < UM; ++u) p[u] = (p[u] + bit <= n && pv[u] < cur[u]) ? p[u] + bit : p[u];
+            }
+            bool mk[UM];
+            uint32_t cell[UM];
+            uint4 vv[UM];
+            float t_in[UM], t_out[UM], tv[UM];
+            float2 q0[UM], q1[UM], q2[UM];
+#pragma unroll
+            for (int u = 0; u < UM; ++u) tv[u] = tin[p[u] < nlast ? p[u] : nlast];
+#pragma unroll
+            for (int u = 0; u < UM; ++u) {
+                const uint32_t j = base + 64 * u + lane;
+                mk[u] = false; cell[u] = TN_EMPTY; vv[u] = make_uint4(TN_EMPTY, TN_EMPTY, TN_EMPTY, TN_EMPTY);
+                t_in[u] = 0.f; t_out[u] = 1.f; q0[u] = q1[u] = q2[u] = make_float2(0.f, 0.f);
+                if (j < S && p[u] < n && tv[u] <= cur[u]) {
+                    const size_t g = src * M + p[u];
+                    mk[u] = true;
+                    t_in[u] = tv[u]; t_out[u] = drow[p[u]].y;
+                    if (FULL) cell[u] = rows.visited[g];
+                    vv[u] = *reinterpret_cast<const uint4 *>(rows.verts + 4 * g);
+                    const float2 *bp = reinterpret_cast<const float2 *>(rows.bary + 6 * g);
+                    q0[u] = bp[0]; q1[u] = bp[1]; q2[u] = bp[2];  // c1.xyz = q0.x q0.y q1.x ; c2.xyz = q1.y q2.x q2.y
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UM; ++u) {
+                const uint32_t j = base + 64 * u + lane;
+                if (j >= S) continue;
+                float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+                if (mk[u]) {
+                    const float mult = (cur[u] - t_in[u]) / (t_out[u] - t_in[u]);
+                    b0 = (1 - mult) * q0[u].x + mult * q1[u].y;
+                    b1 = (1 - mult) * q0[u].y + mult * q2[u].x;
+                    b2 = (1 - mult) * q1[u].x + mult * q2[u].y;
+                }
+                if (FULL) { out.mask[j] = mk[u]; out.cells[j] = cell[u]; }
+                *reinterpret_cast<uint4 *>(out.verts + 4 * (size_t)j) = vv[u];
+                out.bary[3 * (size_t)j] = b0; out.bary[3 * (size_t)j + 1] = b1; out.bary[3 * (size_t)j + 2] = b2;
+            }
+        }
+    } else {
+        // defaults everywhere, then the literal pointer walk on lane 0 (src/tetrahedra_tracer.cu:129-160)
+        for (uint32_t j = lane; j < S; j += 64) {
+            if (FULL) { out.mask[j] = 0; out.cells[j] = TN_EMPTY; }
+            *reinterpret_cast<uint4 *>(out.verts + 4 * (size_t)j) = make_uint4(TN_EMPTY, TN_EMPTY, TN_EMPTY, TN_EMPTY);
+            out.bary[3 * (size_t)j] = 0.f; out.bary[3 * (size_t)j + 1] = 0.f; out.bary[3 * (size_t)j + 2] = 0.f;
+        }
+        wave_global_sync();
+        if (lane == 0) {
+            uint32_t p = 0;
+            for (uint32_t j = 0; j < S; ++j) {
+                const float cur = dist_of(j);
+                while (p < n && drow[p].y < cur) p++;
+                if (p >= n) break;
+                const float2 hd = drow[p];
+                if (hd.x <= cur) {
+                    const size_t g = src * M + p;
+                    if (FULL) { out.mask[j] = 1; out.cells[j] = rows.visited[g]; }
+                    for (int k = 0; k < 4; ++k) out.verts[4 * (size_t)j + k] = rows.verts[4 * g + k];
+                    const float mult = (cur - hd.x) / (hd.y - hd.x);
+                    for (int k = 0; k < 3; ++k)
+                        out.bary[3 * (size_t)j + k] = (1 - mult) * rows.bary[6 * g + k] + mult * rows.bary[6 * g + 3 + k];
+                }
+            }
+        }
+    }
+    lds_sync();
 }
 
 }  // namespace rayops

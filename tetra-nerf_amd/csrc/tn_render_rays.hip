@@ -18,8 +18,9 @@
 //     tile's samples as one contiguous stream: no instruction of another stage between two MFMA layers.
 // The ray phases cost a few dependent round trips per ray (~1 % of a tile's time, measured in DESIGN.md section 4.5b); the
 // kernel chain pays the same stages as separate launches over the whole chunk plus its intermediates' allocations.
-// Every stage is the SAME device function the stand-alone kernels call (tn_ray_ops.h, tn_mlp_fwd.h; the matcher restates
-// k_find_matched's expressions), so the frame is bit-identical to the kernel chain's (tests/test_render_gpu.py).
+// Every stage is the SAME device function the stand-alone kernels call (tn_ray_ops.h: samplers, matcher, composite;
+// tn_mlp_fwd.h / tn_mlp_x3_fwd.h: the MLP phases), so the frame is bit-identical to the kernel chain's
+// (tests/test_render_rays_gpu.py, tests/test_match_gpu.py).
 #include <cstdlib>
 
 #include "tn_mlp_fwd.h"
@@ -79,159 +80,6 @@ struct RenderRaysParams {
     unsigned long long *prof;      // [8] DIAG builds only (TETRANERF_HIP_RENDER_PROFILE=1): 100 MHz ticks per phase kind, summed over blocks
 };
 
-// one ray's samples (the bin centres of e[0 .. S]) against its segments: vi [S] x 4 ids, bc [S] x 3 weights.  The expressions
-// are k_find_matched's (tn_match.hip); only vertex ids and barycentrics are produced (the MLP kernel reads nothing else).
-// tin / pmax: 2 M floats of LDS owned by the wave.
-// n = num_visited[src] (the kernel loads the counts of a whole tile at once: no dependent load here); dv0: the ray's first 512
-// segment bounds as load_bounds() requested them (the caller issues that ahead of the sampler / composite of the same ray, so
-// that the rows are back when the matcher starts); e: global or LDS.
-__device__ __forceinline__ void load_bounds(uint32_t M, size_t src, uint32_t n, const RenderRaysParams &p, float2 (&dv)[8], int lane) {
-    if (n > M) n = M;
-    const float2 *drow = reinterpret_cast<const float2 *>(p.dist) + src * M;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const uint32_t j = 64u * c + lane;
-        dv[c] = make_float2(0.f, -INFINITY);
-        if (j < n) dv[c] = drow[j];
-    }
-}
-
-template <int UM>
-__device__ __forceinline__ void ray_match(uint32_t S, uint32_t M, size_t src, uint32_t n, const RenderRaysParams &p, const float *e,
-                                          uint32_t *__restrict__ vi_out, float *__restrict__ bc_out, float *tin, float *pmax, int lane,
-                                          const float2 (&dv0)[8]) {
-    if (n > M) n = M;
-    const float2 *drow = reinterpret_cast<const float2 *>(p.dist) + src * M;
-    // do the sample distances ascend?  (distance j = centre of bin j, as the callers of find_visited_cells compute it.)  The
-    // loads of a whole group of 64 * UM samples are requested together, ahead of the bounds': the wave owns its ray alone and
-    // every dependent round trip is exposed.
-    bool bad = false;
-    for (uint32_t base = 0; base + 1 < S; base += 64 * UM) {
-        float a0[UM], a1[UM], a2[UM];
-#pragma unroll
-        for (int u = 0; u < UM; ++u) {
-            const uint32_t j = base + 64 * u + lane;
-            a0[u] = a1[u] = a2[u] = 0.f;
-            if (j + 1 < S) { a0[u] = e[j]; a1[u] = e[j + 1]; a2[u] = e[j + 2]; }
-        }
-#pragma unroll
-        for (int u = 0; u < UM; ++u) {
-            const uint32_t j = base + 64 * u + lane;
-            if (j + 1 < S) bad |= !((a1[u] + a0[u]) / 2.0f <= (a2[u] + a1[u]) / 2.0f);
-        }
-    }
-    // stage bounds + inclusive running max of t_out (wave scans over chunks of 64; the rows of up to 8 chunks requested at once,
-    // their scans interleaved: rayops::wave_incl_max_multi)
-    float carry = -INFINITY;
-    for (uint32_t base0 = 0; base0 < n; base0 += 512) {
-        float2 dv[8];
-        float mx[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint32_t j = base0 + 64u * c + lane;
-            dv[c] = dv0[c];
-            if (base0) { dv[c] = make_float2(0.f, -INFINITY); if (j < n) dv[c] = drow[j]; }   // (rays with more than 512 segments)
-            mx[c] = dv[c].y;
-        }
-        wave_incl_max_multi<8>(mx, lane);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint32_t j = base0 + 64u * c + lane;
-            const float m = fmaxf(mx[c], carry);
-            if (j < n) { tin[j] = dv[c].x; pmax[j] = m; }
-            carry = __shfl(m, 63);
-        }
-    }
-    const bool ascending = (__ballot(bad) == 0ull);
-    lds_sync();
-
-    if (ascending) {
-        uint32_t top = 1;                       // largest power of two <= n (0 for n == 0)
-        while ((top << 1) <= n && (top << 1) != 0) top <<= 1;
-        if (n == 0) top = 0;
-        for (uint32_t base = 0; base < S; base += 64 * UM) {
-            float cur[UM];
-            uint32_t pp[UM];
-#pragma unroll
-            for (int u = 0; u < UM; ++u) {
-                const uint32_t j = base + 64 * u + lane;
-                cur[u] = j < S ? (e[j + 1] + e[j]) / 2.0f : 0.f;
-                pp[u] = 0;
-            }
-            // pp = number of segments whose running-max t_out is below the sample = first pp with pmax[pp] >= cur.  Straight-line
-            // (clamped reads + selects): the UM reads of a step are issued together
-            const uint32_t nlast = n ? n - 1 : 0;
-            for (uint32_t bit = top; bit > 0; bit >>= 1) {
-                float pv[UM];
-#pragma unroll
-                for (int u = 0; u < UM; ++u) { const uint32_t k = pp[u] + bit - 1; pv[u] = pmax[k < nlast ? k : nlast]; }
-#pragma unroll
-                for (int u = 0; u < UM; ++u) pp[u] = (pp[u] + bit <= n && pv[u] < cur[u]) ? pp[u] + bit : pp[u];
-            }
-            bool mk[UM];
-            uint4 vv[UM];
-            float t_in[UM], t_out[UM];
-            float2 q0[UM], q1[UM], q2[UM];
-            float tv[UM];
-#pragma unroll
-            for (int u = 0; u < UM; ++u) tv[u] = tin[pp[u] < nlast ? pp[u] : nlast];
-#pragma unroll
-            for (int u = 0; u < UM; ++u) {
-                const uint32_t j = base + 64 * u + lane;
-                mk[u] = false; vv[u] = make_uint4(TN_EMPTY, TN_EMPTY, TN_EMPTY, TN_EMPTY);
-                t_in[u] = 0.f; t_out[u] = 1.f; q0[u] = q1[u] = q2[u] = make_float2(0.f, 0.f);
-                if (j < S && pp[u] < n && tv[u] <= cur[u]) {
-                    const size_t g = src * M + pp[u];
-                    mk[u] = true;
-                    t_in[u] = tv[u]; t_out[u] = drow[pp[u]].y;
-                    vv[u] = *reinterpret_cast<const uint4 *>(p.verts + 4 * g);
-                    const float2 *bp = reinterpret_cast<const float2 *>(p.bary + 6 * g);
-                    q0[u] = bp[0]; q1[u] = bp[1]; q2[u] = bp[2];  // c1.xyz = q0.x q0.y q1.x ; c2.xyz = q1.y q2.x q2.y
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UM; ++u) {
-                const uint32_t j = base + 64 * u + lane;
-                if (j >= S) continue;
-                float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-                if (mk[u]) {
-                    const float mult = (cur[u] - t_in[u]) / (t_out[u] - t_in[u]);
-                    b0 = (1 - mult) * q0[u].x + mult * q1[u].y;
-                    b1 = (1 - mult) * q0[u].y + mult * q2[u].x;
-                    b2 = (1 - mult) * q1[u].x + mult * q2[u].y;
-                }
-                *reinterpret_cast<uint4 *>(vi_out + 4 * (size_t)j) = vv[u];
-                bc_out[3 * (size_t)j] = b0; bc_out[3 * (size_t)j + 1] = b1; bc_out[3 * (size_t)j + 2] = b2;
-            }
-        }
-    } else {
-        // defaults everywhere, then the literal pointer walk on lane 0 (src/tetrahedra_tracer.cu:129-160)
-        for (uint32_t j = lane; j < S; j += 64) {
-            *reinterpret_cast<uint4 *>(vi_out + 4 * (size_t)j) = make_uint4(TN_EMPTY, TN_EMPTY, TN_EMPTY, TN_EMPTY);
-            bc_out[3 * (size_t)j] = 0.f; bc_out[3 * (size_t)j + 1] = 0.f; bc_out[3 * (size_t)j + 2] = 0.f;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-            uint32_t pos = 0;
-            for (uint32_t j = 0; j < S; ++j) {
-                const float cur = (e[j + 1] + e[j]) / 2.0f;
-                while (pos < n && drow[pos].y < cur) pos++;
-                if (pos >= n) break;
-                const float2 hd = drow[pos];
-                if (hd.x <= cur) {
-                    const size_t g = src * M + pos;
-                    for (int k = 0; k < 4; ++k) vi_out[4 * (size_t)j + k] = p.verts[4 * g + k];
-                    const float mult = (cur - hd.x) / (hd.y - hd.x);
-                    for (int k = 0; k < 3; ++k)
-                        bc_out[3 * (size_t)j + k] = (1 - mult) * p.bary[6 * g + k] + mult * p.bary[6 * g + 3 + k];
-                }
-            }
-        }
-    }
-    lds_sync();
-}
-
 // direction encoding of one ray, k_dir_encoding<ENC_PAD>'s elements (tn_mlp_common.h) one pair per lane
 __device__ __forceinline__ void ray_dir_encoding(const float *__restrict__ d3, float *__restrict__ e, int lane) {
     if (lane < 12) {
@@ -244,10 +92,19 @@ __device__ __forceinline__ void ray_dir_encoding(const float *__restrict__ d3, f
     }
 }
 
-// global-memory hand-over between two ray phases of the SAME wave (a lane reads what another lane of its wave wrote)
-__device__ __forceinline__ void wave_global_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
+// one ray's samples (the bin centres of e[0 .. S], as the callers of find_visited_cells compute them; e: global or LDS) against
+// its segments: rayops::ray_match, as k_find_matched runs it (tn_match.hip), producing vertex ids and barycentrics only -- vi
+// [S] x 4, bc [S] x 3: the MLP phases read nothing else.  n = num_visited[src] (the kernel loads the counts of a whole tile at
+// once: no dependent load here); dv0: the ray's first 512 bounds (rayops::load_bounds, issued by the caller ahead of the
+// sampler / composite of the same ray); tin / pmax: 2 M floats of the wave's LDS.  The outputs are __restrict__ HERE (the structs
+// of ray_match carry no qualifier; k_find_matched has it on its kernel arguments): without it this kernel measured 0.9 % (fp32)
+// and 1.6 % (bf16x3) slower per frame (profiles/match_dedupe.txt, 4a).
+template <int UM>
+__device__ __forceinline__ void match_bins(uint32_t S, size_t src, uint32_t n, const RenderRaysParams &p, const float *e,
+                                           uint32_t *__restrict__ vi_out, float *__restrict__ bc_out, float *tin, float *pmax, int lane,
+                                           const float2 (&dv0)[8]) {
+    ray_match<UM, false, true>(S, p.M, src, n, MatchRows{nullptr, p.dist, p.bary, p.verts}, [e](uint32_t j) { return (e[j + 1] + e[j]) / 2.0f; },
+                               MatchOut{nullptr, nullptr, vi_out, bc_out}, tin, pmax, lane, dv0);
 }
 
 }  // namespace
@@ -325,7 +182,7 @@ __global__ __launch_bounds__(RR_BLOCK, 2) void k_render_rays(RenderRaysParams p)
             const uint32_t nv = (uint32_t)__builtin_amdgcn_readlane((int)l_nv, (int)i);
             const float near = __shfl(l_near, (int)i), far = __shfl(l_far, (int)i);
             float2 dv[8];
-            load_bounds(M, ray, nv, p, dv, lane);            // back by the time the matcher wants them
+            load_bounds(M, ray, nv, p.dist, dv, lane);            // back by the time the matcher wants them
             float *e = edges_c + (size_t)t * (S + 1);
             ray_sample_coarse_nf(S, M, ray, nv, near, far, p.dist, p.lin, nullptr, p.biased, e, el, wl, lane);
             // the head layer's per-ray term: Wh[:, :27] enc(dir) + the appearance embedding's bias (head_ray_term, as k_head_ray_term)
@@ -348,8 +205,8 @@ __global__ __launch_bounds__(RR_BLOCK, 2) void k_render_rays(RenderRaysParams p)
                 }
             }
             lds_sync();
-            if (S <= 256) ray_match<4>(S, M, ray, nv, p, el, vi + 4 * (size_t)t * S, bc + 3 * (size_t)t * S, wl, wl + M, lane, dv);
-            else ray_match<9>(S, M, ray, nv, p, el, vi + 4 * (size_t)t * S, bc + 3 * (size_t)t * S, wl, wl + M, lane, dv);
+            if (S <= 256) match_bins<4>(S, ray, nv, p, el, vi + 4 * (size_t)t * S, bc + 3 * (size_t)t * S, wl, wl + M, lane, dv);
+            else match_bins<9>(S, ray, nv, p, el, vi + 4 * (size_t)t * S, bc + 3 * (size_t)t * S, wl, wl + M, lane, dv);
         }
         __syncthreads();
         tick(0);
@@ -375,7 +232,7 @@ if constexpr (X3) x3::forward_group<true, true>(reinterpret_cast<uint4 *>(lds), 
                 const uint32_t nv = (uint32_t)__builtin_amdgcn_readlane((int)l_nv, (int)i);
                 const float near = __shfl(l_near, (int)i), far = __shfl(l_far, (int)i);
                 float2 dv[8];
-                load_bounds(M, ray, nv, p, dv, lane);        // in flight during the composite and the sampler
+                load_bounds(M, ray, nv, p.dist, dv, lane);        // in flight during the composite and the sampler
                 const float *e = edges_c + (size_t)t * (S + 1);
                 ray_composite(S, sigma + (size_t)t * S, nullptr, e, p.bg, nullptr, nullptr, nullptr, wl, lane);
                 lds_sync();
@@ -384,8 +241,8 @@ if constexpr (X3) x3::forward_group<true, true>(reinterpret_cast<uint4 *>(lds), 
                 ray_sample_pdf(S, nb, e, wl, near, far, p.u_table, nullptr, p.hist_pad, p.eps, ef, wl + w_floats, lane, efl);
                 const float *em = efl;
                 if (!lds_edges) { wave_global_sync(); em = ef; }
-                if (Sf <= 256) ray_match<4>(Sf, M, ray, nv, p, em, vi + 4 * (size_t)t * Sf, bc + 3 * (size_t)t * Sf, wl, wl + M, lane, dv);
-                else ray_match<9>(Sf, M, ray, nv, p, em, vi + 4 * (size_t)t * Sf, bc + 3 * (size_t)t * Sf, wl, wl + M, lane, dv);
+                if (Sf <= 256) match_bins<4>(Sf, ray, nv, p, em, vi + 4 * (size_t)t * Sf, bc + 3 * (size_t)t * Sf, wl, wl + M, lane, dv);
+                else match_bins<9>(Sf, ray, nv, p, em, vi + 4 * (size_t)t * Sf, bc + 3 * (size_t)t * Sf, wl, wl + M, lane, dv);
             }
             __syncthreads();
             tick(2);
@@ -453,7 +310,7 @@ void launch_render_rays(const uint32_t *num_visited, const float *dist, const fl
     if (r_max == 0) return;
     const uint32_t nb = S_fine + 1;
     // per wave: phase 1 = [tin / pmax (or the biased sampler's cum): 2 M][coarse edges: S + 1]; phase 2 = [coarse weights |
-    // PDF sampler, re-used as tin / pmax][merged fine edges: S + nb + 1]
+    // PDF sampler, re-used as tin / pmax][merged fine edges: S + nb + 1]  (restated by TetraRenderer._one_launch_ok, render.py)
     const size_t w_fl = ((size_t)S + 3) & ~(size_t)3;
     const size_t region = (std::max<size_t>(phase1_edges_offset(M) + (S + 1), S_fine ? std::max<size_t>(2 * (size_t)M, w_fl + pdf_lds_floats(S, nb)) +
                                                                                   (size_t)S + nb + 1 : 0) + 3) & ~(size_t)3;

@@ -319,10 +319,6 @@ __global__ __launch_bounds__(WALK_BLOCK) void k_hull_entry(WalkParams p) {
     bool flag = false;  // ray must be re-traced by the general path
     uint32_t why = 0;   // first reason (1..12), counted in stats[STAT_REASON + why]
 
-    // ------------------------------------------------------------------ hull crossing search
-    // Wave-uniform traversal of the (small) hull BVH: a node is visited if ANY lane's line hits
-    // its padded box; box / triangle data are read through uniform (scalar) loads, every lane
-    // tests its own ray.  No stack: the tree has a fixed depth (<= 3 internal levels).
     // rounding distance of a projected vertex: the box padding of the BVH path (tn_device.h: line_box)
     const float pad = 16.0f * 1.1920929e-7f * (fmaxf(fabsf(ox), fmaxf(fabsf(oy), fabsf(oz))) + p.scene_max);
     // Rule 8 (fold guard, see the header): delta = 7 * 2^-24 * (|o| + scene) bounds the error of a sheared 2-D vertex

@@ -200,6 +200,37 @@ def composite(sigma: torch.Tensor, rgb: torch.Tensor, starts: torch.Tensor, ends
     return out_rgb, acc, depth, weights
 
 
+TRACE_KEYS = ("num_visited_cells", "visited_cells", "barycentric_coordinates", "hit_distances", "vertex_indices")
+
+
+def trace_rows(out) -> list:
+    """The five row tensors of a trace_rays result, in the order find_visited_cells takes them."""
+    return [out[k] for k in TRACE_KEYS]
+
+
+def bin_centres(edges: torch.Tensor) -> torch.Tensor:
+    """[R,S] sample distances of [R,S+1] bin edges: what find_visited_cells is asked to match."""
+    return ((edges[:, 1:] + edges[:, :-1]) / 2).contiguous()
+
+
+def hit_near_far(out, idx: torch.Tensor):
+    """([r,1], [r,1]) first entry and last exit distance of the hitting rays `idx` (rows of empty rays are unwritten without
+    dense tails: only those of hitting rays are read)."""
+    hd = out["hit_distances"]
+    return hd[idx, 0, 0][:, None], hd[idx, (out["num_visited_cells"][idx].long() - 1), 1][:, None]
+
+
+def coarse_sigma(mlp, feats: torch.Tensor) -> torch.Tensor:
+    """[R,S] densities of the coarse pass (model.py:577-581): mlp_base + density head + softplus, or the `coarse_sigma` of an
+    adapter around other modules (nerfstudio_plugin.ModelMLP)."""
+    if hasattr(mlp, "coarse_sigma"):
+        return mlp.coarse_sigma(feats)
+    x = feats
+    for lin in mlp.base:
+        x = torch.relu(lin(x))
+    return torch.nn.functional.softplus(mlp.density(x))[..., 0]
+
+
 def median_margin(weights: torch.Tensor) -> torch.Tensor:
     """[R,1] distance of a ray's cumulative weights from the median threshold 0.5: the median depth of a ray is DECIDED
     (independent of round-off in the weights) when this exceeds the accumulated rounding error of the cumulative sum."""
@@ -226,26 +257,17 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
     depth = torch.full((R, 1), far_plane, dtype=torch.float32, device=origins.device)
     margin = torch.full((R, 1), 0.5, dtype=torch.float32, device=origins.device)   # test aid: see median_margin
     if bool(ray_mask.any()):
-        lists = [out[k][ray_mask].contiguous() for k in ("num_visited_cells", "visited_cells", "barycentric_coordinates",
-                                                         "hit_distances", "vertex_indices")]
+        lists = [x[ray_mask].contiguous() for x in trace_rows(out)]
         near_r, far_r = nears[ray_mask], fars[ray_mask]
 
         def features(edges):
-            dist = ((edges[:, 1:] + edges[:, :-1]) / 2).contiguous()
-            traced = tracer.find_visited_cells(*lists, dist)
+            traced = tracer.find_visited_cells(*lists, bin_centres(edges))
             return interpolate_values(traced["vertex_indices"], traced["barycentric_coordinates"], field)
 
         edges, spacing = coarse_samples(near_r, far_r, num_samples, biased, lists[0], lists[3])
         feats = features(edges)
         if num_fine_samples > 0:
-            if hasattr(mlp, "coarse_sigma"):     # an adapter around other modules (nerfstudio_plugin.ModelMLP)
-                sigma_c = mlp.coarse_sigma(feats)
-            else:
-                x = feats
-                for lin in mlp.base:
-                    x = torch.relu(lin(x))
-                sigma_c = torch.nn.functional.softplus(mlp.density(x))[..., 0]
-            edges = pdf_sample_bins(spacing, ray_weights(sigma_c, edges), num_fine_samples, near_r, far_r)
+            edges = pdf_sample_bins(spacing, ray_weights(coarse_sigma(mlp, feats), edges), num_fine_samples, near_r, far_r)
             feats = features(edges)
         starts, ends = edges[:, :-1, None], edges[:, 1:, None]
         dirs = directions[ray_mask][:, None, :].expand(-1, edges.shape[1] - 1, -1)
@@ -398,7 +420,7 @@ class TetraRenderer:
         self.train_node_samples = 1 << 22      # render_train: samples per autograd node of the fused MLP (see there)
         # RGBRenderer background: grey level (1.0 white = default config, 0.0 black) or an (r, g, b) triple; render() /
         # render_train() take a per-call override (nerfstudio's BACKGROUND_COLOR_OVERRIDE, model.py:504-518)
-        self.background = background if isinstance(background, (int, float)) else tuple(float(x) for x in background_tensor(background).tolist())
+        self.background = self._bg(background)
         # samplers as device kernels on the trace rows in place (tn_sample_coarse / tn_sample_pdf): a render is then
         # trace -> [sampler -> pass] x 2 with no PyTorch operator in between (False: the PyTorch statements above, ~15
         # small kernels per pass -- the parity definition, kept for tests and A/B)
@@ -443,13 +465,49 @@ class TetraRenderer:
         return rows
 
     def _bg(self, background):
+        """A grey level as it is, a colour as an (r, g, b) tuple of floats; None: the renderer's own."""
         if background is None:
             return self.background
         return background if isinstance(background, (int, float)) else tuple(float(x) for x in background_tensor(background).tolist())
 
+    def _miss_frame(self, R, bg, dev):
+        """(rgb [R,3], accumulation [R,1], depth [R,1]) of R rays that meet nothing: background, 0, far plane."""
+        return (self._background_rows(R, bg, dev), torch.zeros((R, 1), dtype=torch.float32, device=dev),
+                torch.full((R, 1), self.far_plane, dtype=torch.float32, device=dev))
+
+    def _locate(self, lists, edges, ray_index, count=None):
+        """find_visited_cells of the bin centres of `edges` [r,S+1] on the trace rows in place: row i of the result belongs to
+        trace row ray_index[i]; count: device-side number of rows to match."""
+        kw = {} if count is None else {"count": count}
+        return self.tracer.find_visited_cells(*lists, bin_centres(edges), ray_index=ray_index, **kw)
+
+    def _chain_passes(self, lists, edges, ray_index, w, mode, pdf, count=None, coarse_weights=None):
+        """The sample placement of the kernel chain: locate -> [coarse weights -> pdf(edges, weights) -> locate] (the bracket
+        with fine samples only).  Coarse weights: gather + mlp_base + density head in one kernel and get_weights in one more,
+        unless `coarse_weights(traced, edges)` states them otherwise.  Returns (traced, final edges)."""
+        traced = self._locate(lists, edges, ray_index, count)
+        if self.S_fine > 0:
+            if coarse_weights is None:
+                S = edges.shape[1] - 1
+                sigma_c = self.cpp.mlp_forward_gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field,
+                                                      None, w, S, mode=mode, count=count)
+                weights_c = self.cpp.composite(sigma_c.view(-1, S), None, edges, count=count)
+            else:
+                weights_c = coarse_weights(traced, edges)
+            edges = pdf(edges, weights_c)
+            traced = self._locate(lists, edges, ray_index, count)
+        return traced, edges
+
+    def _final_forward(self, vi, bc, edges, dirs, w, mode, hb, count=None):
+        """gather + MLP + heads of the final samples in one kernel (no [64, n] feature buffer): sigma [r,S], rgb [r,S,3]."""
+        S = edges.shape[1] - 1
+        sigma, col = self.cpp.mlp_forward_gather(vi, bc, self.field, dirs, w, S, mode=mode, ray_head_bias=hb, count=count)
+        return sigma.view(-1, S), col.view(-1, S, 3)
+
     def _one_launch_ok(self, mode):
         """tn_render_rays' preconditions: device samplers, the per-wave LDS regions of its ray phases fit (either arithmetic
-        since round 6: the bf16x3 mode runs x3::forward_group in the MLP phases)."""
+        since round 6: the bf16x3 mode runs x3::forward_group in the MLP phases).  `region` restates launch_render_rays'
+        per-wave LDS region (csrc/tn_render_rays.hip)."""
         region = max(max(2 * self.M, 28) + self.S + 1, (max(2 * self.M, 3 * self.S + self.S_fine + 6) + 2 * self.S + self.S_fine + 2) if self.S_fine else 0) + 4
         return (self.fused_pass is not False and mode in ("fp32", "bf16x3") and self.device_samplers and 8 * 4 * region <= 160 * 1024
                 and self.S + self.S_fine + 2 <= 8192)
@@ -477,16 +535,13 @@ class TetraRenderer:
         nv = out["num_visited_cells"]
         ray_mask = nv > 0
         R, dev = origins.shape[0], origins.device
-        rgb = self._background_rows(R, bg, dev)
-        acc = torch.zeros((R, 1), dtype=torch.float32, device=dev)
-        depth = torch.full((R, 1), self.far_plane, dtype=torch.float32, device=dev)
+        rgb, acc, depth = self._miss_frame(R, bg, dev)
         res = {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask}
         if R == 0:
             return res
         # the 26 KB trace rows of the hitting rays are NOT compacted (model.py:546-567 copies them with boolean indexing):
         # samplers, matcher and composite read them in place through the ray index
-        lists = [out[k] for k in ("num_visited_cells", "visited_cells", "barycentric_coordinates", "hit_distances",
-                                  "vertex_indices")]
+        lists = trace_rows(out)
         order, count = cpp.compact_hits(nv)          # hitting rays first, in ray order; their number stays on the device
         w = mlp_weights(self.mlp)
         mode = self.mlp_mode
@@ -499,25 +554,11 @@ class TetraRenderer:
         order_l = order.long()
         dirs_o = d.index_select(0, order_l)
         hb = None if ray_head_bias is None else ray_head_bias.index_select(0, order_l).contiguous()
-
-        def locate(edges):
-            dist = ((edges[:, 1:] + edges[:, :-1]) / 2).contiguous()
-            return self.tracer.find_visited_cells(*lists, dist, ray_index=order, count=count)
-
         edges, near_far = cpp.sample_coarse(lists[0], lists[3], order, S, biased=self.biased, count=count)
-        traced = locate(edges)
-        if self.S_fine > 0:
-            # coarse pass: gather + mlp_base + density head in one kernel, weights in one more
-            sigma_c = cpp.mlp_forward_gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field,
-                                             None, w, S, mode=mode, count=count)
-            weights_c = cpp.composite(sigma_c.view(-1, S), None, edges, count=count)
-            edges = cpp.sample_pdf(edges, weights_c, near_far, self.S_fine, count=count)
-            traced = locate(edges)
-            S = edges.shape[1] - 1
-        # gather + MLP + heads in one kernel (no [64, n] feature buffer)
-        sigma, col = cpp.mlp_forward_gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field,
-                                            dirs_o, w, S, mode=mode, ray_head_bias=hb, count=count)
-        cpp.composite(sigma.view(-1, S), col.view(-1, S, 3), edges, background=bg, clamp=True, out=(rgb, acc, depth), ray_index=order,
+        traced, edges = self._chain_passes(lists, edges, order, w, mode, count=count,
+                                           pdf=lambda e, weights_c: cpp.sample_pdf(e, weights_c, near_far, self.S_fine, count=count))
+        sigma, col = self._final_forward(traced["vertex_indices"], traced["barycentric_coordinates"], edges, dirs_o, w, mode, hb, count)
+        cpp.composite(sigma, col, edges, background=bg, clamp=True, out=(rgb, acc, depth), ray_index=order,
                       count=count)
         return res
 
@@ -528,44 +569,25 @@ class TetraRenderer:
         the reference does; not the production path."""
         cpp, S = self.cpp, self.S
         out = self._trace(origins, directions)
-        nv = out["num_visited_cells"]
-        ray_mask = nv > 0
-        R, dev = origins.shape[0], origins.device
-        rgb = self._background_rows(R, bg, dev)
-        acc = torch.zeros((R, 1), dtype=torch.float32, device=dev)
-        depth = torch.full((R, 1), self.far_plane, dtype=torch.float32, device=dev)
+        ray_mask = out["num_visited_cells"] > 0
+        rgb, acc, depth = self._miss_frame(origins.shape[0], bg, origins.device)
         idx = torch.nonzero(ray_mask)[:, 0]
         mode = self.mlp_mode
         if idx.numel():
-            lists = [out[k] for k in ("num_visited_cells", "visited_cells", "barycentric_coordinates", "hit_distances",
-                                      "vertex_indices")]
+            lists = trace_rows(out)
             ridx = idx.to(torch.int32)
             w = mlp_weights(self.mlp)
             hb = None if ray_head_bias is None else ray_head_bias.index_select(0, idx).contiguous()
-
-            def locate(edges):
-                dist = ((edges[:, 1:] + edges[:, :-1]) / 2).contiguous()
-                return self.tracer.find_visited_cells(*lists, dist, ray_index=ridx)
-
-            # (rows of empty rays are unwritten without dense tails: nears / fars only of the hitting rays)
-            near_r = out["hit_distances"][idx, 0, 0][:, None]
-            far_r = out["hit_distances"][idx, (nv[idx].long() - 1), 1][:, None]
+            near_r, far_r = hit_near_far(out, idx)
             if self.biased:
                 edges = biased_sample_bins(near_r, far_r, S, lists[0][idx], lists[3][idx]).contiguous()
             else:
                 edges = uniform_sample_bins(near_r, far_r, S).contiguous()
-            traced = locate(edges)
-            if self.S_fine > 0:
-                sigma_c = cpp.mlp_forward_gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field,
-                                                 None, w, S, mode=mode)
-                weights_c = cpp.composite(sigma_c.view(-1, S), None, edges)
-                spacing = (edges - near_r) / (far_r - near_r)
-                edges = pdf_sample_bins(spacing, weights_c, self.S_fine, near_r, far_r).contiguous()
-                traced = locate(edges)
-                S = edges.shape[1] - 1
-            sigma, col = cpp.mlp_forward_gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field,
-                                                directions[idx].contiguous(), w, S, mode=mode, ray_head_bias=hb)
-            rgb_r, acc_r, depth_r = cpp.composite(sigma.view(-1, S), col.view(-1, S, 3), edges, background=bg, clamp=True)
+            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, pdf=lambda e, weights_c: pdf_sample_bins(
+                (e - near_r) / (far_r - near_r), weights_c, self.S_fine, near_r, far_r).contiguous())
+            sigma, col = self._final_forward(traced["vertex_indices"], traced["barycentric_coordinates"], edges,
+                                             directions[idx].contiguous(), w, mode, hb)
+            rgb_r, acc_r, depth_r = cpp.composite(sigma, col, edges, background=bg, clamp=True)
             rgb[idx] = rgb_r
             acc[idx] = acc_r
             depth[idx] = depth_r
@@ -647,13 +669,10 @@ class TetraRenderer:
                 if self.sync_free_train:           # this form knows its count on the host anyway
                     self._hit_fraction, self._hits_host_id = idx.numel() / max(R, 1), self._batch_id
         bg = self._bg(background)
-        rgb = self._background_rows(R, bg, dev)
-        acc = torch.zeros((R, 1), dtype=torch.float32, device=dev)
-        depth = torch.full((R, 1), self.far_plane, dtype=torch.float32, device=dev)
+        rgb, acc, depth = self._miss_frame(R, bg, dev)
         if idx.numel() == 0:
             return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask}
-        lists = [out[k] for k in ("num_visited_cells", "visited_cells", "barycentric_coordinates", "hit_distances",
-                                  "vertex_indices")]
+        lists = trace_rows(out)
         if ridx is None:
             ridx = idx.to(torch.int32)
         r = idx.numel()
@@ -670,46 +689,31 @@ class TetraRenderer:
                 edges, near_far = cpp.sample_coarse(lists[0], lists[3], ridx, S, biased=self.biased, t_rand=t_rand.contiguous())
                 near_r, far_r = near_far[:, 0:1], near_far[:, 1:2]
             else:
-                near_r = out["hit_distances"][idx, 0, 0][:, None]
-                far_r = out["hit_distances"][idx, (nv[idx].long() - 1), 1][:, None]
+                near_r, far_r = hit_near_far(out, idx)
                 near_far = torch.cat([near_r, far_r], 1).contiguous()
                 edges, spacing = coarse_samples(near_r, far_r, S, self.biased, lists[0][idx], lists[3][idx], t_rand)
                 edges = edges.contiguous()
 
-            def locate(e):
-                dist = ((e[:, 1:] + e[:, :-1]) / 2).contiguous()
-                return self.tracer.find_visited_cells(*lists, dist, ray_index=ridx)
-
-            traced = locate(edges)
-            if self.S_fine > 0:
-                if fused:
-                    sigma_c = cpp.mlp_forward_gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field,
-                                                     None, w, S, mode=mode).view(-1, S)
-                    weights_c = cpp.composite(sigma_c, None, edges)
-                else:       # model.py:577-582 in PyTorch
-                    gather = self._interpolate_values or cpp.interpolate_values
-                    feats_c = gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field)
-                    if hasattr(self.mlp, "coarse_sigma"):
-                        sigma_c = self.mlp.coarse_sigma(feats_c)
-                    else:
-                        x = feats_c
-                        for lin in self.mlp.base:
-                            x = torch.relu(lin(x))
-                        sigma_c = torch.nn.functional.softplus(self.mlp.density(x))[..., 0]
-                    weights_c = ray_weights(sigma_c, edges)
+            def pdf(e, weights_c):
+                nonlocal spacing
                 u_rand = rand.get("fine")
                 if u_rand is None:
                     u_rand = torch.rand((r, self.S_fine + 1), device=dev, generator=generator)
                 if self.device_samplers:
-                    edges = cpp.sample_pdf(edges, weights_c, near_far, self.S_fine, u_rand=u_rand.contiguous())
                     spacing = None
-                else:
-                    if spacing is None:
-                        spacing = (edges - near_r) / (far_r - near_r)
-                    edges, spacing = pdf_sample_bins(spacing, weights_c, self.S_fine, near_r, far_r, u_rand=u_rand, return_spacing=True)
-                    edges = edges.contiguous()
-                traced = locate(edges)
-                S = edges.shape[1] - 1
+                    return cpp.sample_pdf(e, weights_c, near_far, self.S_fine, u_rand=u_rand.contiguous())
+                if spacing is None:
+                    spacing = (e - near_r) / (far_r - near_r)
+                e, spacing = pdf_sample_bins(spacing, weights_c, self.S_fine, near_r, far_r, u_rand=u_rand, return_spacing=True)
+                return e.contiguous()
+
+            def weights_torch(traced, e):       # model.py:577-582 in PyTorch
+                gather = self._interpolate_values or cpp.interpolate_values
+                feats_c = gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field)
+                return ray_weights(coarse_sigma(self.mlp, feats_c), e)
+
+            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, pdf, coarse_weights=None if fused else weights_torch)
+            S = edges.shape[1] - 1
         dirs = directions[idx].contiguous()      # (a differentiable index: the view term of position_gradients)
         # per-ray bias of the head layer (appearance embedding; fused path only): differentiable w.r.t. the caller's tensor
         hb = None if ray_head_bias is None else ray_head_bias.index_select(0, idx).contiguous()
@@ -721,8 +725,8 @@ class TetraRenderer:
 
             if vertices is None:
                 vertices = self.tracer.tetrahedra_vertices
-            dist = ((edges[:, 1:] + edges[:, :-1]) / 2).contiguous()      # the distances `locate` matched: held constant
-            bc = sample_positions_grad(bc, vi, vertices.reshape(-1, 3), origins[idx], dirs, dist)
+            # (the distances `_locate` matched: held constant)
+            bc = sample_positions_grad(bc, vi, vertices.reshape(-1, 3), origins[idx], dirs, bin_centres(edges))
             if capture is not None:
                 capture["barycentric_positions"] = bc
         if capture is not None:   # the (non-differentiable) sample placement, for tests that restate the rest in float64
@@ -741,8 +745,7 @@ class TetraRenderer:
                 sigma, col = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
             sigma, col = sigma.view(-1, S), col.view(-1, S, 3)
         elif fused:               # no graph: the plain forward kernel, nothing saved
-            sigma, col = cpp.mlp_forward_gather(vi, bc, self.field, dirs, w, S, mode=mode, ray_head_bias=hb)
-            sigma, col = sigma.view(-1, S), col.view(-1, S, 3)
+            sigma, col = self._final_forward(vi, bc, edges, dirs, w, mode, hb)
         else:
             interpolate_values = self._interpolate_values
             if interpolate_values is None:
