@@ -401,6 +401,12 @@ int tn_mlp_set_weights(tn_mlp_t mlp, const tn_mlp_weights *weights, void *stream
  *   0  v_mfma_f32_32x32x2_f32: an exact fp32 fma chain (157 TFLOP/s peak) -- what every parity claim refers to;
  *   1  "bf16x3": v_mfma_f32_32x32x16_bf16 on operands split into three bf16 pieces, six partial products per
  *      multiply, fp32 accumulation: dropped terms < 2^-24 of a product at 2.67x fewer matrix-core cycles (opt-in).
+ *   2  "bf16": ONE v_mfma_f32_32x32x16_bf16 per product (opt-in, evaluation only, NOT at the parity bar of modes 0 and 1).  In
+ *      the four wide layers (mlp_base layers 0, 1, 2; mlp_head layer 0 on [direction encoding 27 | base 128]) both operands
+ *      of every product are rounded to bf16, round to nearest even -- the weight once by tn_mlp_set_weights, the input (the
+ *      fp32 activation; the fp32 direction encoding) as it enters the matrix core; products are accumulated in fp32, bias and
+ *      ray_head_bias added in fp32, ReLU taken in fp32; the narrow heads (density, rgb) read the fp32 activations and run in
+ *      fp32.  Only these two entry points take it: tn_mlp_forward_gather_train[_ex] and tn_render_rays_ex reject mode 2.
  * feats f32 [64, n] feature-major (the buffer tn_interpolate_values writes), dirs f32 [n/samples_per_ray, 3]
  * (one direction per ray; samples of a ray are consecutive) -> sigma f32 [n] (softplus), rgb f32 [n,3] (sigmoid).
  * rgb == NULL: density only (mlp_base + density head: the coarse pass of the model, model.py:577-581); dirs unused. */
@@ -446,7 +452,7 @@ int tn_render_rays(tn_mlp_t mlp, uint32_t max_ray_triangles, const uint32_t *num
                    const float *ray_head_bias, void *stream);
 /* ... with the arithmetic of the MLP phases as a per-call argument like tn_mlp_forward's `mode` (round 6): 0 = fp32 MFMA (what
  * tn_render_rays runs), 1 = bf16x3 (split-operand bf16 MFMA, csrc/tn_mlp_x3.hip; opt-in): then the frame is bit-identical to the
- * kernel chain run with mode 1.  Same reference span (model.py:531-662). */
+ * kernel chain run with mode 1.  Mode 2 is rejected (the kernel chain renders it).  Same reference span (model.py:531-662). */
 int tn_render_rays_ex(tn_mlp_t mlp, uint32_t max_ray_triangles, const uint32_t *num_visited, const float *hit_distances,
                    const float *barycentric, const uint32_t *vertex_indices, const uint32_t *ray_index, const uint32_t *count,
                    size_t num_hit_rays_max, uint32_t num_samples, uint32_t num_fine, int biased, const float *linspace,
@@ -516,7 +522,8 @@ int tn_mlp_forward_gather_train(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray
  * tn_mlp_forward_gather_train, 1 bf16x3 MFMA).  Mode 1: sigma / rgb are bit for bit those of tn_mlp_forward_gather(mode 1), and
  * x0, h1..h4 and masks are saved in the same layouts, so tn_mlp_backward / tn_mlp_ray_head_grad / tn_mlp_param_grads run
  * unchanged (fp32) on them: the gradient is the exact fp32 adjoint at the bf16x3 forward's activations and ReLU decisions.
- * (Only the forward runs on the bf16 matrix cores; the dX chain and the weight-gradient GEMMs have no such mode.) */
+ * (Only the forward runs on the bf16 matrix cores; the dX chain and the weight-gradient GEMMs have no such mode.)  Mode 2 is
+ * rejected: plain bf16 is an evaluation arithmetic. */
 int tn_mlp_forward_gather_train_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
                                    const float *barycentric, const float *field_vm, const float *dirs, int mode, float *sigma,
                                    float *rgb, const tn_mlp_backward_buffers *buffers, const float *ray_head_bias, void *stream);

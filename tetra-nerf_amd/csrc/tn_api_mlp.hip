@@ -14,7 +14,7 @@ using tn::guarded;
 struct tn_mlp {
     int device = 0;
     tn::DevBuf<float> pk_plain, pk_gather, pt, enc, grad_scratch, wenc, hterm;
-    tn::DevBuf<uint4> blob;
+    tn::DevBuf<uint4> blob, blob_bf16;
     tn::DevBuf<float> render_scratch;    // per-block hand-over area of tn_render_rays (grown on demand, never shrunk)
     tn::DevBuf<unsigned long long> render_prof;   // TETRANERF_HIP_RENDER_PROFILE=1 (debug): phase ticks of tn_render_rays
     bool packed = false;
@@ -27,7 +27,7 @@ struct tn_mlp {
             enc.alloc(cap * tn::mlp_enc_floats_per_ray());
             hterm.alloc(cap * 128);
         }
-        return tn::MlpPacks{pk_plain.p, pk_gather.p, pt.p, blob.p, wenc.p, hterm.p, enc.p, nullptr, grad_scratch.p};
+        return tn::MlpPacks{pk_plain.p, pk_gather.p, pt.p, blob.p, wenc.p, hterm.p, enc.p, nullptr, grad_scratch.p, blob_bf16.p};
     }
 };
 
@@ -40,8 +40,20 @@ tn_mlp *checked_mlp(tn_mlp_t m) {
     if (!m) throw tn::Error("mlp handle is null");
     return m;
 }
-void check_mode(int mode) {
-    if (mode != 0 && mode != 1) throw tn::Error("mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA)");
+// inference: the evaluation forwards, which also run in plain bf16; everything else (training forward, tn_render_rays) does not
+void check_mode(int mode, bool inference = false) {
+    if (inference) {
+        if (mode < 0 || mode > 2) throw tn::Error("mlp mode must be 0 (fp32 MFMA), 1 (bf16x3 MFMA) or 2 (plain bf16 MFMA)");
+    } else if (mode == 2) {
+        throw tn::Error("mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA) here: mode 2 (plain bf16 MFMA) is an arithmetic of "
+                        "tn_mlp_forward and tn_mlp_forward_gather only");
+    } else if (mode != 0 && mode != 1) {
+        throw tn::Error("mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA)");
+    }
+}
+// the inference forward of a mode (one signature)
+auto forward_of(int mode) {
+    return mode == 2 ? tn::launch_mlp_forward_bf16 : mode ? tn::launch_mlp_forward_x3 : tn::launch_mlp_forward;
 }
 tn::MlpBackwardBuffers training_buffers(const tn_mlp_backward_buffers *b) {
     return tn::MlpBackwardBuffers{{b->x0, b->h1, b->h2, b->h3, b->h4, (unsigned long long *)b->masks},
@@ -64,6 +76,7 @@ int tn_mlp_create(int device, tn_mlp_t *out) {
         m->pk_gather.alloc(tn::mlp_pack_floats());
         m->pt.alloc(tn::mlp_backward_pack_floats());
         m->blob.alloc(tn::mlp_x3_blob_u4());
+        m->blob_bf16.alloc(tn::mlp_bf16_blob_u4());
         m->wenc.alloc(128 * 28);
         *out = m.release();
     });
@@ -91,6 +104,7 @@ int tn_mlp_set_weights(tn_mlp_t mlp, const tn_mlp_weights *w, void *stream_) {
         tn::launch_mlp_pack(mw, m->pk_gather.p, true, stream);
         tn::launch_mlp_pack_t(mw, m->pt.p, stream);
         tn::launch_mlp_pack_x3(mw, m->blob.p, stream);
+        tn::launch_mlp_pack_bf16(m->blob.p, m->blob_bf16.p, stream);
         tn::launch_pack_wenc(mw, m->wenc.p, stream);
         TN_HIP(hipGetLastError());
         m->packed = true;
@@ -101,13 +115,13 @@ int tn_mlp_forward(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const float
                    float *sigma, float *rgb, void *stream_) {
     return guarded([&] {
         tn_mlp *m = checked_mlp(mlp);
-        check_mode(mode);
+        check_mode(mode, true);
         if (n == 0) return;
         if (!feats || !sigma || (rgb && !dirs)) throw tn::Error("null pointer");
         if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
         DeviceGuard g(m->device);
         const size_t rays = n / samples_per_ray;
-        (mode ? tn::launch_mlp_forward_x3 : tn::launch_mlp_forward)(
+        forward_of(mode)(
             n, samples_per_ray, rays, feats, nullptr, nullptr, nullptr, dirs, m->packs(rays), sigma, rgb, (hipStream_t)stream_, nullptr);
         TN_HIP(hipGetLastError());
     });
@@ -118,7 +132,7 @@ int tn_mlp_forward_gather(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, cons
                           float *rgb, const float *ray_head_bias, const uint32_t *count, void *stream_) {
     return guarded([&] {
         tn_mlp *m = checked_mlp(mlp);
-        check_mode(mode);
+        check_mode(mode, true);
         if (n == 0) return;
         if (!vertex_indices || !barycentric || !field_vm || !sigma || (rgb && !dirs)) throw tn::Error("null pointer");
         if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
@@ -126,7 +140,7 @@ int tn_mlp_forward_gather(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, cons
         const size_t rays = n / samples_per_ray;
         tn::MlpPacks pk = m->packs(rays);
         pk.ray_bias = rgb ? ray_head_bias : nullptr;
-        (mode ? tn::launch_mlp_forward_x3 : tn::launch_mlp_forward)(
+        forward_of(mode)(
             n, samples_per_ray, rays, nullptr, vertex_indices, barycentric, field_vm, dirs, pk, sigma, rgb,
             (hipStream_t)stream_, count);
         TN_HIP(hipGetLastError());

@@ -199,6 +199,7 @@ struct MlpPacks {
     const float *ray_bias;     // per CALL (set by the entry point, never stored): [rays][128] added to the head layer's
                                // pre-activation (appearance embedding, tn_mlp_common.h: add_ray_bias), or null
     float *grad_scratch;       // [mlp_param_grad_scratch_floats()] per-block partial sums of the parameter gradients
+    const uint4 *blob_bf16;    // plain-bf16 weights + fp32 biases and head vectors (forward, mode 2; tn_mlp_bf16.hip)
 };
 size_t mlp_pack_floats();              // tn_mlp.hip
 size_t mlp_backward_pack_floats();     // tn_mlp_bwd.hip
@@ -218,6 +219,13 @@ void launch_mlp_forward(size_t n, uint32_t samples_per_ray, size_t num_rays, con
 void launch_mlp_forward_x3(size_t n, uint32_t samples_per_ray, size_t num_rays, const float *feats, const uint32_t *vi,
                            const float *bc, const float *fieldT, const float *dirs, const MlpPacks &w, float *sigma, float *rgb,
                            hipStream_t stream, const uint32_t *count = nullptr);
+// the same in plain bf16, one MFMA per product (tn_mlp_bf16.hip): evaluation only, not at the parity bar of the two above.  Its blob
+// is made from the bf16x3 blob of the same weights (launch_mlp_pack_x3 first, on the same stream)
+size_t mlp_bf16_blob_u4();
+void launch_mlp_pack_bf16(const uint4 *x3blob, uint4 *blob, hipStream_t stream);
+void launch_mlp_forward_bf16(size_t n, uint32_t samples_per_ray, size_t num_rays, const float *feats, const uint32_t *vi,
+                             const float *bc, const float *fieldT, const float *dirs, const MlpPacks &w, float *sigma, float *rgb,
+                             hipStream_t stream, const uint32_t *count = nullptr);
 // Training (tn_mlp.hip: TRAIN variant of the forward kernel, tn_mlp_bwd.hip, tn_mlp_grad.hip).  The training forward SAVES
 // the layer inputs and the ReLU masks; the backward kernel runs the reverse network from the masks alone (no recompute);
 // the parameter-gradient GEMMs contract the saved inputs with the gradients it leaves.  Device memory owned by the caller;

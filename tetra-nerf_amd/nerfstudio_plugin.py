@@ -253,7 +253,13 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
             kw["mlp_mode"] = str(train_mode)
         return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
                                ray_head_bias=hb, **kw)
-    return rd.render(o, d, background=bg, ray_head_bias=hb)
+    kw = {}
+    eval_mode = getattr(model.config, "eval_mlp_mode", None)
+    if eval_mode is not None:
+        # opt-in like train_mlp_mode (an absent field, as in the reference's config: the renderer's own fp32): "bf16" = the fast
+        # evaluation arithmetic below the parity bar (TetraRenderer.render: mlp_mode)
+        kw["mlp_mode"] = str(eval_mode)
+    return rd.render(o, d, background=bg, ray_head_bias=hb, **kw)
 
 
 def install(model_cls=None):

@@ -66,6 +66,62 @@ class TetraMLP(torch.nn.Module):
         return sigma, rgb
 
 
+def bf16_round(x: torch.Tensor) -> torch.Tensor:
+    """x rounded to the nearest bf16 value (ties to even), in x's own dtype."""
+    return x.to(torch.float32).to(torch.bfloat16).to(x.dtype)
+
+
+def mlp_forward_bf16_statement(mlp, feats: torch.Tensor, dirs: torch.Tensor, ray_head_bias: Optional[torch.Tensor] = None,
+                               dtype=torch.float64):
+    """THE definition of the "bf16" arithmetic of the fused MLP kernels (mlp_mode="bf16", C-ABI mode 2; evaluation only).
+    feats [..., 64] fp32, dirs [..., 3] per sample, ray_head_bias [..., 128] per sample or None -> sigma [..., 1], rgb [..., 3].
+
+    In each of the four wide layers -- mlp_base layers 0, 1, 2 and mlp_head layer 0, whose input is [direction encoding 27 |
+    base 128] -- BOTH operands of every product are rounded to bf16, round to nearest even: the weight (once, when the
+    weights are packed) and the layer's input, which is the fp32 activation of the layer before, the fp32 features, or the fp32
+    direction encoding.  A product of two bf16 values is exact in fp32; the products are accumulated in fp32, bias and
+    ray_head_bias are added in fp32, the ReLU is taken in fp32.  The narrow heads (density 128 -> 1 + softplus, rgb 128 -> 3 +
+    sigmoid) read the fp32 activations and run in fp32 with unrounded weights.  Nothing else of the render path changes.
+
+    `dtype` is the precision the SUMS are evaluated in: float64 gives the value every fp32 accumulation order approximates
+    (what the tests compare the kernel with), float32 is one such order.  The roundings to bf16 start from fp32 values in
+    both: an activation is brought to fp32 before it is rounded."""
+    w1, b1, w2, b2, w3, b3, wd, bd, wh, bh, wr, br = (t.detach() for t in mlp_weights(mlp))
+
+    def wide(x, w, b):
+        return bf16_round(x.to(torch.float32)).to(dtype) @ bf16_round(w).to(dtype).t() + b.to(dtype)
+
+    x = feats.to(torch.float32)
+    for w, b in ((w1, b1), (w2, b2), (w3, b3)):
+        x = torch.relu(wide(x, w, b))
+    sigma = torch.nn.functional.softplus(x @ wd.to(dtype).t() + bd.to(dtype))
+    pre = wide(torch.cat([direction_encoding(dirs.to(torch.float32)), x.to(torch.float32)], dim=-1), wh, bh)
+    if ray_head_bias is not None:
+        pre = pre + ray_head_bias.to(dtype)
+    h = torch.relu(pre)
+    rgb = torch.sigmoid(h @ wr.to(dtype).t() + br.to(dtype))
+    return sigma, rgb
+
+
+class Bf16StatementMLP:
+    """mlp_forward_bf16_statement in the place of a TetraMLP of render_reference (evaluated in fp32): the whole render path
+    with the "bf16" arithmetic stated in PyTorch, for the tests and measurements that need a frame and no kernel under test."""
+
+    def __init__(self, mlp):
+        self.mlp = mlp
+
+    def __call__(self, feats, dirs):
+        sigma, rgb = mlp_forward_bf16_statement(self.mlp, feats, dirs, dtype=torch.float32)
+        return sigma, rgb
+
+    def coarse_sigma(self, feats):
+        w = [t.detach() for t in mlp_weights(self.mlp)]
+        x = feats
+        for l in range(3):
+            x = torch.relu(bf16_round(x) @ bf16_round(w[2 * l]).t() + w[2 * l + 1])
+        return torch.nn.functional.softplus(x @ w[6].t() + w[7])[..., 0]
+
+
 def stratified_bins(num_samples: int, t_rand: torch.Tensor) -> torch.Tensor:
     """Train-mode spacing bins of TetrahedraSampler / nerfstudio's UniformSampler (model.py:166-175): every edge of
     linspace(0, 1, S+1) is jittered between the centres of its two neighbouring bins.  t_rand: U[0,1) [R, S+1]."""
@@ -410,13 +466,14 @@ class TetraRenderer:
         # tests pass the reference's einsum definition so that the statement runs next to the reference model's body
         self._interpolate_values = interpolate_values
         # arithmetic of the fused forward kernels, per renderer (not process-wide): "fp32" = exact fp32 MFMA chain (what
-        # the parity tests pin), "bf16x3" = split-operand bf16 MFMA (opt-in).  mlp_mode is render()'s; render_train has a
+        # the parity tests pin), "bf16x3" = split-operand bf16 MFMA (opt-in), "bf16" = one bf16 MFMA per product (opt-in, render()
+        # only, below the parity bar: mlp_forward_bf16_statement).  mlp_mode is render()'s; render_train has a
         # switch of its own, train_mlp_mode (so that a renderer built with mlp_mode="bf16x3" before the training forward had
         # that mode keeps training in fp32): the forward kernels of a training iteration -- the coarse density pass and the
         # fine forward, saving or not -- run in it; the adjoint kernels are fp32 in both
         self.mlp_mode = mlp_mode
         self.train_mlp_mode = train_mlp_mode
-        cpp._mode(train_mlp_mode)      # (an unknown mode fails here, not in the first training call)
+        cpp._mode(train_mlp_mode, inference=False)      # (an unknown mode fails here, not in the first training call)
         self.train_node_samples = 1 << 22      # render_train: samples per autograd node of the fused MLP (see there)
         # RGBRenderer background: grey level (1.0 white = default config, 0.0 black) or an (r, g, b) triple; render() /
         # render_train() take a per-call override (nerfstudio's BACKGROUND_COLOR_OVERRIDE, model.py:504-518)
@@ -513,11 +570,15 @@ class TetraRenderer:
                 and self.S + self.S_fine + 2 <= 8192)
 
     @torch.no_grad()
-    def render(self, origins: torch.Tensor, directions: torch.Tensor, background=None, ray_head_bias=None) -> Dict[str, torch.Tensor]:
+    def render(self, origins: torch.Tensor, directions: torch.Tensor, background=None, ray_head_bias=None,
+               mlp_mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """Evaluation-mode render (model.py:520-662 with `self.training == False`: samplers without jitter, RGB renderer
         with nan_to_num + clamp).  background: per-call override of the renderer's colour (grey level or (r, g, b)).
         ray_head_bias f32 [R, 128] (fused path only): per-ray vector added to mlp_head's pre-activation -- the appearance
         embedding's share of the head layer, Wh[:, 155:] emb (model.py:608-620), made by the caller.
+        mlp_mode (fused path; None: the renderer's mlp_mode): arithmetic of the MLP kernels of this call.  "bf16" -- both operands
+        of every product of the four wide layers rounded to bf16, fp32 accumulation (mlp_forward_bf16_statement) -- is the fast
+        one and the only one that does NOT hold the 1e-5 parity bar; it renders through the kernel chain.
         NO HOST SYNCHRONISATION (round 5): the reference compacts the hitting rays with boolean indexing (model.py:540-567),
         rounds 2-4 with torch.nonzero -- a device -> host round trip per chunk during which the GPU idles.  Here the hitting
         rays are compacted on the device (tn_compact_hits: their number stays there) and every kernel after the trace takes the
@@ -529,8 +590,10 @@ class TetraRenderer:
                 raise RuntimeError("ray_head_bias is an input of the fused kernels; the PyTorch statement takes the model's own modules")
             return render_reference(self.tracer, cpp.interpolate_values, self.field, self.mlp, origins, directions,
                                     S, self.M, self.far_plane, self.S_fine, self.biased, background=bg)
+        mode = self.mlp_mode if mlp_mode is None else mlp_mode
+        cpp._mode(mode)
         if not self.device_samplers:
-            return self._render_host_compaction(origins, directions, bg, ray_head_bias)
+            return self._render_host_compaction(origins, directions, bg, ray_head_bias, mode)
         out = self._trace(origins, directions)
         nv = out["num_visited_cells"]
         ray_mask = nv > 0
@@ -544,7 +607,6 @@ class TetraRenderer:
         lists = trace_rows(out)
         order, count = cpp.compact_hits(nv)          # hitting rays first, in ray order; their number stays on the device
         w = mlp_weights(self.mlp)
-        mode = self.mlp_mode
         d = directions.contiguous()
         if self._one_launch_ok(mode):
             cpp.render_rays(lists, order, count, self.field, d, w, S, self.S_fine, self.biased, out=(rgb, acc, depth), background=bg,
@@ -563,7 +625,7 @@ class TetraRenderer:
         return res
 
     @torch.no_grad()
-    def _render_host_compaction(self, origins, directions, bg, ray_head_bias=None):
+    def _render_host_compaction(self, origins, directions, bg, ray_head_bias=None, mode=None):
         """render() with the PyTorch SAMPLER statements (device_samplers=False: the parity definition of tn_sample_coarse /
         tn_sample_pdf, ~15 small operators per pass) between the HIP kernels.  Sizes its work on the host (torch.nonzero), as
         the reference does; not the production path."""
@@ -572,7 +634,7 @@ class TetraRenderer:
         ray_mask = out["num_visited_cells"] > 0
         rgb, acc, depth = self._miss_frame(origins.shape[0], bg, origins.device)
         idx = torch.nonzero(ray_mask)[:, 0]
-        mode = self.mlp_mode
+        mode = self.mlp_mode if mode is None else mode
         if idx.numel():
             lists = trace_rows(out)
             ridx = idx.to(torch.int32)
@@ -622,7 +684,7 @@ class TetraRenderer:
         the exact fp32 gradient at that forward's activations and ReLU decisions."""
         cpp, S = self.cpp, self.S
         mode = self.train_mlp_mode if mlp_mode is None else mlp_mode
-        cpp._mode(mode)
+        cpp._mode(mode, inference=False)
         R, dev = origins.shape[0], origins.device
         rand = rand or {}
         # SYNC-FREE form (default for the fused path): the reference compacts the hitting rays with boolean indexing

@@ -611,12 +611,17 @@ class _MlpWeightsStruct(C.Structure):
 
 
 _WEIGHT_SHAPES = [(128, 64), (128,), (128, 128), (128,), (128, 128), (128,), (1, 128), (1,), (128, 155), (128,), (3, 128), (3,)]
-_MODES = {"fp32": 0, "bf16x3": 1, 0: 0, 1: 1}
+_MODES = {"fp32": 0, "bf16x3": 1, "bf16": 2, 0: 0, 1: 1, 2: 2}
 
 
-def _mode(mode):
+def _mode(mode, inference=True):
+    """C-ABI value of an arithmetic of the fused MLP kernels.  "bf16" (plain bf16 products, fp32 accumulation: render.py,
+    mlp_forward_bf16_statement) is an arithmetic of the evaluation forwards only: inference=False -- the training forward and
+    the one-launch render -- refuses it."""
     m = _MODES.get(mode)
-    _check(m is not None, 'mlp mode must be "fp32" or "bf16x3"')
+    _check(m is not None, 'mlp mode must be "fp32", "bf16x3" or (evaluation forwards only) "bf16"')
+    _check(inference or m != 2, 'mlp mode must be "fp32" or "bf16x3" here: "bf16" is an arithmetic of the evaluation forwards '
+                                '(mlp_forward, mlp_forward_gather, TetraRenderer.render) only')
     return m
 
 
@@ -725,8 +730,9 @@ def mlp_forward(feats_fm, dirs, weights, samples_per_ray, mode="fp32"):
     reference surface; the reference runs these through nerfstudio/PyTorch, model.py:602-621).
     feats_fm f32 [64, n] feature-major (interpolate_values(...).moveaxis(-1, 0) is that buffer),
     dirs f32 [n // samples_per_ray, 3], weights: 12 contiguous fp32 CUDA tensors in nn.Linear layout
-    (w1,b1,w2,b2,w3,b3,wd,bd,wh,bh,wr,br).  mode: "fp32" (exact fp32 MFMA chain) or "bf16x3" (bf16 MFMA on 3-way
-    split operands; opt-in).  Returns sigma [n], rgb [n,3]."""
+    (w1,b1,w2,b2,w3,b3,wd,bd,wh,bh,wr,br).  mode: "fp32" (exact fp32 MFMA chain), "bf16x3" (bf16 MFMA on 3-way
+    split operands; opt-in) or "bf16" (one bf16 MFMA per product, fp32 accumulation; opt-in, NOT at the 1e-5 parity bar of the
+    other two: render.mlp_forward_bf16_statement states it).  Returns sigma [n], rgb [n,3]."""
     _check_input(feats_fm, "feats")
     _check_input(dirs, "dirs")
     _check(feats_fm.dtype == torch.float32 and feats_fm.dim() == 2 and feats_fm.size(0) == 64, "feats must be f32 [64, n]")
@@ -820,6 +826,7 @@ def render_rays(trace_lists, order, count, field, directions, weights, num_sampl
     + MLP -> weights -> PDF sampler -> match -> gather + MLP + heads -> composite, for the hitting rays order[:count] (compact_hits)
     whose number stays on the device.  trace_lists as returned by trace_rays; directions f32 [R,3] and ray_head_bias f32 [R,128]
     over ALL rays; out = (rgb [R,3], accumulation [R,1] or [R], depth) pre-filled with the background values."""
+    mode = _mode(mode, inference=False)     # (the persistent kernel has no "bf16" phases: TetraRenderer.render takes the chain)
     nv, _cells, bary, dist, verts = trace_lists
     for x, name in ((nv, "num_visited_cells"), (bary, "barycentric_coordinates"), (dist, "hit_distances"), (verts, "vertex_indices"),
                     (order, "order"), (field, "field"), (directions, "directions")):
@@ -843,7 +850,7 @@ def render_rays(trace_lists, order, count, field, directions, weights, num_sampl
         _lib.check(_lib.load().tn_render_rays_ex(
             m.handle, M, _ptr(nv), _ptr(dist), _ptr(bary), _ptr(verts), _ptr(order), _ptr(count), order.numel(), S, Sf, 1 if biased else 0,
             _ptr(_linspace_table(S, dev)), _ptr(_quantile_table(Sf + 1, True, dev)) if Sf else None, float(histogram_padding), float(eps),
-            _ptr(field_vm), _ptr(directions), _background(background, clamp), _ptr(rgb), _ptr(acc), _ptr(depth), _ptr(hb), _mode(mode), _stream(dev)))
+            _ptr(field_vm), _ptr(directions), _background(background, clamp), _ptr(rgb), _ptr(acc), _ptr(depth), _ptr(hb), mode, _stream(dev)))
 
 
 _TABLES = {}    # (kind, n, device) -> small constant tables of the samplers (the values the PyTorch statements use)
@@ -983,7 +990,7 @@ def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dir
     mlp_backward, which then recomputes nothing.  mode: "fp32" (default) or "bf16x3" (tn_mlp_forward_gather_train_ex): sigma /
     rgb are then mlp_forward_gather(mode="bf16x3")'s bits and `saved` holds that forward's activations and ReLU masks in the
     same layouts; mlp_backward is the same fp32 adjoint in both modes."""
-    mode = _mode(mode)
+    mode = _mode(mode, inference=False)
     _check_input(dirs, "dirs")   # (no density-only form: the training forward is the full network)
     n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
     m = fused_mlp(weights)
