@@ -522,13 +522,27 @@ int tn_mlp_forward_gather_train(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray
  * tn_mlp_forward_gather_train, 1 bf16x3 MFMA).  Mode 1: sigma / rgb are bit for bit those of tn_mlp_forward_gather(mode 1), and
  * x0, h1..h4 and masks are saved in the same layouts, so tn_mlp_backward / tn_mlp_ray_head_grad / tn_mlp_param_grads run
  * unchanged (fp32) on them: the gradient is the exact fp32 adjoint at the bf16x3 forward's activations and ReLU decisions.
- * (Only the forward runs on the bf16 matrix cores; the dX chain and the weight-gradient GEMMs have no such mode.)  Mode 2 is
- * rejected: plain bf16 is an evaluation arithmetic. */
+ * (The dX chain has an arithmetic of its own, chosen independently: tn_mlp_backward_ex below.  The weight-gradient GEMMs are
+ * fp32 only.)  Mode 2 is rejected: plain bf16 is an evaluation arithmetic. */
 int tn_mlp_forward_gather_train_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
                                    const float *barycentric, const float *field_vm, const float *dirs, int mode, float *sigma,
                                    float *rgb, const tn_mlp_backward_buffers *buffers, const float *ray_head_bias, void *stream);
 int tn_mlp_backward(tn_mlp_t mlp, size_t n, const float *sigma, const float *rgb, const float *d_sigma, const float *d_rgb,
                     const tn_mlp_backward_buffers *buffers, void *stream);
+/* The same with the arithmetic of the dX chain chosen per call, independently of the forward's: mode 0 (fp32 MFMA) IS
+ * tn_mlp_backward -- the same launcher, the same bits; mode 1 (bf16x3 MFMA) evaluates the four matrix products of the chain
+ * (Wh[:, 27:]^T d4, W3^T d3, W2^T d2, W1^T d1) on the bf16 matrix cores with three bf16 pieces per operand, six products per
+ * multiply and fp32 accumulation, as the forward's mode 1 does.  Everything else stays fp32, operation for operation as in
+ * mode 0: softplus' / sigmoid' from the forward's outputs, d4 = ReLU'(h4) Wr^T d rgb_raw, the density term wd d sigma_raw, the
+ * ReLU masks and the transposition of dx0 -- so dhead and d4 are bit for bit those of mode 0, and d3, d2, d1, dx0 each follow
+ * from the stored gradient before them within 2^-21 of the sum of the products' magnitudes.  Buffers and layouts are those of
+ * tn_mlp_backward: tn_mlp_ray_head_grad, tn_mlp_param_grads (fp32 in either mode) and the gather adjoint run on them
+ * unchanged.  Any other mode fails with a message (tn_last_error); mode 2, plain bf16, is an evaluation arithmetic.
+ * Measured on an MI355X (profiles/train_x3_adjoint_bench.txt): 2.34 -> 1.62 ms at 4096 x 513 samples (1.45x), 1.21 -> 0.81 ms at
+ * 4096 x 257 (1.49x); a training iteration -6.4 % / -6.3 % (tetra-nerf-original / tetra-nerf).  k_mlp_backward_x3: 256 VGPRs,
+ * 172 bytes of scratch per lane, 2 waves per SIMD, 146 KB of LDS (one 8-wave block per CU). */
+int tn_mlp_backward_ex(tn_mlp_t mlp, size_t n, const float *sigma, const float *rgb, const float *d_sigma, const float *d_rgb,
+                       const tn_mlp_backward_buffers *buffers, int mode, void *stream);
 /* gradient of the per-ray head bias after tn_mlp_backward: d_ray_head_bias f32 [n / samples_per_ray, 128] = the sum over
  * each ray's samples of d4 (bit-reproducible) */
 int tn_mlp_ray_head_grad(size_t n, uint32_t samples_per_ray, const tn_mlp_backward_buffers *buffers, float *d_ray_head_bias,

@@ -14,7 +14,7 @@ using tn::guarded;
 struct tn_mlp {
     int device = 0;
     tn::DevBuf<float> pk_plain, pk_gather, pt, enc, grad_scratch, wenc, hterm;
-    tn::DevBuf<uint4> blob, blob_bf16;
+    tn::DevBuf<uint4> blob, blob_bf16, blob_t;
     tn::DevBuf<float> render_scratch;    // per-block hand-over area of tn_render_rays (grown on demand, never shrunk)
     tn::DevBuf<unsigned long long> render_prof;   // TETRANERF_HIP_RENDER_PROFILE=1 (debug): phase ticks of tn_render_rays
     bool packed = false;
@@ -27,7 +27,7 @@ struct tn_mlp {
             enc.alloc(cap * tn::mlp_enc_floats_per_ray());
             hterm.alloc(cap * 128);
         }
-        return tn::MlpPacks{pk_plain.p, pk_gather.p, pt.p, blob.p, wenc.p, hterm.p, enc.p, nullptr, grad_scratch.p, blob_bf16.p};
+        return tn::MlpPacks{pk_plain.p, pk_gather.p, pt.p, blob.p, wenc.p, hterm.p, enc.p, nullptr, grad_scratch.p, blob_bf16.p, blob_t.p};
     }
 };
 
@@ -77,6 +77,7 @@ int tn_mlp_create(int device, tn_mlp_t *out) {
         m->pt.alloc(tn::mlp_backward_pack_floats());
         m->blob.alloc(tn::mlp_x3_blob_u4());
         m->blob_bf16.alloc(tn::mlp_bf16_blob_u4());
+        m->blob_t.alloc(tn::mlp_x3_t_blob_u4());
         m->wenc.alloc(128 * 28);
         *out = m.release();
     });
@@ -105,6 +106,7 @@ int tn_mlp_set_weights(tn_mlp_t mlp, const tn_mlp_weights *w, void *stream_) {
         tn::launch_mlp_pack_t(mw, m->pt.p, stream);
         tn::launch_mlp_pack_x3(mw, m->blob.p, stream);
         tn::launch_mlp_pack_bf16(m->blob.p, m->blob_bf16.p, stream);
+        tn::launch_mlp_pack_x3_t(mw, m->blob_t.p, stream);
         tn::launch_pack_wenc(mw, m->wenc.p, stream);
         TN_HIP(hipGetLastError());
         m->packed = true;
@@ -248,6 +250,21 @@ int tn_mlp_backward(tn_mlp_t mlp, size_t n, const float *sigma, const float *rgb
         if (!b->masks || !b->d1 || !b->d2 || !b->d3 || !b->d4 || !b->dhead || !b->dx0) throw tn::Error("null pointer");
         DeviceGuard g(m->device);
         tn::launch_mlp_backward(n, sigma, rgb, m->packs(0), d_sigma, d_rgb, training_buffers(b), (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_mlp_backward_ex(tn_mlp_t mlp, size_t n, const float *sigma, const float *rgb, const float *d_sigma, const float *d_rgb,
+                       const tn_mlp_backward_buffers *b, int mode, void *stream_) {
+    if (mode == 0) return tn_mlp_backward(mlp, n, sigma, rgb, d_sigma, d_rgb, b, stream_);
+    return guarded([&] {
+        tn_mlp *m = checked_mlp(mlp);
+        check_mode(mode);
+        if (n == 0) return;
+        if (!b || !sigma || !rgb || !d_sigma || !d_rgb) throw tn::Error("null pointer");
+        if (!b->masks || !b->d1 || !b->d2 || !b->d3 || !b->d4 || !b->dhead || !b->dx0) throw tn::Error("null pointer");
+        DeviceGuard g(m->device);
+        tn::launch_mlp_backward_x3(n, sigma, rgb, m->packs(0), d_sigma, d_rgb, training_buffers(b), (hipStream_t)stream_);
         TN_HIP(hipGetLastError());
     });
 }

@@ -200,15 +200,18 @@ struct MlpPacks {
                                // pre-activation (appearance embedding, tn_mlp_common.h: add_ray_bias), or null
     float *grad_scratch;       // [mlp_param_grad_scratch_floats()] per-block partial sums of the parameter gradients
     const uint4 *blob_bf16;    // plain-bf16 weights + fp32 biases and head vectors (forward, mode 2; tn_mlp_bf16.hip)
+    const uint4 *blob_t;       // bf16x3 pieces of the transposed weights (backward, mode 1; tn_mlp_x3_bwd.hip)
 };
 size_t mlp_pack_floats();              // tn_mlp.hip
 size_t mlp_backward_pack_floats();     // tn_mlp_bwd.hip
 size_t mlp_x3_blob_u4();               // tn_mlp_x3.hip
+size_t mlp_x3_t_blob_u4();             // tn_mlp_x3_bwd.hip
 size_t mlp_enc_floats_per_ray();       // 32: covers the fp32 kernels' 28 and the bf16x3 kernel's 32
 void launch_mlp_pack(const MlpWeights &w, float *pk, bool gather_l1, hipStream_t stream);
 void launch_pack_wenc(const MlpWeights &w, float *wenc, hipStream_t stream);   // [128 * 28] floats
 void launch_mlp_pack_t(const MlpWeights &w, float *pt, hipStream_t stream);
 void launch_mlp_pack_x3(const MlpWeights &w, uint4 *blob, hipStream_t stream);
+void launch_mlp_pack_x3_t(const MlpWeights &w, uint4 *blob_t, hipStream_t stream);
 // feats != null: input is the [64, n] feature buffer; feats == null: the kernel gathers the features itself from
 // (vi [n,4], bc [n,3], fieldT [V, 64] VERTEX-major)
 // count (nullable): device-side number of RAYS (n, num_rays are then upper bounds the grid is sized for)
@@ -253,6 +256,10 @@ void launch_mlp_forward_x3_train(size_t n, uint32_t samples_per_ray, size_t num_
 // sigmoid' = rgb (1 - rgb)); d_sigma [n], d_rgb [n, 3]; fills d1..d4, dhead, dx0
 void launch_mlp_backward(size_t n, const float *sigma, const float *rgb, const MlpPacks &w, const float *d_sigma, const float *d_rgb,
                          const MlpBackwardBuffers &b, hipStream_t stream);
+// the same with its four matrix products in bf16x3 (tn_mlp_x3_bwd.hip); everything on the VALU is launch_mlp_backward's fp32
+// statement, so dhead and d4 are its bits; same buffers, same layouts
+void launch_mlp_backward_x3(size_t n, const float *sigma, const float *rgb, const MlpPacks &w, const float *d_sigma, const float *d_rgb,
+                            const MlpBackwardBuffers &b, hipStream_t stream);
 // gradient of the per-ray head bias: out [rays, 128] = sum over the ray's samples of d4 (the gradient w.r.t. the head
 // layer's pre-activation, left by launch_mlp_backward)
 void launch_ray_head_grad(size_t n, uint32_t samples_per_ray, const float *d4, float *out, hipStream_t stream);

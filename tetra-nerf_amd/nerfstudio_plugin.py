@@ -37,6 +37,10 @@ REFERENCE `get_outputs` unchanged (i.e. the HIP tracer / matcher / gather under 
 the reference, just without the fused speed-up.  `fused_config_supported` states the rule; both method configs the
 reference registers (`tetra-nerf-original`, `tetra-nerf`) are supported.
 
+Opt-ins (fields the reference's config does not have; absent = off, read with getattr): `position_gradients` (gradients for
+origins / directions / vertices), `train_mlp_mode` ("bf16x3": the forward kernels of a training iteration), `train_adjoint_mode`
+("bf16x3": the dX chain of the MLP adjoint, independent of the forward's mode), `eval_mlp_mode` ("bf16x3" / "bf16").
+
 nerfstudio is not installed in this environment: the adapter is duck-typed (it only touches the attribute names listed
 above) and is tested with stand-ins of nerfstudio's MLP / FieldHead / RayBundle (tests/golden/nerfstudio_standins.py).
 """
@@ -251,6 +255,11 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
             # opt-in as well (an absent field: fp32): "bf16x3" = the forward kernels of a training iteration in the split-operand
             # bf16 arithmetic, fp32 adjoints (TetraRenderer.render_train: mlp_mode)
             kw["mlp_mode"] = str(train_mode)
+        adjoint_mode = getattr(model.config, "train_adjoint_mode", None)
+        if adjoint_mode is not None:
+            # opt-in, independent of train_mlp_mode (an absent field: fp32): "bf16x3" = the matrix products of the dX chain in the
+            # split-operand bf16 arithmetic (TetraRenderer.render_train: adjoint_mode)
+            kw["adjoint_mode"] = str(adjoint_mode)
         return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
                                ray_head_bias=hb, **kw)
     kw = {}

@@ -355,7 +355,8 @@ class GradientScaler(torch.autograd.Function):
 class _FusedMlpFunction(torch.autograd.Function):
     """gather + MLP + heads as ONE autograd node: forward = tn_mlp_forward_gather_train_ex (`mode`: "fp32" or "bf16x3"; saves the
     layer inputs and the ReLU masks, 2.3 KB per sample), backward = tn_mlp_backward + tn_mlp_param_grads + tn_interpolate_values_backward (dX
-    chain and weight gradients on the fp32 matrix cores, nothing recomputed).  Gradients flow to the field and the 12
+    chain and weight gradients on the fp32 matrix cores, nothing recomputed; with the adjoint mode "bf16x3" the dX chain is
+    tn_mlp_backward_ex(mode 1), its four matrix products on the bf16 matrix cores).  Gradients flow to the field and the 12
     weight tensors, and -- when they require it -- to the barycentrics (tn_interpolate_values_backward_bary_vm on the same
     d x0 rows; the vertex indices are constants) and to the view directions (through the head layer's per-ray term)."""
 
@@ -363,9 +364,10 @@ class _FusedMlpFunction(torch.autograd.Function):
     def forward(ctx, vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray, ray_head_bias, *weights):
         from . import tetranerf_cpp_extension as cpp
 
-        # weights: the 12 tensors, optionally followed by the forward's mode ("fp32" when absent)
-        ctx.has_mode = len(weights) == 13
-        mode = weights[12] if ctx.has_mode else "fp32"
+        # weights: the 12 tensors, optionally followed by the forward's mode and then the adjoint's ("fp32" when absent)
+        ctx.num_modes = len(weights) - 12
+        mode = weights[12] if ctx.num_modes >= 1 else "fp32"
+        ctx.adjoint_mode = weights[13] if ctx.num_modes >= 2 else "fp32"
         weights = weights[:12]
         ctx.has_bias = ray_head_bias is not None
         sigma, rgb, saved = cpp.mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dirs, list(weights),
@@ -386,7 +388,8 @@ class _FusedMlpFunction(torch.autograd.Function):
         saved = ctx.saved          # (kept: a second backward through a retained graph reads the same activations)
         need_bary, need_dirs = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
         res = cpp.mlp_backward(saved, vi, bc, field, dirs, list(weights), sigma, rgb, d_sigma.contiguous(), d_rgb.contiguous(),
-                               want_ray_head_grad=ctx.has_bias or need_dirs, want_bary_grad=need_bary)
+                               want_ray_head_grad=ctx.has_bias or need_dirs, want_bary_grad=need_bary,
+                               adjoint_mode=ctx.adjoint_mode)
         grad_field, grads = res[0], res[1]
         # the per-ray head bias (appearance embedding): its gradient = per-ray sums of the head pre-activation's gradient
         d_head = res[2] if (ctx.has_bias or need_dirs) else None
@@ -399,7 +402,7 @@ class _FusedMlpFunction(torch.autograd.Function):
             with torch.enable_grad():
                 d_leaf = dirs.detach().requires_grad_(True)
                 (grad_dirs,) = torch.autograd.grad(direction_encoding(d_leaf), d_leaf, g_enc)
-        return (None, grad_bary, grad_field, grad_dirs, None, d_head if ctx.has_bias else None, *grads, *((None,) if ctx.has_mode else ()))
+        return (None, grad_bary, grad_field, grad_dirs, None, d_head if ctx.has_bias else None, *grads, *((None,) * ctx.num_modes))
 
 
 class _FusedCompositeFunction(torch.autograd.Function):
@@ -444,7 +447,7 @@ class TetraRenderer:
                  num_fine_samples: int = 0, biased: bool = False, dense_tails: bool = False, fused_pass="auto",
                  mlp_mode: str = "fp32", background=1.0, cache_field: bool = True, device_samplers: bool = True,
                  interpolate_values=None, sync_free_train: bool = True, sync_free_min_hits: float = None,
-                 bin_rays: bool = False, train_mlp_mode: str = "fp32"):
+                 bin_rays: bool = False, train_mlp_mode: str = "fp32", train_adjoint_mode: str = "fp32"):
         from . import tetranerf_cpp_extension as cpp
 
         # incoherent batches (random pixels over many cameras): the tracer walks the rays in a locality order of its own
@@ -470,10 +473,14 @@ class TetraRenderer:
         # only, below the parity bar: mlp_forward_bf16_statement).  mlp_mode is render()'s; render_train has a
         # switch of its own, train_mlp_mode (so that a renderer built with mlp_mode="bf16x3" before the training forward had
         # that mode keeps training in fp32): the forward kernels of a training iteration -- the coarse density pass and the
-        # fine forward, saving or not -- run in it; the adjoint kernels are fp32 in both
+        # fine forward, saving or not -- run in it.  The adjoint has an arithmetic of its own, train_adjoint_mode, independent of
+        # the forward's (all four combinations are valid): "bf16x3" runs the dX chain's four matrix products on the bf16 matrix
+        # cores (tn_mlp_backward_ex); the weight-gradient GEMMs and the gather adjoint are fp32 in both
         self.mlp_mode = mlp_mode
         self.train_mlp_mode = train_mlp_mode
+        self.train_adjoint_mode = train_adjoint_mode
         cpp._mode(train_mlp_mode, inference=False)      # (an unknown mode fails here, not in the first training call)
+        cpp._mode(train_adjoint_mode, inference=False)
         self.train_node_samples = 1 << 22      # render_train: samples per autograd node of the fused MLP (see there)
         # RGBRenderer background: grey level (1.0 white = default config, 0.0 black) or an (r, g, b) triple; render() /
         # render_train() take a per-call override (nerfstudio's BACKGROUND_COLOR_OVERRIDE, model.py:504-518)
@@ -659,7 +666,8 @@ class TetraRenderer:
                      generator: Optional[torch.Generator] = None, rand: Optional[Dict[str, torch.Tensor]] = None,
                      fused: bool = True, capture: Optional[dict] = None, background=None,
                      ray_head_bias: Optional[torch.Tensor] = None, position_gradients: bool = False,
-                     vertices: Optional[torch.Tensor] = None, mlp_mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
+                     vertices: Optional[torch.Tensor] = None, mlp_mode: Optional[str] = None,
+                     adjoint_mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
         (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches
         them), gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) --
@@ -680,11 +688,16 @@ class TetraRenderer:
         tracer's hit distances.  After the vertices moved, the tracer must be reloaded (load_tetrahedra).
         mlp_mode (fused path; None: the renderer's train_mlp_mode, "fp32" unless chosen otherwise): "bf16x3" runs the forward
         kernels of this call -- the coarse density pass, the recorded fine node and the no-graph fine forward -- in the
-        split-operand bf16 arithmetic (same 1e-5 bar against fp32 as in render()); the adjoints stay fp32 kernels and give
-        the exact fp32 gradient at that forward's activations and ReLU decisions."""
+        split-operand bf16 arithmetic (same 1e-5 bar against fp32 as in render()); the adjoints take that forward's
+        activations and ReLU decisions.
+        adjoint_mode (fused path; None: the renderer's train_adjoint_mode, "fp32" unless chosen otherwise; independent of
+        mlp_mode): "bf16x3" runs the four matrix products of the recorded node's dX chain in the split-operand bf16 arithmetic
+        (tn_mlp_backward_ex); the outputs of the call do not depend on it, the weight-gradient GEMMs stay fp32."""
         cpp, S = self.cpp, self.S
         mode = self.train_mlp_mode if mlp_mode is None else mlp_mode
         cpp._mode(mode, inference=False)
+        amode = self.train_adjoint_mode if adjoint_mode is None else adjoint_mode
+        modes = (mode,) if cpp._mode(amode, inference=False) == 0 else (mode, amode)      # (the default node is built as it always was)
         R, dev = origins.shape[0], origins.device
         rand = rand or {}
         # SYNC-FREE form (default for the fused path): the reference compacts the hitting rays with boolean indexing
@@ -799,10 +812,10 @@ class TetraRenderer:
             # beyond 2^22 samples (nerfstudio trains on 4096 rays) go through several nodes, one per block of rays
             rays_per_node = max(1, int(self.train_node_samples) // S)
             if r <= rays_per_node:
-                sigma, col = _FusedMlpFunction.apply(vi, bc, self.field, dirs, S, hb, *w, mode)
+                sigma, col = _FusedMlpFunction.apply(vi, bc, self.field, dirs, S, hb, *w, *modes)
             else:
                 parts = [_FusedMlpFunction.apply(vi[a:a + rays_per_node], bc[a:a + rays_per_node], self.field,
-                                                 dirs[a:a + rays_per_node], S, None if hb is None else hb[a:a + rays_per_node], *w, mode)
+                                                 dirs[a:a + rays_per_node], S, None if hb is None else hb[a:a + rays_per_node], *w, *modes)
                          for a in range(0, r, rays_per_node)]
                 sigma, col = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
             sigma, col = sigma.view(-1, S), col.view(-1, S, 3)
@@ -851,7 +864,7 @@ class TetraNerfModule(torch.nn.Module):
 
     def __init__(self, tracer, num_vertices: int, num_samples: int = 256, max_ray_triangles: int = 512,
                  num_fine_samples: int = 256, biased: bool = False, gradient_scaling: bool = False,
-                 train_mlp_mode: str = "fp32", **renderer_kw):
+                 train_mlp_mode: str = "fp32", train_adjoint_mode: str = "fp32", **renderer_kw):
         super().__init__()
         field = (torch.rand(FIELD_DIM, num_vertices) * 2 - 1) * 1e-4      # model.py:269-271
         field[1:4] = torch.rand(3, num_vertices) * 2 - 1                  # colours, model.py:379-386
@@ -861,7 +874,7 @@ class TetraNerfModule(torch.nn.Module):
         self._tracer = tracer
         self._renderer_args = (int(num_samples), int(max_ray_triangles))
         self._renderer_kw = dict(num_fine_samples=int(num_fine_samples), biased=bool(biased), train_mlp_mode=train_mlp_mode,
-                                 **renderer_kw)
+                                 train_adjoint_mode=train_adjoint_mode, **renderer_kw)
         self._renderer = None
 
     def renderer(self) -> "TetraRenderer":

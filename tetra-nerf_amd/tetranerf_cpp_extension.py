@@ -989,7 +989,7 @@ def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dir
     """mlp_forward_gather for training: returns (sigma [n], rgb [n,3], saved) -- `saved` holds 2.3 KB per sample for
     mlp_backward, which then recomputes nothing.  mode: "fp32" (default) or "bf16x3" (tn_mlp_forward_gather_train_ex): sigma /
     rgb are then mlp_forward_gather(mode="bf16x3")'s bits and `saved` holds that forward's activations and ReLU masks in the
-    same layouts; mlp_backward is the same fp32 adjoint in both modes."""
+    same layouts; mlp_backward runs on them in either arithmetic of its own (adjoint_mode), chosen independently."""
     mode = _mode(mode, inference=False)
     _check_input(dirs, "dirs")   # (no density-only form: the training forward is the full network)
     n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
@@ -1015,8 +1015,15 @@ def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dir
     return sv.sigma, sv.rgb, sv
 
 
+class MlpChain:
+    """What the dX chain of one mlp_backward call produced (return_chain=True; for tests that follow the chain layer by layer):
+    d1..d4 [128, n] slices of quad-major memory ([F/4][n][4], like MlpSaved.acts), dhead [4, n] (d sigma_raw, d rgb_raw) and
+    dx0 [n, 64]."""
+    __slots__ = ("d1", "d2", "d3", "d4", "dhead", "dx0")
+
+
 def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, weights, sigma, rgb, d_sigma, d_rgb,
-                 want_ray_head_grad=False, want_bary_grad=False, return_dx0=False):
+                 want_ray_head_grad=False, want_bary_grad=False, return_dx0=False, adjoint_mode="fp32", return_chain=False):
     """Adjoint of mlp_forward_gather_train (addition; the reference leaves this to PyTorch autograd, model.py:602-630):
     given the forward's outputs sigma [n] / rgb [n,3], dL/dsigma [n] and dL/drgb [n,3] returns (grad_field [64,V], [12 weight
     gradients in the order of `weights`]).
@@ -1025,7 +1032,13 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
     summed without atomics (bit-reproducible) -- then the gather's adjoint.  2.1 KB of gradient buffers per sample.
     Appended to the result, in this order: want_ray_head_grad: the per-ray sums of the head pre-activation's gradient [rays, 128];
     want_bary_grad: dL/d barycentric_coordinates [n, 3], the gather's adjoint w.r.t. the barycentrics on the same d x0 rows
-    (tn_interpolate_values_backward_bary_vm; tet membership is a constant of it); return_dx0: those rows, d x0 [n, 64]."""
+    (tn_interpolate_values_backward_bary_vm; tet membership is a constant of it); return_dx0: those rows, d x0 [n, 64];
+    return_chain: an MlpChain with views of everything the dX chain wrote.
+    adjoint_mode: arithmetic of the dX chain, independent of the forward's.  "fp32" (default): tn_mlp_backward.  "bf16x3"
+    (tn_mlp_backward_ex, mode 1): its four matrix products on the bf16 matrix cores, three bf16 pieces per operand; softplus' /
+    sigmoid', the head layer's gradient d4, the density term and the masks stay fp32 (dhead and d4 are the default's bits), and
+    so do the parameter gradients and the gather adjoint, which read the same buffers.  "bf16" is not an adjoint arithmetic."""
+    amode = _mode(adjoint_mode, inference=False)
     mh = fused_mlp(weights)
     keep = [w.detach() for w in weights]
     n, S = saved.n, saved.S
@@ -1056,8 +1069,11 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
                              buf[256:384].data_ptr(), buf[384:512].data_ptr(), buf[512:516].data_ptr(), rows.data_ptr())
     stream = _stream(dev)
     with _on(dev):
-        _lib.check(lib.tn_mlp_backward(mh.handle, n, _ptr(sigma.contiguous()), _ptr(rgb.contiguous()), _ptr(d_sigma), _ptr(d_rgb),
-                                       C.byref(bs), stream))
+        head = (mh.handle, n, _ptr(sigma.contiguous()), _ptr(rgb.contiguous()), _ptr(d_sigma), _ptr(d_rgb), C.byref(bs))
+        if amode == 0:      # the default goes through the entry it always went through
+            _lib.check(lib.tn_mlp_backward(*head, stream))
+        else:
+            _lib.check(lib.tn_mlp_backward_ex(*head, amode, stream))
         _lib.check(lib.tn_mlp_param_grads(mh.handle, n, S, _ptr(dirs), C.byref(bs), C.byref(gs), stream))
         d_ray_bias = None
         if want_ray_head_grad:      # gradient of the per-ray head bias: per-ray sums of d4
@@ -1075,6 +1091,10 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
         res += (grad_bary,)
     if return_dx0:
         res += (rows,)
+    if return_chain:
+        ch = MlpChain()
+        ch.d1, ch.d2, ch.d3, ch.d4, ch.dhead, ch.dx0 = buf[0:128], buf[128:256], buf[256:384], buf[384:512], buf[512:516], rows
+        res += (ch,)
     return res
 
 
