@@ -121,7 +121,8 @@ def test_composite_matches_torch(tn, device, render):
     import torch
 
     torch.manual_seed(2)
-    for R, S in ((16, 256), (7, 65), (3, 2), (100, 128)):
+    # (1 sample; 321 and 577: the first size of the 9-chunk form and of its second group; 1153: a third group)
+    for R, S in ((16, 256), (7, 65), (3, 2), (100, 128), (16, 1), (16, 321), (16, 577), (16, 1153)):
         sigma = torch.rand(R, S) * 20
         sigma[0] = 0            # empty ray: background only, depth = last sample
         if R > 1:

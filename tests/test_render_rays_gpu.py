@@ -54,12 +54,15 @@ def _frame(scenes, device, w, h, dist=2.0):
 
 
 @pytest.mark.parametrize("S,S_fine,biased,M", [(64, 0, False, 256), (100, 37, False, 256), (256, 256, False, 512),
-                                               (128, 128, True, 512), (64, 64, True, 1024), (33, 20, False, 256)])
+                                               (128, 128, True, 512), (64, 64, True, 1024), (33, 20, False, 256),
+                                               (320, 320, False, 256), (64, 330, True, 256)])
 def test_one_launch_render_is_bit_identical_to_the_kernel_chain(tn, device, scenes, render, S, S_fine, biased, M):
     """tn_render_rays (everything after the trace in ONE persistent launch) against tn_sample_coarse ->
     tn_find_matched_cells_indexed -> tn_mlp_forward_gather -> tn_composite -> tn_sample_pdf -> ... on the same trace rows, for
     a frame with missing rays (tiles of several rays per wave, partial MLP groups), a batch smaller than the grid (blocks
-    with one ray or none) and a batch that misses the mesh entirely."""
+    with one ray or none) and a batch that misses the mesh entirely.  (320, 320) and (64, 330): more than 320 entries in a list
+    of the PDF sampler, i.e. its plain-loop form, whose merged edges reach the matcher through global memory
+    (pdf_writes_second_copy is false); (320, 320) ends in a composite of 641 samples, two groups of nine chunks."""
     import torch
 
     tr, mlp, field = _setup(tn, scenes, render, device)
@@ -94,7 +97,8 @@ def test_one_launch_render_is_bit_identical_to_the_kernel_chain(tn, device, scen
     assert bool((a["rgb"][~a["ray_mask"]] == torch.tensor([0.1, 0.5, 0.9], device=device)).all())
 
 
-@pytest.mark.parametrize("S,S_fine,biased,M", [(64, 0, False, 256), (100, 37, False, 256), (256, 256, False, 512), (128, 128, True, 512)])
+@pytest.mark.parametrize("S,S_fine,biased,M", [(64, 0, False, 256), (100, 37, False, 256), (256, 256, False, 512), (128, 128, True, 512),
+                                               (320, 320, False, 256)])
 def test_one_launch_render_bf16x3_is_bit_identical_to_the_bf16x3_chain(tn, device, scenes, render, S, S_fine, biased, M):
     """Round 6: the persistent launch also in the opt-in bf16x3 arithmetic (tn_render_rays_ex, mode 1: the MLP phases run
     x3::forward_group, the loop body of k_mlp_forward_x3; ray phase 1 leaves the ray's 32-float direction encoding and its

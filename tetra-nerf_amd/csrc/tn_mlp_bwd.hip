@@ -19,6 +19,7 @@
 //
 // FLOPs per fine sample: forward 122.6 k, dX 114.7 k, dW 122.4 k.
 #include "tn_mlp_common.h"
+#include "tn_ray_ops.h"
 
 namespace tn {
 
@@ -237,40 +238,45 @@ __global__ __launch_bounds__(BWD_BLOCK) void k_mlp_backward(size_t n, BwdIn in, 
 // no gradient): one wavefront per ray.  With dd_i = delta_i sigma_i, T_i = exp(-sum_{k<i} dd_k), w_i = (1 - exp(-dd_i)) T_i
 // and a_i = dL/dw_i = g_rgb . c_i - bg sum(g_rgb) + g_acc:
 //     dL/d sigma_i = delta_i (a_i T_{i+1} - sum_{k>i} a_k w_k),      dL/d c_i = w_i g_rgb.
-// The samples are swept from the far end (suffix sums by wave scans, carried across chunks of 64); the prefix of dd is
-// the total minus the suffix.  Samples whose weight is not finite get zero gradients (nan_to_num in the forward).
+// Two sweeps over the ray.  The first runs near to far and leaves, per chunk of 64 samples, the sum of dd over all chunks
+// before it (`carries`, one float of LDS per chunk): the inclusive wave scan and the carry of ray_composite_chunks, the same
+// operations in the same order, so the prefix of dd -- and with it w_i -- has the forward's bits.  (A total minus a suffix sum
+// would carry an error of ulp(total): on a ray that ends in a surface that is the whole transmittance of the samples in front
+// of it.)  The second runs far to near: the same scan plus the chunk's carry give the prefix, the suffix of a w is an exclusive
+// wave scan from the far end (the values shifted by one lane first) carried across chunks.  Samples whose weight is not finite
+// get zero gradients (nan_to_num in the forward).
 __global__ __launch_bounds__(64) void k_composite_backward(size_t R, uint32_t S, const float *__restrict__ sigma,
                                                            const float *__restrict__ rgb, const float *__restrict__ edges,
                                                            Background background, const float *__restrict__ g_rgb,
                                                            const float *__restrict__ g_acc, float *__restrict__ d_sigma,
                                                            float *__restrict__ d_rgb) {
+    extern __shared__ float carries[];                   // [chunks of the ray]
     const int lane = threadIdx.x;
+    const uint32_t nchunks = (S + 63) / 64;
     for (size_t ray = blockIdx.x; ray < R; ray += gridDim.x) {
         const float *e = edges + ray * (S + 1);
         const float gr = g_rgb ? g_rgb[3 * ray] : 0.f, gg = g_rgb ? g_rgb[3 * ray + 1] : 0.f, gb = g_rgb ? g_rgb[3 * ray + 2] : 0.f;
         const float ga = g_acc ? g_acc[ray] : 0.f;
         const float a_const = ga - ((background.r * gr + background.g * gg) + background.b * gb);
-        // total of dd
-        float tot = 0.f;
-        for (uint32_t j = lane; j < S; j += 64) tot += (e[j + 1] - e[j]) * sigma[ray * S + j];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
-        float carry_dd = 0.f, carry_aw = 0.f;   // suffix sums over the chunks already processed (farther samples)
-        const uint32_t nchunks = (S + 63) / 64;
+        // near to far: the carry every chunk starts from
+        float carry = 0.f;
+        for (uint32_t c = 0; c < nchunks; ++c) {
+            const uint32_t j = c * 64 + lane;
+            const float dd = j < S ? (e[j + 1] - e[j]) * sigma[ray * S + j] : 0.f;
+            const float inc = rayops::wave_incl_scan(dd, lane);
+            if (lane == 0) carries[c] = carry;
+            carry += __shfl(inc, 63);
+        }
+        rayops::lds_sync();
+        float carry_aw = 0.f;                            // sum of a w over the chunks already processed (farther samples)
         for (uint32_t c = nchunks; c-- > 0;) {
             const uint32_t j = c * 64 + lane;
             const bool ok = j < S;
             const size_t q = ray * S + (ok ? j : S - 1);
             const float delta = ok ? e[j + 1] - e[j] : 0.f;
             const float dd = ok ? delta * sigma[q] : 0.f;
-            // inclusive suffix sum of dd within the chunk
-            float suf = dd;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const float o2 = __shfl_down(suf, off);
-                if (lane + off < 64) suf += o2;
-            }
-            const float excl = tot - (suf + carry_dd);          // sum_{k<j} dd_k
+            const float inc = rayops::wave_incl_scan(dd, lane);
+            const float excl = carries[c] + (inc - dd);         // sum_{k<j} dd_k, as ray_composite_chunks forms it
             const float Ti = expf(-excl), Tn = expf(-(excl + dd));
             float w = (1.0f - expf(-dd)) * Ti;
             const bool fin = ok && (w == w) && fabsf(w) <= 3.0e38f;
@@ -278,30 +284,34 @@ __global__ __launch_bounds__(64) void k_composite_backward(size_t R, uint32_t S,
             const float c0 = rgb[3 * q], c1 = rgb[3 * q + 1], c2 = rgb[3 * q + 2];
             const float ai = ((gr * c0 + gg * c1) + gb * c2) + a_const;
             const float aw = fin ? ai * w : 0.f;
-            float sufaw = aw;
+            // exclusive suffix sum of a w within the chunk: the inclusive one of the values one lane farther
+            const float nxt = __shfl_down(aw, 1);
+            float suf = lane < 63 ? nxt : 0.f;
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
-                const float o2 = __shfl_down(sufaw, off);
-                if (lane + off < 64) sufaw += o2;
+                const float o2 = __shfl_down(suf, off);
+                if (lane + off < 64) suf += o2;
             }
-            const float later = (sufaw - aw) + carry_aw;        // sum_{k>j} a_k w_k
+            const float later = suf + carry_aw;                 // sum_{k>j} a_k w_k
             if (ok) {
                 float ds = delta * (ai * Tn - later);
                 if (!fin || !(ds == ds)) ds = 0.f;
                 d_sigma[q] = ds;
                 d_rgb[3 * q] = w * gr; d_rgb[3 * q + 1] = w * gg; d_rgb[3 * q + 2] = w * gb;
             }
-            carry_dd += __shfl(suf, 0);
-            carry_aw += __shfl(sufaw, 0);
+            carry_aw += __shfl(suf, 0) + __shfl(aw, 0);
         }
+        rayops::lds_sync();                              // the next ray overwrites the carries
     }
 }
 
 void launch_composite_backward(size_t R, uint32_t S, const float *sigma, const float *rgb, const float *edges, Background background,
                                const float *d_out_rgb, const float *d_out_acc, float *d_sigma, float *d_rgb, hipStream_t stream) {
     if (R == 0 || S == 0) return;
+    const size_t smem = ((size_t)S + 63) / 64 * sizeof(float);
+    if (smem > 64 * 1024) throw Error("composite_backward: too many samples per ray");
     const unsigned grid = (unsigned)(R < 256u * 32u ? R : 256u * 32u);
-    hipLaunchKernelGGL(k_composite_backward, dim3(grid), dim3(64), 0, stream, R, S, sigma, rgb, edges, background, d_out_rgb, d_out_acc,
+    hipLaunchKernelGGL(k_composite_backward, dim3(grid), dim3(64), smem, stream, R, S, sigma, rgb, edges, background, d_out_rgb, d_out_acc,
                        d_sigma, d_rgb);
 }
 

@@ -218,7 +218,7 @@ def ray_weights(sigma: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
     """RaySamples.get_weights on [R,S] densities and [R,S+1] edges."""
     dd = (edges[:, 1:] - edges[:, :-1]) * sigma
     trans = torch.cumsum(dd[:, :-1], dim=-1)
-    trans = torch.cat([torch.zeros_like(trans[:, :1]), trans], dim=-1)
+    trans = torch.cat([torch.zeros_like(dd[:, :1]), trans], dim=-1)      # (of dd, not of trans: one sample leaves trans empty)
     return torch.nan_to_num((1.0 - torch.exp(-dd)) * torch.exp(-trans))
 
 
@@ -242,7 +242,7 @@ def composite(sigma: torch.Tensor, rgb: torch.Tensor, starts: torch.Tensor, ends
     dd = deltas * sigma
     alphas = 1.0 - torch.exp(-dd)
     trans = torch.cumsum(dd[..., :-1, :], dim=-2)
-    trans = torch.cat([torch.zeros_like(trans[..., :1, :]), trans], dim=-2)
+    trans = torch.cat([torch.zeros_like(dd[..., :1, :]), trans], dim=-2)   # (of dd, not of trans: one sample leaves trans empty)
     weights = torch.nan_to_num(alphas * torch.exp(-trans))
     acc = weights.sum(-2)
     out_rgb = (weights * rgb).sum(-2) + background_tensor(background, rgb.device) * (1.0 - acc)
@@ -423,8 +423,9 @@ class _FusedCompositeFunction(torch.autograd.Function):
         from . import tetranerf_cpp_extension as cpp
 
         sigma, rgb, edges = ctx.saved_tensors
-        d_sigma, d_col = cpp.composite_backward(sigma, rgb, edges, d_rgb, None if d_acc is None else d_acc.reshape(-1),
-                                                ctx.background)
+        # (autograd hands over whatever layout the loss produced -- an expanded scalar after .sum() -- the op takes rows)
+        d_sigma, d_col = cpp.composite_backward(sigma, rgb, edges, None if d_rgb is None else d_rgb.contiguous(),
+                                                None if d_acc is None else d_acc.reshape(-1).contiguous(), ctx.background)
         return d_sigma, d_col, None, None
 
 

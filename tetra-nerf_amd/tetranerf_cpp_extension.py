@@ -1099,17 +1099,25 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
 
 
 def composite_backward(sigma, rgb, edges, d_out_rgb, d_out_acc, background=1.0):
-    """Adjoint of composite() w.r.t. sigma [R,S] and rgb [R,S,3] (the median depth has no gradient)."""
+    """Adjoint of composite() w.r.t. sigma [R,S] and rgb [R,S,3] (the median depth has no gradient).  sigma f32 [R,S], rgb f32
+    [R,S,3], edges f32 [R,S+1]; d_out_rgb f32 [R,3] and d_out_acc f32 [R] (either may be None: that output has no gradient)."""
+    given = ((sigma, "sigma"), (rgb, "rgb"), (edges, "edges")) + tuple((x, name) for x, name in ((d_out_rgb, "d_out_rgb"), (d_out_acc, "d_out_acc"))
+                                                                      if x is not None)
+    for x, name in given:
+        _check_input(x, name)
+        _check(x.dtype == torch.float32, f"{name} must have float32 type")
+    _check(sigma.dim() == 2, "sigma must be f32 [R,S]")
     R, S = sigma.shape
+    _check(tuple(rgb.shape) == (R, S, 3) and tuple(edges.shape) == (R, S + 1), "shape mismatch")
+    _check(d_out_rgb is None or tuple(d_out_rgb.shape) == (R, 3), "d_out_rgb must be f32 [R,3]")
+    _check(d_out_acc is None or tuple(d_out_acc.shape) == (R,), "d_out_acc must be f32 [R]")
     dev = sigma.device
+    _check(all(x.device == dev for x, _ in given), "all tensors must be on the same device")
     d_sigma = _empty((R, S), dtype=torch.float32, device=dev)
     d_rgb = _empty((R, S, 3), dtype=torch.float32, device=dev)
-    g_rgb = None if d_out_rgb is None else d_out_rgb.contiguous().float()
-    g_acc = None if d_out_acc is None else d_out_acc.contiguous().float()
     with _on(dev):
-        _lib.check(_lib.load().tn_composite_backward(R, S, _ptr(sigma.contiguous()), _ptr(rgb.contiguous()), _ptr(edges.contiguous()),
-                                                     _background(background), _ptr(g_rgb), _ptr(g_acc), _ptr(d_sigma), _ptr(d_rgb),
-                                                     _stream(dev)))
+        _lib.check(_lib.load().tn_composite_backward(R, S, _ptr(sigma), _ptr(rgb), _ptr(edges), _background(background), _ptr(d_out_rgb),
+                                                     _ptr(d_out_acc), _ptr(d_sigma), _ptr(d_rgb), _stream(dev)))
     return d_sigma, d_rgb
 
 
