@@ -522,8 +522,8 @@ int tn_mlp_forward_gather_train(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray
  * tn_mlp_forward_gather_train, 1 bf16x3 MFMA).  Mode 1: sigma / rgb are bit for bit those of tn_mlp_forward_gather(mode 1), and
  * x0, h1..h4 and masks are saved in the same layouts, so tn_mlp_backward / tn_mlp_ray_head_grad / tn_mlp_param_grads run
  * unchanged (fp32) on them: the gradient is the exact fp32 adjoint at the bf16x3 forward's activations and ReLU decisions.
- * (The dX chain has an arithmetic of its own, chosen independently: tn_mlp_backward_ex below.  The weight-gradient GEMMs are
- * fp32 only.)  Mode 2 is rejected: plain bf16 is an evaluation arithmetic. */
+ * (The dX chain has an arithmetic of its own, chosen independently: tn_mlp_backward_ex below, and so do the weight-gradient
+ * GEMMs: tn_mlp_param_grads_ex.)  Mode 2 is rejected: plain bf16 is an evaluation arithmetic. */
 int tn_mlp_forward_gather_train_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
                                    const float *barycentric, const float *field_vm, const float *dirs, int mode, float *sigma,
                                    float *rgb, const tn_mlp_backward_buffers *buffers, const float *ray_head_bias, void *stream);
@@ -552,6 +552,18 @@ typedef struct tn_mlp_grads { /* same shapes as tn_mlp_weights */
 } tn_mlp_grads;
 int tn_mlp_param_grads(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const float *dirs,
                        const tn_mlp_backward_buffers *buffers, const tn_mlp_grads *grads, void *stream);
+/* The same with the arithmetic of the four weight-gradient GEMMs chosen per call, independently of the forward's and of the dX
+ * chain's: mode 0 (fp32 MFMA) IS tn_mlp_param_grads -- the same launcher, the same bits; mode 1 (bf16x3 MFMA) evaluates d4 [h3 |
+ * enc]^T, d3 h2^T, d2 h1^T and d1 x0^T on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, K = the sample axis): BOTH streamed
+ * operands are split into three bf16 pieces (round to nearest even, residuals formed in fp32) once per element per block, as
+ * they are staged into LDS, six products per multiply (hh, hm, mh, hl, lh, mm), fp32 accumulation -- each product within 2^-21
+ * of |a| |b|.  Everything else stays fp32: the bias gradients (row sums of d1..d4) and d wd = sum d sigma_raw h3 are VALU
+ * statements over the unsplit values, the rgb head / d bd / d br kernels are those of mode 0 (the same bits).  Buffers, layouts,
+ * accumulation INTO grads, the scratch and the fixed-order reductions are those of tn_mlp_param_grads: no atomics,
+ * bit-reproducible.  Any other mode fails with a message (tn_last_error); mode 2, plain bf16, is an evaluation arithmetic.
+ * Measured on an MI355X: profiles/train_x3_dw_bench.txt. */
+int tn_mlp_param_grads_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const float *dirs,
+                          const tn_mlp_backward_buffers *buffers, const tn_mlp_grads *grads, int mode, void *stream);
 
 /* adjoint of tn_composite w.r.t. sigma [R,S] and rgb [R,S,3], given the gradients of the rendered rgb [R,3] and
  * accumulation [R] (either nullable); the median depth carries no gradient. */

@@ -24,7 +24,7 @@ SYMBOLS = (
     "tn_postprocess_hits", "tn_postprocess_hits_tables",
     "tn_trace_stats", "tn_trace_flag_reasons", "tn_set_option", "tn_mlp_create", "tn_mlp_destroy", "tn_mlp_set_weights",
     "tn_mlp_forward", "tn_mlp_forward_gather", "tn_composite", "tn_gather_uint32", "tn_scatter_ema_uint32",
-    "tn_mlp_forward_gather_train", "tn_mlp_forward_gather_train_ex", "tn_mlp_backward", "tn_mlp_backward_ex", "tn_mlp_ray_head_grad", "tn_mlp_param_grads", "tn_composite_backward", "tn_sample_coarse", "tn_sample_pdf",
+    "tn_mlp_forward_gather_train", "tn_mlp_forward_gather_train_ex", "tn_mlp_backward", "tn_mlp_backward_ex", "tn_mlp_ray_head_grad", "tn_mlp_param_grads", "tn_mlp_param_grads_ex", "tn_composite_backward", "tn_sample_coarse", "tn_sample_pdf",
     "tn_trace_timings", "tn_trace_cross_check", "tn_fill_rows", "tn_compact_hits", "tn_render_rays", "tn_render_rays_ex",
     "tn_trace_ray_order",
     "tn_interpolate_values_backward_bary_vm", "tn_sample_positions_backward",
@@ -100,6 +100,7 @@ def load():
     lib.tn_mlp_backward.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
     lib.tn_mlp_backward_ex.argtypes = [vp, sz, vp, vp, vp, vp, vp, i32, vp]
     lib.tn_mlp_param_grads.argtypes = [vp, sz, u32, vp, vp, vp, vp]
+    lib.tn_mlp_param_grads_ex.argtypes = [vp, sz, u32, vp, vp, vp, i32, vp]
     lib.tn_composite_backward.argtypes = [sz, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_sample_coarse.argtypes = [sz, u32, u32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.tn_sample_pdf.argtypes = [sz, u32, u32, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]

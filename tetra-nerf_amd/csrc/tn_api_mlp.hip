@@ -305,6 +305,33 @@ int tn_mlp_param_grads(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const f
     });
 }
 
+int tn_mlp_param_grads_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const float *dirs, const tn_mlp_backward_buffers *b,
+                          const tn_mlp_grads *grads, int mode, void *stream_) {
+    if (mode == 0) return tn_mlp_param_grads(mlp, n, samples_per_ray, dirs, b, grads, stream_);
+    return guarded([&] {
+        tn_mlp *m = checked_mlp(mlp);
+        check_mode(mode);
+        if (n == 0) return;
+        if (!b || !grads || !dirs) throw tn::Error("null pointer");
+        if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
+        float *const gp[12] = {grads->w1, grads->b1, grads->w2, grads->b2, grads->w3, grads->b3,
+                               grads->wd, grads->bd, grads->wh, grads->bh, grads->wr, grads->br};
+        for (float *p : gp)
+            if (!p) throw tn::Error("null pointer");
+        if (!b->x0 || !b->h1 || !b->h2 || !b->h3 || !b->h4 || !b->d1 || !b->d2 || !b->d3 || !b->d4 || !b->dhead)
+            throw tn::Error("null pointer");
+        DeviceGuard g(m->device);
+        if (!m->grad_scratch.p) {   // first training call of this handle
+            TN_HIP(hipDeviceSynchronize());
+            m->grad_scratch.alloc(tn::mlp_param_grad_scratch_floats());
+        }
+        const tn::MlpBackwardBuffers bb = training_buffers(b);
+        tn::MlpParamGrads pg{gp[0], gp[1], gp[2], gp[3], gp[4], gp[5], gp[6], gp[7], gp[8], gp[9], gp[10], gp[11]};
+        tn::launch_mlp_param_grads_x3(n, samples_per_ray, dirs, m->packs(n / samples_per_ray), bb, pg, (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
 int tn_compact_hits(size_t num_rays, const uint32_t *num_visited, uint32_t *order, uint32_t *count, uint32_t *padded,
                     uint32_t *scratch, size_t scratch_len, void *stream_) {
     return guarded([&] {

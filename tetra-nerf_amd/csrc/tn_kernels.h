@@ -270,6 +270,21 @@ struct MlpParamGrads { float *w1, *b1, *w2, *b2, *w3, *b3, *wd, *bd, *wh, *bh, *
 size_t mlp_param_grad_scratch_floats();
 void launch_mlp_param_grads(size_t n, uint32_t samples_per_ray, const float *dirs, const MlpPacks &w, const MlpBackwardBuffers &b,
                             const MlpParamGrads &g, hipStream_t stream);
+// the same with its four weight-gradient GEMMs in bf16x3 (tn_mlp_x3_dw.hip: both operands split into three bf16 pieces as they
+// are staged, six products per multiply, fp32 accumulation); the bias sums, d wd and the rgb head are fp32 statements as
+// above; same buffers, same scratch, same fixed-order reductions
+void launch_mlp_param_grads_x3(size_t n, uint32_t samples_per_ray, const float *dirs, const MlpPacks &w, const MlpBackwardBuffers &b,
+                               const MlpParamGrads &g, hipStream_t stream);
+// one weight-gradient GEMM of launch_mlp_param_grads_x3: the arguments, grid, slices and slots of tn_mlp_grad.hip's k_dw_gemm
+struct DwGemmArgs {
+    const float *A;        // [128, n]
+    const float *B;        // [32 nbm, n]
+    const float *enc;      // extra: [rays, 28] direction encodings -> a further tile of 32 B rows (28..31 zero)
+    const float *dh;       // extra: d sigma_raw [n]
+    uint32_t spr;          // samples per ray
+    float *part;           // [grid][128 * 32 nb + 256]: dW tile, row sums of A, (extra) the d wd vector
+};
+void launch_dw_gemm_x3(int nbm, bool extra, unsigned grid, const DwGemmArgs &g, size_t n, uint32_t slice, hipStream_t stream);
 // background colour of the RGB renderer (RGBRenderer.combine_rgb: comp + background (1 - accumulation)) and its evaluation-mode
 // behaviour (RGBRenderer.forward when not training: nan_to_num of the sample colours, result clamped to [0, 1])
 struct Background { float r, g, b; int clamp; };

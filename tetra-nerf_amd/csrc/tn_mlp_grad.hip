@@ -304,13 +304,35 @@ Slicing slicing(size_t n, uint32_t unit) {
     return {(unsigned)grid, (uint32_t)slice};
 }
 
+// x3: the GEMM in bf16x3 (k_dw_gemm_x3, tn_mlp_x3_dw.hip: the same grid, slices and slots); the reduction is the same
 template <int NBM, bool EXTRA>
-void run_dw(size_t n, const DwArgs &g, ReduceArgs r, hipStream_t stream) {
+void run_dw(size_t n, const DwArgs &g, ReduceArgs r, bool x3, hipStream_t stream) {
     const Slicing sl = slicing(n, 32);
-    hipLaunchKernelGGL((k_dw_gemm<NBM, EXTRA>), dim3(sl.grid), dim3(256), 0, stream, g, n, sl.slice);
+    if (x3) launch_dw_gemm_x3(NBM, EXTRA, sl.grid, DwGemmArgs{g.A, g.B, g.enc, g.dh, g.spr, g.part}, n, sl.slice, stream);
+    else hipLaunchKernelGGL((k_dw_gemm<NBM, EXTRA>), dim3(sl.grid), dim3(256), 0, stream, g, n, sl.slice);
     r.part = g.part; r.nslots = sl.grid; r.RBM = 32 * NBM; r.RB = 32 * (NBM + (EXTRA ? 1 : 0));
     const uint32_t count = 128 * r.RB + 256;
     hipLaunchKernelGGL(k_reduce_partials, dim3((count + 63) / 64), dim3(256), 0, stream, r);
+}
+
+void param_grads(size_t n, uint32_t samples_per_ray, const float *dirs, const MlpPacks &w, const MlpBackwardBuffers &b,
+                 const MlpParamGrads &g, bool x3, hipStream_t stream) {
+    if (n == 0) return;
+    if (n > 0xFFFFFFFFull) throw Error("param_grads: more than 2^32 samples per call");
+    launch_dir_encoding(n / samples_per_ray, dirs, w.enc, ENC_PAD, stream);
+    float *part = w.grad_scratch;
+    // mlp_head: [enc(27) | base(128)] -> 128, and the density head's weight vector
+    run_dw<4, true>(n, DwArgs{b.d4, b.h3, w.enc, b.dhead, samples_per_ray, part},
+                    ReduceArgs{nullptr, 0, 0, 0, g.wh + ENC, ENC + HID, g.wh, ENC, g.bh, g.wd}, x3, stream);
+    run_dw<4, false>(n, DwArgs{b.d3, b.h2, nullptr, nullptr, 0, part},
+                     ReduceArgs{nullptr, 0, 0, 0, g.w3, HID, nullptr, 0, g.b3, nullptr}, x3, stream);
+    run_dw<4, false>(n, DwArgs{b.d2, b.h1, nullptr, nullptr, 0, part},
+                     ReduceArgs{nullptr, 0, 0, 0, g.w2, HID, nullptr, 0, g.b2, nullptr}, x3, stream);
+    run_dw<2, false>(n, DwArgs{b.d1, b.x0, nullptr, nullptr, 0, part},
+                     ReduceArgs{nullptr, 0, 0, 0, g.w1, FD, nullptr, 0, g.b1, nullptr}, x3, stream);
+    const Slicing sl = slicing(n, 128);
+    hipLaunchKernelGGL(k_rgb_head_grad, dim3(sl.grid), dim3(256), 0, stream, n, sl.slice, b.dhead, b.h4, part);
+    hipLaunchKernelGGL(k_reduce_rgb, dim3((RGB_SLOT + 63) / 64), dim3(256), 0, stream, part, sl.grid, g.wr, g.bd, g.br);
 }
 
 }  // namespace
@@ -319,22 +341,12 @@ size_t mlp_param_grad_scratch_floats() { return (size_t)DW_GRID * (128 * 160 + 2
 
 void launch_mlp_param_grads(size_t n, uint32_t samples_per_ray, const float *dirs, const MlpPacks &w, const MlpBackwardBuffers &b,
                             const MlpParamGrads &g, hipStream_t stream) {
-    if (n == 0) return;
-    if (n > 0xFFFFFFFFull) throw Error("param_grads: more than 2^32 samples per call");
-    launch_dir_encoding(n / samples_per_ray, dirs, w.enc, ENC_PAD, stream);
-    float *part = w.grad_scratch;
-    // mlp_head: [enc(27) | base(128)] -> 128, and the density head's weight vector
-    run_dw<4, true>(n, DwArgs{b.d4, b.h3, w.enc, b.dhead, samples_per_ray, part},
-                    ReduceArgs{nullptr, 0, 0, 0, g.wh + ENC, ENC + HID, g.wh, ENC, g.bh, g.wd}, stream);
-    run_dw<4, false>(n, DwArgs{b.d3, b.h2, nullptr, nullptr, 0, part},
-                     ReduceArgs{nullptr, 0, 0, 0, g.w3, HID, nullptr, 0, g.b3, nullptr}, stream);
-    run_dw<4, false>(n, DwArgs{b.d2, b.h1, nullptr, nullptr, 0, part},
-                     ReduceArgs{nullptr, 0, 0, 0, g.w2, HID, nullptr, 0, g.b2, nullptr}, stream);
-    run_dw<2, false>(n, DwArgs{b.d1, b.x0, nullptr, nullptr, 0, part},
-                     ReduceArgs{nullptr, 0, 0, 0, g.w1, FD, nullptr, 0, g.b1, nullptr}, stream);
-    const Slicing sl = slicing(n, 128);
-    hipLaunchKernelGGL(k_rgb_head_grad, dim3(sl.grid), dim3(256), 0, stream, n, sl.slice, b.dhead, b.h4, part);
-    hipLaunchKernelGGL(k_reduce_rgb, dim3((RGB_SLOT + 63) / 64), dim3(256), 0, stream, part, sl.grid, g.wr, g.bd, g.br);
+    param_grads(n, samples_per_ray, dirs, w, b, g, false, stream);
+}
+
+void launch_mlp_param_grads_x3(size_t n, uint32_t samples_per_ray, const float *dirs, const MlpPacks &w, const MlpBackwardBuffers &b,
+                               const MlpParamGrads &g, hipStream_t stream) {
+    param_grads(n, samples_per_ray, dirs, w, b, g, true, stream);
 }
 
 }  // namespace tn

@@ -39,7 +39,8 @@ reference registers (`tetra-nerf-original`, `tetra-nerf`) are supported.
 
 Opt-ins (fields the reference's config does not have; absent = off, read with getattr): `position_gradients` (gradients for
 origins / directions / vertices), `train_mlp_mode` ("bf16x3": the forward kernels of a training iteration), `train_adjoint_mode`
-("bf16x3": the dX chain of the MLP adjoint, independent of the forward's mode), `eval_mlp_mode` ("bf16x3" / "bf16").
+("bf16x3": the dX chain of the MLP adjoint, independent of the forward's mode), `train_dw_mode` ("bf16x3": the four
+weight-gradient GEMMs of the MLP adjoint, independent of both), `eval_mlp_mode` ("bf16x3" / "bf16").
 
 nerfstudio is not installed in this environment: the adapter is duck-typed (it only touches the attribute names listed
 above) and is tested with stand-ins of nerfstudio's MLP / FieldHead / RayBundle (tests/golden/nerfstudio_standins.py).
@@ -260,6 +261,11 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
             # opt-in, independent of train_mlp_mode (an absent field: fp32): "bf16x3" = the matrix products of the dX chain in the
             # split-operand bf16 arithmetic (TetraRenderer.render_train: adjoint_mode)
             kw["adjoint_mode"] = str(adjoint_mode)
+        dw_mode = getattr(model.config, "train_dw_mode", None)
+        if dw_mode is not None:
+            # opt-in, independent of the other two (an absent field: fp32): "bf16x3" = the weight-gradient GEMMs in the
+            # split-operand bf16 arithmetic (TetraRenderer.render_train: dw_mode)
+            kw["dw_mode"] = str(dw_mode)
         return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
                                ray_head_bias=hb, **kw)
     kw = {}

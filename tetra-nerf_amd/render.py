@@ -356,7 +356,8 @@ class _FusedMlpFunction(torch.autograd.Function):
     """gather + MLP + heads as ONE autograd node: forward = tn_mlp_forward_gather_train_ex (`mode`: "fp32" or "bf16x3"; saves the
     layer inputs and the ReLU masks, 2.3 KB per sample), backward = tn_mlp_backward + tn_mlp_param_grads + tn_interpolate_values_backward (dX
     chain and weight gradients on the fp32 matrix cores, nothing recomputed; with the adjoint mode "bf16x3" the dX chain is
-    tn_mlp_backward_ex(mode 1), its four matrix products on the bf16 matrix cores).  Gradients flow to the field and the 12
+    tn_mlp_backward_ex(mode 1), its four matrix products on the bf16 matrix cores; with the weight-gradient mode "bf16x3" the
+    four weight-gradient GEMMs are tn_mlp_param_grads_ex(mode 1), both operands split as they are staged).  Gradients flow to the field and the 12
     weight tensors, and -- when they require it -- to the barycentrics (tn_interpolate_values_backward_bary_vm on the same
     d x0 rows; the vertex indices are constants) and to the view directions (through the head layer's per-ray term)."""
 
@@ -364,10 +365,12 @@ class _FusedMlpFunction(torch.autograd.Function):
     def forward(ctx, vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray, ray_head_bias, *weights):
         from . import tetranerf_cpp_extension as cpp
 
-        # weights: the 12 tensors, optionally followed by the forward's mode and then the adjoint's ("fp32" when absent)
+        # weights: the 12 tensors, optionally followed by the forward's mode, then the adjoint's, then the weight-gradient GEMMs'
+        # ("fp32" when absent)
         ctx.num_modes = len(weights) - 12
         mode = weights[12] if ctx.num_modes >= 1 else "fp32"
         ctx.adjoint_mode = weights[13] if ctx.num_modes >= 2 else "fp32"
+        ctx.dw_mode = weights[14] if ctx.num_modes >= 3 else "fp32"
         weights = weights[:12]
         ctx.has_bias = ray_head_bias is not None
         sigma, rgb, saved = cpp.mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dirs, list(weights),
@@ -389,7 +392,7 @@ class _FusedMlpFunction(torch.autograd.Function):
         need_bary, need_dirs = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
         res = cpp.mlp_backward(saved, vi, bc, field, dirs, list(weights), sigma, rgb, d_sigma.contiguous(), d_rgb.contiguous(),
                                want_ray_head_grad=ctx.has_bias or need_dirs, want_bary_grad=need_bary,
-                               adjoint_mode=ctx.adjoint_mode)
+                               adjoint_mode=ctx.adjoint_mode, dw_mode=ctx.dw_mode)
         grad_field, grads = res[0], res[1]
         # the per-ray head bias (appearance embedding): its gradient = per-ray sums of the head pre-activation's gradient
         d_head = res[2] if (ctx.has_bias or need_dirs) else None
@@ -448,7 +451,8 @@ class TetraRenderer:
                  num_fine_samples: int = 0, biased: bool = False, dense_tails: bool = False, fused_pass="auto",
                  mlp_mode: str = "fp32", background=1.0, cache_field: bool = True, device_samplers: bool = True,
                  interpolate_values=None, sync_free_train: bool = True, sync_free_min_hits: float = None,
-                 bin_rays: bool = False, train_mlp_mode: str = "fp32", train_adjoint_mode: str = "fp32"):
+                 bin_rays: bool = False, train_mlp_mode: str = "fp32", train_adjoint_mode: str = "fp32",
+                 train_dw_mode: str = "fp32"):
         from . import tetranerf_cpp_extension as cpp
 
         # incoherent batches (random pixels over many cameras): the tracer walks the rays in a locality order of its own
@@ -476,12 +480,16 @@ class TetraRenderer:
         # that mode keeps training in fp32): the forward kernels of a training iteration -- the coarse density pass and the
         # fine forward, saving or not -- run in it.  The adjoint has an arithmetic of its own, train_adjoint_mode, independent of
         # the forward's (all four combinations are valid): "bf16x3" runs the dX chain's four matrix products on the bf16 matrix
-        # cores (tn_mlp_backward_ex); the weight-gradient GEMMs and the gather adjoint are fp32 in both
+        # cores (tn_mlp_backward_ex).  The four weight-gradient GEMMs have a third switch, train_dw_mode, independent of both
+        # (all eight combinations are valid): "bf16x3" splits both streamed operands as they are staged and multiplies on the
+        # bf16 matrix cores (tn_mlp_param_grads_ex); the bias sums, the rgb head and the gather adjoint are fp32 in all of them
         self.mlp_mode = mlp_mode
         self.train_mlp_mode = train_mlp_mode
         self.train_adjoint_mode = train_adjoint_mode
         cpp._mode(train_mlp_mode, inference=False)      # (an unknown mode fails here, not in the first training call)
         cpp._mode(train_adjoint_mode, inference=False)
+        self.train_dw_mode = train_dw_mode
+        cpp._mode(train_dw_mode, inference=False)
         self.train_node_samples = 1 << 22      # render_train: samples per autograd node of the fused MLP (see there)
         # RGBRenderer background: grey level (1.0 white = default config, 0.0 black) or an (r, g, b) triple; render() /
         # render_train() take a per-call override (nerfstudio's BACKGROUND_COLOR_OVERRIDE, model.py:504-518)
@@ -668,7 +676,7 @@ class TetraRenderer:
                      fused: bool = True, capture: Optional[dict] = None, background=None,
                      ray_head_bias: Optional[torch.Tensor] = None, position_gradients: bool = False,
                      vertices: Optional[torch.Tensor] = None, mlp_mode: Optional[str] = None,
-                     adjoint_mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
+                     adjoint_mode: Optional[str] = None, dw_mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
         (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches
         them), gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) --
@@ -693,12 +701,21 @@ class TetraRenderer:
         activations and ReLU decisions.
         adjoint_mode (fused path; None: the renderer's train_adjoint_mode, "fp32" unless chosen otherwise; independent of
         mlp_mode): "bf16x3" runs the four matrix products of the recorded node's dX chain in the split-operand bf16 arithmetic
-        (tn_mlp_backward_ex); the outputs of the call do not depend on it, the weight-gradient GEMMs stay fp32."""
+        (tn_mlp_backward_ex); the outputs of the call do not depend on it.
+        dw_mode (fused path; None: the renderer's train_dw_mode, "fp32" unless chosen otherwise; independent of the other two):
+        "bf16x3" runs the four weight-gradient GEMMs of the recorded node in the split-operand bf16 arithmetic
+        (tn_mlp_param_grads_ex); neither the outputs nor the field gradient depend on it."""
         cpp, S = self.cpp, self.S
         mode = self.train_mlp_mode if mlp_mode is None else mlp_mode
         cpp._mode(mode, inference=False)
         amode = self.train_adjoint_mode if adjoint_mode is None else adjoint_mode
-        modes = (mode,) if cpp._mode(amode, inference=False) == 0 else (mode, amode)      # (the default node is built as it always was)
+        wmode = self.train_dw_mode if dw_mode is None else dw_mode
+        # (the default node is built as it always was: a trailing mode is passed only when it, or one behind it, is chosen)
+        if cpp._mode(wmode, inference=False) != 0:
+            cpp._mode(amode, inference=False)
+            modes = (mode, amode, wmode)
+        else:
+            modes = (mode,) if cpp._mode(amode, inference=False) == 0 else (mode, amode)
         R, dev = origins.shape[0], origins.device
         rand = rand or {}
         # SYNC-FREE form (default for the fused path): the reference compacts the hitting rays with boolean indexing
@@ -865,7 +882,7 @@ class TetraNerfModule(torch.nn.Module):
 
     def __init__(self, tracer, num_vertices: int, num_samples: int = 256, max_ray_triangles: int = 512,
                  num_fine_samples: int = 256, biased: bool = False, gradient_scaling: bool = False,
-                 train_mlp_mode: str = "fp32", train_adjoint_mode: str = "fp32", **renderer_kw):
+                 train_mlp_mode: str = "fp32", train_adjoint_mode: str = "fp32", train_dw_mode: str = "fp32", **renderer_kw):
         super().__init__()
         field = (torch.rand(FIELD_DIM, num_vertices) * 2 - 1) * 1e-4      # model.py:269-271
         field[1:4] = torch.rand(3, num_vertices) * 2 - 1                  # colours, model.py:379-386
@@ -875,7 +892,7 @@ class TetraNerfModule(torch.nn.Module):
         self._tracer = tracer
         self._renderer_args = (int(num_samples), int(max_ray_triangles))
         self._renderer_kw = dict(num_fine_samples=int(num_fine_samples), biased=bool(biased), train_mlp_mode=train_mlp_mode,
-                                 train_adjoint_mode=train_adjoint_mode, **renderer_kw)
+                                 train_adjoint_mode=train_adjoint_mode, train_dw_mode=train_dw_mode, **renderer_kw)
         self._renderer = None
 
     def renderer(self) -> "TetraRenderer":

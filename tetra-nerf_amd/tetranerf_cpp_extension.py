@@ -1023,7 +1023,8 @@ class MlpChain:
 
 
 def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, weights, sigma, rgb, d_sigma, d_rgb,
-                 want_ray_head_grad=False, want_bary_grad=False, return_dx0=False, adjoint_mode="fp32", return_chain=False):
+                 want_ray_head_grad=False, want_bary_grad=False, return_dx0=False, adjoint_mode="fp32", return_chain=False,
+                 dw_mode="fp32"):
     """Adjoint of mlp_forward_gather_train (addition; the reference leaves this to PyTorch autograd, model.py:602-630):
     given the forward's outputs sigma [n] / rgb [n,3], dL/dsigma [n] and dL/drgb [n,3] returns (grad_field [64,V], [12 weight
     gradients in the order of `weights`]).
@@ -1037,8 +1038,13 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
     adjoint_mode: arithmetic of the dX chain, independent of the forward's.  "fp32" (default): tn_mlp_backward.  "bf16x3"
     (tn_mlp_backward_ex, mode 1): its four matrix products on the bf16 matrix cores, three bf16 pieces per operand; softplus' /
     sigmoid', the head layer's gradient d4, the density term and the masks stay fp32 (dhead and d4 are the default's bits), and
-    so do the parameter gradients and the gather adjoint, which read the same buffers.  "bf16" is not an adjoint arithmetic."""
+    so does the gather adjoint, which reads the same buffers.  "bf16" is not an adjoint arithmetic.
+    dw_mode: arithmetic of the four weight-gradient GEMMs, independent of the other two.  "fp32" (default): tn_mlp_param_grads.
+    "bf16x3" (tn_mlp_param_grads_ex, mode 1): both streamed operands split into three bf16 pieces as they are staged, six
+    products per multiply on the bf16 matrix cores, fp32 accumulation; the bias gradients, d wd and the rgb head stay fp32;
+    still without atomics, bit-reproducible.  grad_field does not depend on it.  "bf16" is not a training arithmetic."""
     amode = _mode(adjoint_mode, inference=False)
+    wmode = _mode(dw_mode, inference=False)
     mh = fused_mlp(weights)
     keep = [w.detach() for w in weights]
     n, S = saved.n, saved.S
@@ -1074,7 +1080,10 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
             _lib.check(lib.tn_mlp_backward(*head, stream))
         else:
             _lib.check(lib.tn_mlp_backward_ex(*head, amode, stream))
-        _lib.check(lib.tn_mlp_param_grads(mh.handle, n, S, _ptr(dirs), C.byref(bs), C.byref(gs), stream))
+        if wmode == 0:      # the default goes through the entry it always went through
+            _lib.check(lib.tn_mlp_param_grads(mh.handle, n, S, _ptr(dirs), C.byref(bs), C.byref(gs), stream))
+        else:
+            _lib.check(lib.tn_mlp_param_grads_ex(mh.handle, n, S, _ptr(dirs), C.byref(bs), C.byref(gs), wmode, stream))
         d_ray_bias = None
         if want_ray_head_grad:      # gradient of the per-ray head bias: per-ray sums of d4
             d_ray_bias = _empty((n // S, 128), dtype=torch.float32, device=dev)
