@@ -198,7 +198,10 @@ int tn_interpolate_values_backward_rows(uint32_t interpolation_dim, uint32_t num
  *   tn_transpose_f32: in [rows, cols] -> out [cols, rows]
  *   tn_interpolate_values_vm: field_vm f32 [V,F]; result f32 [F,n] as tn_interpolate_values
  *   tn_interpolate_values_backward_vm: grad_rows f32 [n,F]; field_grad_vm f32 [V,F] is ACCUMULATED into
- *     (zero it first; the adjoint of tn_transpose_f32 brings it back to [F,V]) */
+ *     (zero it first; the adjoint of tn_transpose_f32 brings it back to [F,V])
+ * ALIGNMENT: `result`, `field_vm` and `grad_rows` must be 16-byte aligned, here and in tn_interpolate_values[_backward*] and
+ * tn_interpolate_values_backward_bary_vm: whenever a row is a multiple of 16 bytes (F % 4 == 0 for the [V,F] and [n,F] rows,
+ * num_values % 4 == 0 for the [F,n] result rows) the kernels read and write it as 16-byte vectors. */
 int tn_transpose_f32(uint32_t rows, uint32_t cols, const float *in, float *out, void *stream);
 int tn_interpolate_values_vm(uint32_t interpolation_dim, uint32_t num_values, uint32_t field_dim,
                              const uint32_t *vertex_indices, const float *barycentric, const float *field_vm,

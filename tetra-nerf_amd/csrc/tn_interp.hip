@@ -297,11 +297,13 @@ void run_fwd_vm(uint32_t n, uint32_t Fd, const uint32_t *vi, const float *bc, co
                 hipStream_t stream) {
     if (Fd == 64) {
         const uint32_t nblocks = ((n + 63) / 64 + 3) / 4;  // 4 waves (256 samples) per block
+        // (tests/test_gather_edges_gpu.py: SECOND_TRIP["fwd64"] quotes 256 samples per block and this cap of 4096 blocks)
         const unsigned grid = nblocks < 256u * 16u ? nblocks : 256u * 16u;
         hipLaunchKernelGGL(k_interp_fwd64<D>, dim3(grid), dim3(256), 0, stream, n, vi, bc, fieldT, result);
         return;
     }
     const uint32_t nblocks = ((n + 31) / 32 + 3) / 4;  // 4 waves (128 samples) per block
+    // (tests/test_gather_edges_gpu.py: SECOND_TRIP["fwd"] quotes 128 samples per block and this cap of 4096 blocks)
     const unsigned grid = nblocks < 256u * 16u ? nblocks : 256u * 16u;
     hipLaunchKernelGGL(k_interp_fwd<D>, dim3(grid), dim3(256), 0, stream, n, Fd, vi, bc, fieldT, result);
 }
@@ -312,6 +314,7 @@ void run_bwd_vm(uint32_t n, uint32_t Fd, const uint32_t *vi, const float *bc, co
                 hipStream_t stream) {
     if (n == 0) return;
     const uint32_t nblocks = ((n + TS - 1) / TS + 3) / 4;  // 4 waves per block
+    // (tests/test_gather_edges_gpu.py: SECOND_TRIP["bwd"] quotes 256 samples per block and this cap of 8192 blocks)
     const unsigned grid = nblocks < 256u * 32u ? nblocks : 256u * 32u;
     hipLaunchKernelGGL(k_interp_bwd<D>, dim3(grid), dim3(256), 0, stream, n, Fd, vi, bc, rows, gradT);
 }
@@ -425,6 +428,7 @@ void run_bwd_det(uint32_t V, uint32_t n, uint32_t Fd, const uint32_t *vi, const 
     TN_HIP(rocprim::radix_sort_pairs(tmp, bytes, vi, ks, io, vs, np, 0u, 32u, stream));
     TN_HIP(hipMemsetAsync(st, 0, 2 * (size_t)V * sizeof(uint32_t), stream));
     hipLaunchKernelGGL(k_run_bounds, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream, (uint32_t)np, ks, V, st, en);
+    // (tests/gather_cases.py: DET_GRID quotes this cap of 16,384 blocks, one vertex each)
     const unsigned grid = V < 256u * 64u ? V : 256u * 64u;
     hipLaunchKernelGGL(k_interp_bwd_det<D>, dim3(grid), dim3(256), 0, stream, V, Fd, st, en, vs, bc, grad_rows, gradT);
 }

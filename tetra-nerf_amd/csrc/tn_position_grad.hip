@@ -94,6 +94,7 @@ template <int D>
 void run_bwd_bary(uint32_t n, uint32_t Fd, const uint32_t *vi, const float *rows, const float *fieldT, float *grad_bary,
                   hipStream_t stream) {
     const uint32_t nblocks = ((n + 31) / 32 + 3) / 4;  // 4 waves (128 samples) per block
+    // (tests/test_gather_edges_gpu.py: SECOND_TRIP["bary"] quotes 128 samples per block and this cap of 4096 blocks)
     const unsigned grid = nblocks < 256u * 16u ? nblocks : 256u * 16u;
     hipLaunchKernelGGL(k_interp_bwd_bary<D>, dim3(grid), dim3(256), 0, stream, n, Fd, vi, rows, fieldT, grad_bary);
 }
