@@ -429,6 +429,48 @@ int tn_mlp_forward_gather(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, cons
                           float *rgb, const float *ray_head_bias, const uint32_t *count /* device-side number of RAYS, nullable */,
                           void *stream);
 
+/* ---- per-tetrahedron occupancy field (addition) ------------------------------------------------
+ * The reference declares the field and leaves it unused: TetrahedraNerfConfig.use_occupancy_field registers a
+ * `tetrahedra_occupancy` buffer, f32 [num_cells] (tetranerf/nerfstudio/model.py:98-99,256-265), exports gather_uint32 /
+ * scatter_ema_uint32 for it, and get_outputs never reads or writes it.  The three entry points below finish it; all are
+ * opt-in, on the caller's stream, without a host synchronisation.
+ *
+ * tn_occupancy_update: occupancy f32 [num_cells], in place:
+ *     occupancy[t] = max(decay * occupancy[t], max{ sigma[i] : cells[i] == t })
+ * cells u32 [n] = the matched tetrahedron of every sample (tn_find_matched_cells' cells_out; 0xFFFFFFFF = unmatched), sigma
+ * f32 [n] their densities.  Samples whose cell is unmatched or >= num_cells, or whose sigma is not >= 0 (NaN, negative),
+ * contribute nothing; every tetrahedron decays on every update (one rounding: fl32(decay * occupancy[t])); a NaN occupancy
+ * stays NaN.  One linear pass, then one integer atomic maximum per run of equal cells on the float's bit pattern (accepted
+ * sigmas are >= 0): independent of the order of the samples, identical from run to run.  count (nullable): device-side
+ * number of RAYS of samples_per_ray samples each (see tn_compact_hits); samples from *count * samples_per_ray on are not read. */
+int tn_occupancy_update(uint32_t num_cells, size_t n, const uint32_t *cells, const float *sigma, float decay, float *occupancy,
+                        uint32_t samples_per_ray, const uint32_t *count, void *stream);
+
+/* tn_cull_samples (the reference has no counterpart: model.py:98-99,256-265 declares the field and leaves it unused): a sample
+ * is CULLED iff its cell is a valid id < num_cells and occupancy[cell] < threshold.  Unmatched samples stay live (they are
+ * evaluated on zero features, as without a field), a NaN occupancy is live, threshold <= 0 culls nothing.
+ * live u32 [n]: live[0 .. *live_count) = the indices of the live samples in ASCENDING order (a stable compaction: neighbours
+ * on a ray stay neighbours in the list and share their vertices' field rows; the list equals torch.nonzero of the live mask);
+ * live_count u32 [1] stays in DEVICE memory.  sigma f32 [n] and rgb f32 [n,3] (nullable) are set to 0 at every culled sample
+ * and not touched at live ones; nothing is touched from sample *count * samples_per_ray on (count nullable, as above).
+ * scratch: ceil(n / 1024) + 1 uint32 of device memory (scratch_len = its length): live samples per 1024-sample tile, scanned
+ * by one block (tn_compact_hits' two levels plus that scan). */
+int tn_cull_samples(size_t n, uint32_t samples_per_ray, const uint32_t *cells, const float *occupancy, uint32_t num_cells,
+                    float threshold, uint32_t *live, uint32_t *live_count, float *sigma, float *rgb, uint32_t *scratch,
+                    size_t scratch_len, const uint32_t *count, void *stream);
+
+/* tn_mlp_forward_gather over the listed samples only (the consumer of tn_cull_samples; model.py:98-99,256-265 declares the
+ * occupancy field and leaves it unused): slot i < *live_count of the launch computes sample s = live[i] -- it gathers at s, takes
+ * the per-ray head term (and ray_head_bias row) of ray s / samples_per_ray and stores sigma[s] / rgb[s]; positions not listed
+ * are NOT written.  All arrays keep the shapes of tn_mlp_forward_gather over n_max samples, which is also what the launch is
+ * sized for; rgb == NULL: density only.  For every listed sample the result is bit for bit what tn_mlp_forward_gather gives
+ * it in the same mode.  mode: 0 (fp32 MFMA) or 1 (bf16x3 MFMA); 2 (plain bf16) is refused.  List entries >= n_max (or, with
+ * count, >= *count * samples_per_ray) are skipped. */
+int tn_mlp_forward_gather_indexed(tn_mlp_t mlp, size_t n_max, uint32_t samples_per_ray, const uint32_t *live,
+                                  const uint32_t *live_count, const uint32_t *vertex_indices, const float *barycentric,
+                                  const float *field_vm, const float *dirs, int mode, float *sigma, float *rgb,
+                                  const float *ray_head_bias, const uint32_t *count, void *stream);
+
 /* background colour of nerfstudio's RGBRenderer as the reference model configures / overrides it (model.py:466,504-518;
  * `renderers.BACKGROUND_COLOR_OVERRIDE`): comp_rgb + background (1 - accumulation).  clamp != 0 = the renderer's
  * evaluation mode (RGBRenderer.forward when not training): nan_to_num of the sample colours, result clamped to [0, 1].

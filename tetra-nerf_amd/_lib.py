@@ -28,6 +28,7 @@ SYMBOLS = (
     "tn_trace_timings", "tn_trace_cross_check", "tn_fill_rows", "tn_compact_hits", "tn_render_rays", "tn_render_rays_ex",
     "tn_trace_ray_order",
     "tn_interpolate_values_backward_bary_vm", "tn_sample_positions_backward",
+    "tn_occupancy_update", "tn_cull_samples", "tn_mlp_forward_gather_indexed",
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -107,6 +108,9 @@ def load():
     lib.tn_compact_hits.argtypes = [sz, vp, vp, vp, vp, vp, sz, vp]
     lib.tn_render_rays.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, sz, u32, u32, i32, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_render_rays_ex.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, sz, u32, u32, i32, vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.tn_occupancy_update.argtypes = [u32, sz, vp, vp, C.c_float, vp, u32, vp, vp]
+    lib.tn_cull_samples.argtypes = [sz, u32, vp, vp, u32, C.c_float, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.tn_mlp_forward_gather_indexed.argtypes = [vp, sz, u32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("tn_last_error", "tn_version", "tn_abi_version", "tn_num_faces"):

@@ -343,6 +343,56 @@ int tn_compact_hits(size_t num_rays, const uint32_t *num_visited, uint32_t *orde
     });
 }
 
+int tn_occupancy_update(uint32_t num_cells, size_t n, const uint32_t *cells, const float *sigma, float decay, float *occupancy,
+                        uint32_t samples_per_ray, const uint32_t *count, void *stream_) {
+    return guarded([&] {
+        if (num_cells == 0) return;
+        if (!occupancy || (n && (!cells || !sigma))) throw tn::Error("null pointer");
+        if (count && samples_per_ray == 0) throw tn::Error("occupancy_update: a device-side ray count needs samples_per_ray");
+        tn::launch_occupancy_update(num_cells, n, cells, sigma, decay, occupancy, samples_per_ray, count, (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_cull_samples(size_t n, uint32_t samples_per_ray, const uint32_t *cells, const float *occupancy, uint32_t num_cells,
+                    float threshold, uint32_t *live, uint32_t *live_count, float *sigma, float *rgb, uint32_t *scratch,
+                    size_t scratch_len, const uint32_t *count, void *stream_) {
+    return guarded([&] {
+        if (!live_count || !scratch) throw tn::Error("null pointer");
+        if (n && (!cells || !live || !sigma || (num_cells && !occupancy))) throw tn::Error("null pointer");
+        if (n >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
+        if (count && samples_per_ray == 0) throw tn::Error("cull_samples: a device-side ray count needs samples_per_ray");
+        if (scratch_len < tn::cull_scratch_u32(n)) throw tn::Error("cull_samples: scratch too small (ceil(n / 1024) + 1 uint32)");
+        tn::launch_cull_samples(n, samples_per_ray, cells, occupancy, num_cells, threshold, live, live_count, sigma, rgb, scratch, count,
+                                (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_mlp_forward_gather_indexed(tn_mlp_t mlp, size_t n_max, uint32_t samples_per_ray, const uint32_t *live,
+                                  const uint32_t *live_count, const uint32_t *vertex_indices, const float *barycentric,
+                                  const float *field_vm, const float *dirs, int mode, float *sigma, float *rgb,
+                                  const float *ray_head_bias, const uint32_t *count, void *stream_) {
+    return guarded([&] {
+        tn_mlp *m = checked_mlp(mlp);
+        if (mode == 2)
+            throw tn::Error("mlp_forward_gather_indexed: mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA): the plain-bf16 kernel "
+                            "(mode 2) has no indexed form");
+        check_mode(mode);
+        if (n_max == 0) return;
+        if (!live || !live_count || !vertex_indices || !barycentric || !field_vm || !sigma || (rgb && !dirs)) throw tn::Error("null pointer");
+        if (samples_per_ray == 0 || n_max % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
+        if (n_max >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
+        DeviceGuard g(m->device);
+        const size_t rays = n_max / samples_per_ray;
+        tn::MlpPacks pk = m->packs(rays);
+        pk.ray_bias = rgb ? ray_head_bias : nullptr;
+        tn::launch_mlp_forward_indexed(n_max, samples_per_ray, rays, live, live_count, vertex_indices, barycentric, field_vm, dirs, pk, mode,
+                                       sigma, rgb, (hipStream_t)stream_, count);
+        TN_HIP(hipGetLastError());
+    });
+}
+
 int tn_sample_coarse(size_t num_hit_rays, uint32_t num_samples, uint32_t M, const uint32_t *ray_index, const uint32_t *num_visited,
                      const float *hit_distances, const float *linspace, const float *t_rand, int biased, float *edges,
                      float *near_far, const uint32_t *count, void *stream_) {

@@ -326,6 +326,23 @@ size_t compact_scratch_u32(size_t R);
 void launch_compact_hits(size_t R, const uint32_t *num_visited, uint32_t *order, uint32_t *count, uint32_t *padded, uint32_t *scratch,
                          hipStream_t stream);
 
+// the head layer's per-ray term of a call (tn_mlp.hip): direction encodings (w.enc) -> w.hterm (+ w.ray_bias)
+void launch_head_ray_term(size_t num_rays, const float *dirs, const MlpPacks &w, hipStream_t stream);
+
+// per-tetrahedron occupancy field (tn_occupancy.hip).  update: occupancy[t] = max(decay occupancy[t], max sigma of the samples
+// with cells == t); cull: live [n] = the samples whose tetrahedron is not below the threshold, ascending, *live_count of them,
+// sigma / rgb (nullable) = 0 at the others, scratch: cull_scratch_u32(n) uint32; forward: launch_mlp_forward (mode 0) /
+// launch_mlp_forward_x3 (mode 1) with the fused gather over the listed samples only.  count (nullable): device-side number of rays
+void launch_occupancy_update(uint32_t T, size_t n, const uint32_t *cells, const float *sigma, float decay, float *occupancy,
+                             uint32_t samples_per_ray, const uint32_t *count, hipStream_t stream);
+size_t cull_scratch_u32(size_t n);
+void launch_cull_samples(size_t n, uint32_t samples_per_ray, const uint32_t *cells, const float *occupancy, uint32_t T, float threshold,
+                         uint32_t *live, uint32_t *live_count, float *sigma, float *rgb, uint32_t *scratch, const uint32_t *count,
+                         hipStream_t stream);
+void launch_mlp_forward_indexed(size_t n_max, uint32_t samples_per_ray, size_t num_rays, const uint32_t *live, const uint32_t *live_count,
+                                const uint32_t *vi, const float *bc, const float *fieldT, const float *dirs, const MlpPacks &w, int mode,
+                                float *sigma, float *rgb, hipStream_t stream, const uint32_t *count);
+
 // uint32-indexed gather / EMA scatter (tn_uint32.hip); elem_size 4 = f32, 8 = f64
 void launch_gather_uint32(int elem_size, uint32_t num_values, uint32_t num_indices, const uint32_t *indices,
                           const void *values, void *result, hipStream_t stream);

@@ -303,6 +303,22 @@ static __device__ __forceinline__ void gather_features(float (&bin)[KSH], const 
     }
 }
 
+// Which sample a lane of a 32-sample tile works on.  Plain: slot = sample (s stores when below ns = n; sc = the clamped duplicate
+// it computes).  INDEXED: the slot names its sample through `live` (tn_occupancy.hip); a lane that has none -- beyond the list, or a
+// list entry >= n_samples -- computes a duplicate of an in-range sample and stores nothing (s = ns).
+struct IndexedSample { size_t s, sc, ns; };
+template <bool INDEXED>
+static __device__ __forceinline__ IndexedSample indexed_sample(size_t slot, size_t slotc, size_t n, const uint32_t *__restrict__ live,
+                                                               size_t n_samples) {
+    if constexpr (!INDEXED) return IndexedSample{slot, slotc, n};
+    else {
+        const size_t li = live[slotc];
+        const size_t sc = li < n_samples ? li : n_samples - 1;
+        constexpr size_t NONE = ~(size_t)0;
+        return IndexedSample{slot < n && li < n_samples ? sc : NONE, sc, NONE};
+    }
+}
+
 // density head 128 -> 1 + softplus on the VALU, fp32.  dv: the staged vector behind layer 3's weights (DVEC floats)
 static __device__ __forceinline__ void density_head(const float *dv, const float (&bin)[KSH], int h, size_t s, size_t n,
                                                     float *__restrict__ sigma) {

@@ -15,17 +15,25 @@ namespace mlp {
 // group g = samples [g * GROUP, (g + 1) * GROUP) of n; every thread of the block calls it (it contains the block barriers of
 // the weight stages).  TRAIN: cy carries h4 and the place of its mask from one group of the block to the next (FwdCarry,
 // tn_mlp_common.h: cy->p == nullptr before the first group; the caller stores the last group's with flush_carry).  lds: MAX_STAGE_FLOATS floats.  hterm [rays][128]: the head layer's per-ray term (unused when DENSITY_ONLY).
-template <bool GATHER, bool DENSITY_ONLY, int BLOCK, bool TRAIN>
+// INDEXED (tn_occupancy.hip: the forward over a list of samples): n counts the SLOTS of the list, slot i stands for sample live[i]
+// < n_samples -- it gathers there, takes that sample's ray term and stores there; nothing else of the group changes, so a listed
+// sample gets the bits the plain kernel gives it.  A slot beyond the list, or one that names a sample >= n_samples, stores nothing.
+template <bool GATHER, bool DENSITY_ONLY, int BLOCK, bool TRAIN, bool INDEXED = false>
 static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, size_t n, uint32_t samples_per_ray,
                                                          const float *__restrict__ feats, const uint32_t *__restrict__ vi,
                                                          const float *__restrict__ bc, const float *__restrict__ fieldT,
                                                          const float *__restrict__ hterm, const float *__restrict__ pk,
                                                          float *__restrict__ sigma, float *__restrict__ rgb, const FwdSave &sv,
-                                                         FwdCarry *cy = nullptr) {
+                                                         FwdCarry *cy = nullptr, const uint32_t *__restrict__ live = nullptr,
+                                                         size_t n_samples = 0) {
+    static_assert(!INDEXED || (GATHER && !TRAIN), "the indexed forward is the gathering inference forward");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     constexpr size_t GROUP = (BLOCK / 64) * 32;
-    const size_t s = g * GROUP + (size_t)wave * 32 + (lane & 31);
-    const size_t sc = s < n ? s : n - 1;  // clamped: out-of-range lanes compute a duplicate, store nothing
+    const size_t slot = g * GROUP + (size_t)wave * 32 + (lane & 31);
+    const size_t slotc = slot < n ? slot : n - 1;  // clamped: out-of-range lanes compute a duplicate, store nothing
+    // s: where the lane stores (below ns, or not at all); sc: the sample it computes
+    const IndexedSample ix = indexed_sample<INDEXED>(slot, slotc, n, live, n_samples);
+    const size_t s = ix.s, sc = ix.sc, ns = ix.ns;
     float bin[KSH];
 
     // ---- layer 1: 64 -> 128, B operands straight from the feature-major input [64, n]
@@ -74,7 +82,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
         bias_step<KSH, OT>(acc, lds, lane);
         relu_to_bin(acc, bin);  // mlp_base out_activation = ReLU
     }
-    density_head(lds + lfloats(KSH, OT), bin, h, s, n, sigma);   // (the vector rides behind layer 3's weights)
+    density_head(lds + lfloats(KSH, OT), bin, h, s, ns, sigma);   // (the vector rides behind layer 3's weights)
     if constexpr (DENSITY_ONLY) return;  // coarse pass of the model (model.py:577-581)
     // ---- head [enc(27) | base(128)] -> 128 ReLU: the 128 base columns as a GEMM, the encoding's 27 columns (constant along a
     //      ray) as the per-ray vector the caller made (hterm = Wh[:, :27] enc(dir) + the appearance embedding's bias, if any)
@@ -96,7 +104,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
         cy->p = quad_ptr(sv.h4, n, sc, h);
         cy->m = mask_ptr(3);
     }
-    rgb_head(lds + lfloats(HEAD_KS, OT), bin, h, s, n, rgb);
+    rgb_head(lds + lfloats(HEAD_KS, OT), bin, h, s, ns, rgb);
 }
 
 // after a block's last group: the carried h4 and its mask

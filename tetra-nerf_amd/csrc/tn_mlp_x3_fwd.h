@@ -165,17 +165,22 @@ static __device__ __forceinline__ void init_bias(f32x16 (&acc)[TILES], const uin
 // does (mlp::FwdCarry), they cost this kernel -- which has no register to spare: 256 VGPRs at 2 waves per SIMD -- 30 spilled
 // registers and measured 3 % SLOWER (1.83 against 1.78 ms at 2.1 M samples, alternating processes).  The arithmetic, and so sigma / rgb, are those of
 // TRAIN = false.
-template <bool GATHER, bool DENSITY_ONLY, bool TRAIN = false>
+// INDEXED: as in mlp::mlp_forward_group -- n counts the slots of the list `live`, slot i stands for sample live[i] < n_samples.
+template <bool GATHER, bool DENSITY_ONLY, bool TRAIN = false, bool INDEXED = false>
 static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_t n, uint32_t samples_per_ray, const float *__restrict__ feats,
                                                      const uint32_t *__restrict__ vi, const float *__restrict__ bc,
                                                      const float *__restrict__ fieldT, const float *__restrict__ enc,
                                                      const uint4 *__restrict__ blob, float *__restrict__ sigma, float *__restrict__ rgb,
-                                                     const float *__restrict__ ray_bias, const mlp::FwdSave *sv = nullptr) {
+                                                     const float *__restrict__ ray_bias, const mlp::FwdSave *sv = nullptr,
+                                                     const uint32_t *__restrict__ live = nullptr, size_t n_samples = 0) {
     static_assert(!TRAIN || (GATHER && !DENSITY_ONLY), "the training forward is the gathering, full network");
+    static_assert(!INDEXED || (GATHER && !TRAIN), "the indexed forward is the gathering inference forward");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     constexpr size_t GROUP = (X3_BLOCK / 64) * 32;
-    const size_t s = g * GROUP + (size_t)wave * 32 + (lane & 31);
-    const size_t sc = s < n ? s : n - 1;
+    const size_t slot = g * GROUP + (size_t)wave * 32 + (lane & 31);
+    const size_t slotc = slot < n ? slot : n - 1;
+    const mlp::IndexedSample ix = mlp::indexed_sample<INDEXED>(slot, slotc, n, live, n_samples);
+    const size_t s = ix.s, sc = ix.sc, ns = ix.ns;
     float bin[KSH];
 
     // ---- layer 1: this lane supplies features 32h .. 32h+31 of its sample
@@ -206,7 +211,7 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
         else x3_steps<8, 4>(acc, lds, bin, lane);
         relu_to_bin(acc, bin);
     }
-    mlp::density_head(reinterpret_cast<const float *>(lds + N_L2), bin, h, s, n, sigma);   // (vector behind layer 3's blob)
+    mlp::density_head(reinterpret_cast<const float *>(lds + N_L2), bin, h, s, ns, sigma);   // (vector behind layer 3's blob)
     if constexpr (DENSITY_ONLY) return;
     // ---- head [enc(27) | base(128)] -> 128 ReLU
     __syncthreads();
@@ -234,7 +239,7 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
         mlp::store_bin(sv->h4, n, sc, bin, h);
         *mask_ptr(3) = mlp::mask_of(bin);
     }
-    mlp::rgb_head(reinterpret_cast<const float *>(lds + wu4(2, 4) + wu4(8, 4) + bu4(4)), bin, h, s, n, rgb);
+    mlp::rgb_head(reinterpret_cast<const float *>(lds + wu4(2, 4) + wu4(8, 4) + bu4(4)), bin, h, s, ns, rgb);
 }
 
 }  // namespace x3

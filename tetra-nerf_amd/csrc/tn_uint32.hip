@@ -1,5 +1,6 @@
 // tn_uint32.hip -- the two uint32-indexed helper ops the reference exports for its (dormant) occupancy
-// field: gather_uint32 and scatter_ema_uint32 (src/tetrahedra_tracer.cu:30-113).  Not on the model path.
+// field: gather_uint32 and scatter_ema_uint32 (src/tetrahedra_tracer.cu:30-113).  Not on the model path (the field itself is
+// finished in tn_occupancy.hip, with a maximum instead of this moving average).
 // The EMA update is a compare-and-swap loop on the value's bit pattern; unlike the reference it keeps
 // the full precision of the new value (the reference routes the bit pattern through a float temporary,
 // :61-66,77, which only passes its test through the tolerance).

@@ -40,7 +40,10 @@ reference registers (`tetra-nerf-original`, `tetra-nerf`) are supported.
 Opt-ins (fields the reference's config does not have; absent = off, read with getattr): `position_gradients` (gradients for
 origins / directions / vertices), `train_mlp_mode` ("bf16x3": the forward kernels of a training iteration), `train_adjoint_mode`
 ("bf16x3": the dX chain of the MLP adjoint, independent of the forward's mode), `train_dw_mode` ("bf16x3": the four
-weight-gradient GEMMs of the MLP adjoint, independent of both), `eval_mlp_mode` ("bf16x3" / "bf16").
+weight-gradient GEMMs of the MLP adjoint, independent of both), `eval_mlp_mode` ("bf16x3" / "bf16"), and -- only for a model that
+has the reference's own `tetrahedra_occupancy` buffer (`use_occupancy_field=True`, model.py:98-99,256-265: registered there, never
+used) -- `occupancy_threshold` (evaluation renders skip the network in tetrahedra below it) and `occupancy_decay` (training
+batches update the buffer: max(decay occupancy, max density seen)).
 
 nerfstudio is not installed in this environment: the adapter is duck-typed (it only touches the attribute names listed
 above) and is tested with stand-ins of nerfstudio's MLP / FieldHead / RayBundle (tests/golden/nerfstudio_standins.py).
@@ -266,9 +269,20 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
             # opt-in, independent of the other two (an absent field: fp32): "bf16x3" = the weight-gradient GEMMs in the
             # split-operand bf16 arithmetic (TetraRenderer.render_train: dw_mode)
             kw["dw_mode"] = str(dw_mode)
+        occupancy = getattr(model, "tetrahedra_occupancy", None)
+        decay = getattr(model.config, "occupancy_decay", None)
+        if occupancy is not None and decay is not None:
+            # opt-in (no such field in the reference's config; the BUFFER is the reference's own, registered under
+            # use_occupancy_field=True and left unused there): updated in place once per batch; training itself is not culled
+            kw["occupancy"], kw["occupancy_decay"] = occupancy, float(decay)
         return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
                                ray_head_bias=hb, **kw)
     kw = {}
+    occupancy = getattr(model, "tetrahedra_occupancy", None)
+    threshold = getattr(model.config, "occupancy_threshold", None)
+    if occupancy is not None and threshold is not None:
+        # opt-in as above: samples in tetrahedra whose occupancy is below the threshold skip the network (TetraRenderer.render)
+        kw["occupancy"], kw["occupancy_threshold"] = occupancy, float(threshold)
     eval_mode = getattr(model.config, "eval_mlp_mode", None)
     if eval_mode is not None:
         # opt-in like train_mlp_mode (an absent field, as in the reference's config: the renderer's own fp32): "bf16" = the fast

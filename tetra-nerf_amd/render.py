@@ -294,14 +294,77 @@ def median_margin(weights: torch.Tensor) -> torch.Tensor:
     return (cum - 0.5).abs().min(dim=-1, keepdim=True).values
 
 
+def _cell_ids(cells: torch.Tensor) -> torch.Tensor:
+    """int64 tetrahedron ids of find_visited_cells' "cell_indices" (int32 with -1, or uint32 with 0xFFFFFFFF, for unmatched: both
+    come out as invalid ids, negative or >= 2^32 - 1)."""
+    return cells.to(torch.int64)
+
+
+def occupancy_update_statement(occupancy: torch.Tensor, cells: torch.Tensor, sigma: torch.Tensor, decay: float) -> torch.Tensor:
+    """Statement of the per-tetrahedron occupancy update (tn_occupancy_update computes it in place, bit for bit):
+        occ_new[t] = max(fl32(decay * occupancy[t]), max{ sigma[i] : cells[i] == t })
+    occupancy f32 [T]; cells: the matched tetrahedron of every sample (0xFFFFFFFF / -1 = unmatched); sigma: their densities.
+    The inner maximum is over nothing -- absent -- for a tetrahedron no sample touches; samples whose cell is unmatched or >= T,
+    or whose sigma is not >= 0 (NaN, negative), contribute nothing (an accepted -0 counts as +0); every tetrahedron decays on
+    every update; a NaN occupancy stays NaN.  A maximum: the result does not depend on the order of the samples."""
+    T = occupancy.numel()
+    c = _cell_ids(cells).reshape(-1)
+    s = sigma.detach().reshape(-1).to(torch.float32)
+    ok = (c >= 0) & (c < T) & (s >= 0)
+    decayed = occupancy.detach() * torch.tensor(float(decay), dtype=torch.float32, device=occupancy.device)
+    top = torch.full_like(decayed, float("-inf")).scatter_reduce(0, c[ok], s[ok].abs(), "amax", include_self=True)
+    return torch.maximum(decayed, top)
+
+
+def cull_mask_statement(cells: torch.Tensor, occupancy: torch.Tensor, threshold: float) -> torch.Tensor:
+    """bool mask, shape of `cells`: True = the sample is CULLED, i.e. its cell is a valid id < T and occupancy[cell] < threshold.
+    Unmatched samples stay live (they are evaluated on zero features, as without a field), a NaN occupancy is live (the
+    comparison fails), threshold <= 0 culls nothing.  A culled render is the unculled chain with sigma = 0 and rgb = 0 at the
+    culled samples of both passes (tn_cull_samples writes the zeros, tn_mlp_forward_gather_indexed skips the samples)."""
+    T = occupancy.numel()
+    c = _cell_ids(cells)
+    if T == 0 or not float(threshold) > 0:
+        return torch.zeros(c.shape, dtype=torch.bool, device=cells.device)
+    valid = (c >= 0) & (c < T)
+    return valid & (occupancy.detach()[c.clamp(0, T - 1)] < float(threshold))
+
+
+def occupancy_from_field(cells: torch.Tensor, field: torch.Tensor, mlp, mode: str = "fp32") -> torch.Tensor:
+    """A starting occupancy f32 [T] for a checkpoint that has none: the maximum density over five probes per tetrahedron -- the
+    centroid and the four vertices -- through the density-only gather + MLP kernel (cpp.mlp_forward_gather(dirs=None)).
+    cells int [T, 4]: the vertex ids of the tetrahedra; field f32 [64, V]; mlp: a TetraMLP or an adapter (mlp_weights).
+    A HEURISTIC, not a bound: the field is linear inside a tetrahedron but the density is a ReLU network of it, so the
+    density can exceed all five probes in the interior; choose the threshold with a margin, and let training updates
+    (render_train(occupancy=, occupancy_decay=)) take over."""
+    from . import tetranerf_cpp_extension as cpp
+
+    T, dev = cells.shape[0], field.device
+    if T == 0:
+        return torch.zeros((0,), dtype=torch.float32, device=dev)
+    vi = cells.to(device=dev, dtype=torch.int32).reshape(T, 1, 4).expand(T, 5, 4).contiguous()
+    # barycentrics (b1, b2, b3) of the probes, b0 = 1 - sum: centroid, vertex 0, 1, 2, 3
+    probes = torch.tensor([[0.25, 0.25, 0.25], [0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]],
+                          dtype=torch.float32, device=dev)
+    bc = probes[None].expand(T, 5, 3).contiguous()
+    with torch.no_grad():
+        sigma = cpp.mlp_forward_gather(vi, bc, field.detach(), None, [x.detach() for x in mlp_weights(mlp)], 5, mode=mode)
+    return sigma.view(T, 5).max(dim=1).values
+
+
 def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: TetraMLP, origins: torch.Tensor,
                      directions: torch.Tensor, num_samples: int = 256, max_ray_triangles: int = 512,
                      far_plane: float = 1000.0, num_fine_samples: int = 0, biased: bool = False,
-                     background=1.0) -> Dict[str, torch.Tensor]:
+                     background=1.0, occupancy: Optional[torch.Tensor] = None,
+                     occupancy_threshold: Optional[float] = None) -> Dict[str, torch.Tensor]:
     """Plain-PyTorch statement of the render path in EVALUATION mode (model.py:520-662 with `self.training == False`: the
     samplers do not jitter, the RGB renderer sanitises and clamps); `tracer` needs trace_rays / find_visited_cells
     returning tensors, `interpolate_values(vi, bc, field)` the gather.  Pinned by the reference's own `get_outputs`
-    executed from its file (tests/test_reference_model.py)."""
+    executed from its file (tests/test_reference_model.py).
+    occupancy f32 [T] + occupancy_threshold (both or neither): the CULLED render -- sigma = 0 and rgb = 0 at the samples
+    cull_mask_statement names, in both passes: the coarse weights, hence the PDF samples, see the masked densities, the final
+    composite the masked final samples."""
+    if (occupancy is None) != (occupancy_threshold is None):
+        raise RuntimeError("occupancy and occupancy_threshold go together: pass both or neither")
     out = tracer.trace_rays(origins.contiguous(), directions.contiguous(), max_ray_triangles)
     nv = out["num_visited_cells"]
     nears = out["hit_distances"][:, 0, 0][:, None]
@@ -316,18 +379,29 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
         lists = [x[ray_mask].contiguous() for x in trace_rows(out)]
         near_r, far_r = nears[ray_mask], fars[ray_mask]
 
+        culled = None     # [r, S] of the current pass, with an occupancy
+
         def features(edges):
+            nonlocal culled
             traced = tracer.find_visited_cells(*lists, bin_centres(edges))
+            if occupancy is not None:
+                culled = cull_mask_statement(traced["cell_indices"], occupancy, occupancy_threshold)
             return interpolate_values(traced["vertex_indices"], traced["barycentric_coordinates"], field)
 
         edges, spacing = coarse_samples(near_r, far_r, num_samples, biased, lists[0], lists[3])
         feats = features(edges)
         if num_fine_samples > 0:
-            edges = pdf_sample_bins(spacing, ray_weights(coarse_sigma(mlp, feats), edges), num_fine_samples, near_r, far_r)
+            sigma_c = coarse_sigma(mlp, feats)
+            if culled is not None:
+                sigma_c = torch.where(culled, torch.zeros_like(sigma_c), sigma_c)
+            edges = pdf_sample_bins(spacing, ray_weights(sigma_c, edges), num_fine_samples, near_r, far_r)
             feats = features(edges)
         starts, ends = edges[:, :-1, None], edges[:, 1:, None]
         dirs = directions[ray_mask][:, None, :].expand(-1, edges.shape[1] - 1, -1)
         sigma, col = mlp(feats, dirs)
+        if culled is not None:
+            sigma = torch.where(culled[..., None], torch.zeros_like(sigma), sigma)
+            col = torch.where(culled[..., None], torch.zeros_like(col), col)
         rgb_r, acc_r, depth_r, w_r = composite(sigma, col, starts, ends, background=background, clamp=True)
         rgb[ray_mask] = rgb_r
         acc[ray_mask] = acc_r
@@ -554,16 +628,33 @@ class TetraRenderer:
         kw = {} if count is None else {"count": count}
         return self.tracer.find_visited_cells(*lists, bin_centres(edges), ray_index=ray_index, **kw)
 
-    def _chain_passes(self, lists, edges, ray_index, w, mode, pdf, count=None, coarse_weights=None):
+    def _culled_forward(self, traced, S, dirs, w, mode, hb, count, occ):
+        """mlp_forward_gather of one pass with an occupancy (occ = (occupancy, threshold)): cull_samples on the pass's matched
+        cells writes the zeros of the culled samples and lists the others, mlp_forward_gather_indexed runs the network on those."""
+        cpp = self.cpp
+        vi, bc, cells = traced["vertex_indices"], traced["barycentric_coordinates"], traced["cell_indices"]
+        n, dev = cells.numel(), cells.device
+        sigma = cpp._empty((n,), dtype=torch.float32, device=dev)
+        rgb = None if dirs is None else cpp._empty((n, 3), dtype=torch.float32, device=dev)
+        live, live_count = cpp.cull_samples(cells, occ[0], occ[1], sigma, rgb, samples_per_ray=S, count=count)
+        cpp.mlp_forward_gather_indexed(live, live_count, vi, bc, self.field, dirs, w, S, mode=mode, ray_head_bias=hb, count=count,
+                                       sigma=sigma, rgb=rgb)
+        return sigma if dirs is None else (sigma, rgb)
+
+    def _chain_passes(self, lists, edges, ray_index, w, mode, pdf, count=None, coarse_weights=None, occ=None):
         """The sample placement of the kernel chain: locate -> [coarse weights -> pdf(edges, weights) -> locate] (the bracket
         with fine samples only).  Coarse weights: gather + mlp_base + density head in one kernel and get_weights in one more,
-        unless `coarse_weights(traced, edges)` states them otherwise.  Returns (traced, final edges)."""
+        unless `coarse_weights(traced, edges)` states them otherwise.  occ = (occupancy, threshold): the culled chain
+        (_culled_forward).  Returns (traced, final edges)."""
         traced = self._locate(lists, edges, ray_index, count)
         if self.S_fine > 0:
             if coarse_weights is None:
                 S = edges.shape[1] - 1
-                sigma_c = self.cpp.mlp_forward_gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field,
-                                                      None, w, S, mode=mode, count=count)
+                if occ is None:
+                    sigma_c = self.cpp.mlp_forward_gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field,
+                                                          None, w, S, mode=mode, count=count)
+                else:
+                    sigma_c = self._culled_forward(traced, S, None, w, mode, None, count, occ)
                 weights_c = self.cpp.composite(sigma_c.view(-1, S), None, edges, count=count)
             else:
                 weights_c = coarse_weights(traced, edges)
@@ -571,23 +662,44 @@ class TetraRenderer:
             traced = self._locate(lists, edges, ray_index, count)
         return traced, edges
 
-    def _final_forward(self, vi, bc, edges, dirs, w, mode, hb, count=None):
-        """gather + MLP + heads of the final samples in one kernel (no [64, n] feature buffer): sigma [r,S], rgb [r,S,3]."""
+    def _final_forward(self, vi, bc, edges, dirs, w, mode, hb, count=None, occ=None, traced=None):
+        """gather + MLP + heads of the final samples in one kernel (no [64, n] feature buffer): sigma [r,S], rgb [r,S,3].
+        occ = (occupancy, threshold) with the pass's `traced`: culled (_culled_forward)."""
         S = edges.shape[1] - 1
-        sigma, col = self.cpp.mlp_forward_gather(vi, bc, self.field, dirs, w, S, mode=mode, ray_head_bias=hb, count=count)
+        if occ is None:
+            sigma, col = self.cpp.mlp_forward_gather(vi, bc, self.field, dirs, w, S, mode=mode, ray_head_bias=hb, count=count)
+        else:
+            sigma, col = self._culled_forward(traced, S, dirs, w, mode, hb, count, occ)
         return sigma.view(-1, S), col.view(-1, S, 3)
 
-    def _one_launch_ok(self, mode):
+    def _occupancy_args(self, occupancy, threshold, mode):
+        """(occupancy, threshold) of a culled render() call, checked; None without an occupancy"""
+        if (occupancy is None) != (threshold is None):
+            raise RuntimeError("occupancy and occupancy_threshold go together: pass both or neither (there is no default "
+                               "threshold: what counts as empty is the caller's decision)")
+        if occupancy is None:
+            return None
+        if not self.fused:
+            raise RuntimeError("an occupancy is an input of the fused kernel chain (fused=True); the PyTorch statement is "
+                               "render_reference(..., occupancy=, occupancy_threshold=)")
+        if self.cpp._mode(mode) == 2:
+            raise RuntimeError('mlp_mode="bf16" cannot be combined with an occupancy: the plain-bf16 kernel has no indexed form')
+        return occupancy.detach(), float(threshold)
+
+    def _one_launch_ok(self, mode, culled=False):
         """tn_render_rays' preconditions: device samplers, the per-wave LDS regions of its ray phases fit (either arithmetic
         since round 6: the bf16x3 mode runs x3::forward_group in the MLP phases).  `region` restates launch_render_rays'
-        per-wave LDS region (csrc/tn_render_rays.hip)."""
+        per-wave LDS region (csrc/tn_render_rays.hip).  culled: a call with an occupancy -- the persistent launch does not cull."""
+        if culled:
+            return False
         region = max(max(2 * self.M, 28) + self.S + 1, (max(2 * self.M, 3 * self.S + self.S_fine + 6) + 2 * self.S + self.S_fine + 2) if self.S_fine else 0) + 4
         return (self.fused_pass is not False and mode in ("fp32", "bf16x3") and self.device_samplers and 8 * 4 * region <= 160 * 1024
                 and self.S + self.S_fine + 2 <= 8192)
 
     @torch.no_grad()
     def render(self, origins: torch.Tensor, directions: torch.Tensor, background=None, ray_head_bias=None,
-               mlp_mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
+               mlp_mode: Optional[str] = None, occupancy: Optional[torch.Tensor] = None,
+               occupancy_threshold: Optional[float] = None) -> Dict[str, torch.Tensor]:
         """Evaluation-mode render (model.py:520-662 with `self.training == False`: samplers without jitter, RGB renderer
         with nan_to_num + clamp).  background: per-call override of the renderer's colour (grey level or (r, g, b)).
         ray_head_bias f32 [R, 128] (fused path only): per-ray vector added to mlp_head's pre-activation -- the appearance
@@ -598,9 +710,14 @@ class TetraRenderer:
         NO HOST SYNCHRONISATION (round 5): the reference compacts the hitting rays with boolean indexing (model.py:540-567),
         rounds 2-4 with torch.nonzero -- a device -> host round trip per chunk during which the GPU idles.  Here the hitting
         rays are compacted on the device (tn_compact_hits: their number stays there) and every kernel after the trace takes the
-        address of that count."""
+        address of that count.
+        occupancy f32 [num_cells] + occupancy_threshold (opt-in; both or neither, fused path, "fp32" / "bf16x3"): the per-tetrahedron
+        occupancy field.  Samples whose tetrahedron lies below the threshold (cull_mask_statement) get sigma = rgb = 0 without
+        running the network, in both passes; every other sample gets the bits it gets without an occupancy.  Such a call renders
+        through the kernel chain (the persistent launch does not cull)."""
         cpp, S = self.cpp, self.S
         bg = self._bg(background)
+        occ = self._occupancy_args(occupancy, occupancy_threshold, self.mlp_mode if mlp_mode is None else mlp_mode)
         if not self.fused:
             if ray_head_bias is not None:
                 raise RuntimeError("ray_head_bias is an input of the fused kernels; the PyTorch statement takes the model's own modules")
@@ -609,7 +726,7 @@ class TetraRenderer:
         mode = self.mlp_mode if mlp_mode is None else mlp_mode
         cpp._mode(mode)
         if not self.device_samplers:
-            return self._render_host_compaction(origins, directions, bg, ray_head_bias, mode)
+            return self._render_host_compaction(origins, directions, bg, ray_head_bias, mode, *(occ or ()))
         out = self._trace(origins, directions)
         nv = out["num_visited_cells"]
         ray_mask = nv > 0
@@ -624,7 +741,7 @@ class TetraRenderer:
         order, count = cpp.compact_hits(nv)          # hitting rays first, in ray order; their number stays on the device
         w = mlp_weights(self.mlp)
         d = directions.contiguous()
-        if self._one_launch_ok(mode):
+        if self._one_launch_ok(mode, culled=occ is not None):
             cpp.render_rays(lists, order, count, self.field, d, w, S, self.S_fine, self.biased, out=(rgb, acc, depth), background=bg,
                             clamp=True, ray_head_bias=ray_head_bias, mode=mode)
             return res
@@ -633,15 +750,17 @@ class TetraRenderer:
         dirs_o = d.index_select(0, order_l)
         hb = None if ray_head_bias is None else ray_head_bias.index_select(0, order_l).contiguous()
         edges, near_far = cpp.sample_coarse(lists[0], lists[3], order, S, biased=self.biased, count=count)
-        traced, edges = self._chain_passes(lists, edges, order, w, mode, count=count,
+        traced, edges = self._chain_passes(lists, edges, order, w, mode, count=count, occ=occ,
                                            pdf=lambda e, weights_c: cpp.sample_pdf(e, weights_c, near_far, self.S_fine, count=count))
-        sigma, col = self._final_forward(traced["vertex_indices"], traced["barycentric_coordinates"], edges, dirs_o, w, mode, hb, count)
+        sigma, col = self._final_forward(traced["vertex_indices"], traced["barycentric_coordinates"], edges, dirs_o, w, mode, hb, count,
+                                         occ=occ, traced=traced)
         cpp.composite(sigma, col, edges, background=bg, clamp=True, out=(rgb, acc, depth), ray_index=order,
                       count=count)
         return res
 
     @torch.no_grad()
-    def _render_host_compaction(self, origins, directions, bg, ray_head_bias=None, mode=None):
+    def _render_host_compaction(self, origins, directions, bg, ray_head_bias=None, mode=None, occupancy=None,
+                                occupancy_threshold=None):
         """render() with the PyTorch SAMPLER statements (device_samplers=False: the parity definition of tn_sample_coarse /
         tn_sample_pdf, ~15 small operators per pass) between the HIP kernels.  Sizes its work on the host (torch.nonzero), as
         the reference does; not the production path."""
@@ -651,6 +770,7 @@ class TetraRenderer:
         rgb, acc, depth = self._miss_frame(origins.shape[0], bg, origins.device)
         idx = torch.nonzero(ray_mask)[:, 0]
         mode = self.mlp_mode if mode is None else mode
+        occ = self._occupancy_args(occupancy, occupancy_threshold, mode)
         if idx.numel():
             lists = trace_rows(out)
             ridx = idx.to(torch.int32)
@@ -661,10 +781,10 @@ class TetraRenderer:
                 edges = biased_sample_bins(near_r, far_r, S, lists[0][idx], lists[3][idx]).contiguous()
             else:
                 edges = uniform_sample_bins(near_r, far_r, S).contiguous()
-            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, pdf=lambda e, weights_c: pdf_sample_bins(
+            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, occ=occ, pdf=lambda e, weights_c: pdf_sample_bins(
                 (e - near_r) / (far_r - near_r), weights_c, self.S_fine, near_r, far_r).contiguous())
             sigma, col = self._final_forward(traced["vertex_indices"], traced["barycentric_coordinates"], edges,
-                                             directions[idx].contiguous(), w, mode, hb)
+                                             directions[idx].contiguous(), w, mode, hb, occ=occ, traced=traced)
             rgb_r, acc_r, depth_r = cpp.composite(sigma, col, edges, background=bg, clamp=True)
             rgb[idx] = rgb_r
             acc[idx] = acc_r
@@ -676,7 +796,8 @@ class TetraRenderer:
                      fused: bool = True, capture: Optional[dict] = None, background=None,
                      ray_head_bias: Optional[torch.Tensor] = None, position_gradients: bool = False,
                      vertices: Optional[torch.Tensor] = None, mlp_mode: Optional[str] = None,
-                     adjoint_mode: Optional[str] = None, dw_mode: Optional[str] = None) -> Dict[str, torch.Tensor]:
+                     adjoint_mode: Optional[str] = None, dw_mode: Optional[str] = None,
+                     occupancy: Optional[torch.Tensor] = None, occupancy_decay: Optional[float] = None) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
         (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches
         them), gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) --
@@ -704,8 +825,17 @@ class TetraRenderer:
         (tn_mlp_backward_ex); the outputs of the call do not depend on it.
         dw_mode (fused path; None: the renderer's train_dw_mode, "fp32" unless chosen otherwise; independent of the other two):
         "bf16x3" runs the four weight-gradient GEMMs of the recorded node in the split-operand bf16 arithmetic
-        (tn_mlp_param_grads_ex); neither the outputs nor the field gradient depend on it."""
+        (tn_mlp_param_grads_ex); neither the outputs nor the field gradient depend on it.
+        occupancy f32 [num_cells] + occupancy_decay (opt-in; both or neither, fused path): the per-tetrahedron occupancy field is
+        UPDATED in place once per batch, after the forward, from the final pass's matched cells and the detached final densities
+        (cpp.occupancy_update: occupancy[t] = max(decay occupancy[t], max sigma in t)).  Training itself is not culled: the outputs
+        and the gradients of the batch do not depend on the field.  (The padded duplicate rays of the sync-free form repeat
+        samples of a real ray: harmless to a maximum.)"""
         cpp, S = self.cpp, self.S
+        if (occupancy is None) != (occupancy_decay is None):
+            raise RuntimeError("occupancy and occupancy_decay go together: pass both or neither")
+        if occupancy is not None and not fused:
+            raise RuntimeError("the occupancy update is a kernel of the fused path (fused=True); its statement is occupancy_update_statement")
         mode = self.train_mlp_mode if mlp_mode is None else mlp_mode
         cpp._mode(mode, inference=False)
         amode = self.train_adjoint_mode if adjoint_mode is None else adjoint_mode
@@ -847,6 +977,9 @@ class TetraRenderer:
             feats = interpolate_values(vi, bc, self.field)
             sg, col = self.mlp(feats, dirs[:, None, :].expand(-1, S, -1))
             sigma = sg[..., 0]
+        if occupancy is not None:
+            with torch.no_grad():
+                cpp.occupancy_update(occupancy, traced["cell_indices"], sigma.detach().contiguous(), occupancy_decay)
         if gradient_scaling and torch.is_grad_enabled():
             if spacing is None:
                 spacing = (edges - near_r) / (far_r - near_r)

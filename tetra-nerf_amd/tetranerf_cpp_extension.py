@@ -805,6 +805,124 @@ def mlp_forward_gather(vertex_indices, barycentric_coordinates, field, dirs, wei
     return sigma if density_only else (sigma, rgb)
 
 
+# ---- per-tetrahedron occupancy field (the reference registers `tetrahedra_occupancy`, model.py:98-99,256-265, and never uses it)
+
+def _check_cells(cells, name="cells"):
+    _check_input(cells, name)
+    _check(cells.dtype == torch.int32, f"{name} must be an int32 tensor (find_visited_cells' cell_indices; -1 = unmatched)")
+
+
+def _check_occupancy(occupancy, dev):
+    _check_input(occupancy, "occupancy")
+    _check(occupancy.dtype == torch.float32 and occupancy.dim() == 1 and occupancy.device == dev,
+           "occupancy must be f32 [num_cells] on the samples' device")
+
+
+def _check_count(count, samples_per_ray, n, what):
+    if count is None:
+        return
+    _check(count.dtype == torch.int32 and count.numel() >= 1 and count.is_cuda, "count must be an i32 device tensor")
+    _check(samples_per_ray is not None and int(samples_per_ray) > 0 and n % int(samples_per_ray) == 0,
+           f"{what}: `count` counts rays: it needs samples_per_ray, a divisor of the number of samples")
+
+
+def occupancy_update(occupancy, cells, sigma, decay, samples_per_ray=None, count=None):
+    """IN PLACE update of the per-tetrahedron occupancy field (tn_occupancy_update; statement: render.occupancy_update_statement):
+        occupancy[t] = max(decay * occupancy[t], max{ sigma[i] : cells[i] == t })
+    occupancy f32 [T]; cells i32 [...] = the matched tetrahedron of every sample (find_visited_cells' "cell_indices", -1 =
+    unmatched); sigma f32, as many values.  Unmatched samples, ids >= T and sigmas that are not >= 0 contribute nothing; every
+    tetrahedron decays.  count (i32 [1] on the device, with samples_per_ray): only the samples of the first count[0] rays are
+    read.  Caller's stream, no host synchronisation; bit-identical from run to run.  Returns `occupancy`."""
+    _check_cells(cells)
+    _check_input(sigma, "sigma")
+    dev = cells.device
+    _check_occupancy(occupancy, dev)
+    _check(sigma.dtype == torch.float32 and sigma.numel() == cells.numel() and sigma.device == dev,
+           "sigma must be f32 with one value per entry of cells")
+    n = cells.numel()
+    if samples_per_ray is None and count is not None and cells.dim() >= 2:
+        samples_per_ray = cells.size(-1)
+    _check_count(count, samples_per_ray, n, "occupancy_update")
+    with _on(dev):
+        _lib.check(_lib.load().tn_occupancy_update(occupancy.numel(), n, _ptr(cells), _ptr(sigma), float(decay), _ptr(occupancy),
+                                                   int(samples_per_ray or 0), _ptr(count), _stream(dev)))
+    return occupancy
+
+
+_CULL_SCRATCH = {}   # device -> i32 scratch of cull_samples (tile counts), allocated once and grown on demand
+
+
+def cull_samples(cells, occupancy, threshold, sigma, rgb=None, samples_per_ray=None, count=None):
+    """The samples the network still has to run on (tn_cull_samples; statement: render.cull_mask_statement): a sample is culled iff
+    its cell is a valid id < T and occupancy[cell] < threshold; unmatched samples and a NaN occupancy stay live, threshold <= 0
+    culls nothing.  Writes sigma = 0 (and rgb = 0 when given) at the culled samples, leaves the live positions untouched, and returns
+    (live i32 [n], live_count i32 [1] on the device): live[:live_count] = the indices of the live samples, ascending
+    (= torch.nonzero of the live mask); the rest of `live` is unwritten.  count (i32 [1] device tensor, with samples_per_ray --
+    default: the last dimension of a 2-D `cells`): samples from count[0] * samples_per_ray on are neither listed nor touched.
+    Caller's stream, no host synchronisation."""
+    _check_cells(cells)
+    _check_input(sigma, "sigma")
+    dev = cells.device
+    _check_occupancy(occupancy, dev)
+    n = cells.numel()
+    _check(n < 0xFFFFFFFF, "too many samples for one call")
+    _check(sigma.dtype == torch.float32 and sigma.numel() == n and sigma.device == dev, "sigma must be f32 with one value per entry of cells")
+    if rgb is not None:
+        _check_input(rgb, "rgb")
+        _check(rgb.dtype == torch.float32 and rgb.numel() == 3 * n and rgb.device == dev, "rgb must be f32 [n, 3]")
+    if samples_per_ray is None:
+        samples_per_ray = cells.size(-1) if cells.dim() >= 2 else 1
+    _check_count(count, samples_per_ray, n, "cull_samples")
+    live = _empty((n,), dtype=torch.int32, device=dev)
+    live_count = _empty((1,), dtype=torch.int32, device=dev)
+    need = (n + 1023) // 1024 + 1
+    scratch = _CULL_SCRATCH.get(dev)
+    if scratch is None or scratch.numel() < need:
+        scratch = _CULL_SCRATCH[dev] = torch.empty((max(need + need // 4, 1024),), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().tn_cull_samples(n, int(samples_per_ray), _ptr(cells), _ptr(occupancy), occupancy.numel(), float(threshold),
+                                               _ptr(live), _ptr(live_count), _ptr(sigma), _ptr(rgb), _ptr(scratch), scratch.numel(),
+                                               _ptr(count), _stream(dev)))
+    return live, live_count
+
+
+def mlp_forward_gather_indexed(live, live_count, vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray,
+                               mode="fp32", ray_head_bias=None, count=None, sigma=None, rgb=None):
+    """mlp_forward_gather over the listed samples only (tn_mlp_forward_gather_indexed): slot i < live_count[0] computes sample
+    live[i] -- gathers there, takes the head term of that sample's ray, stores sigma / rgb there.  live i32 [n], live_count i32 [1]
+    on the device (cull_samples); all other arguments as mlp_forward_gather over all n samples.  sigma f32 [n] / rgb f32 [n, 3]: the
+    tensors to store into (what cull_samples zeroed at the culled samples); positions that are not listed are NOT written --
+    without them fresh (unwritten) tensors are returned.  For every listed sample the result is bit for bit mlp_forward_gather's
+    in the same mode; mode "fp32" or "bf16x3" ("bf16" has no indexed kernel).  dirs=None: density only -> sigma."""
+    density_only = dirs is None
+    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
+    _check(_MODES.get(mode) != 2, 'mlp_forward_gather_indexed: mlp mode must be "fp32" or "bf16x3": the plain-bf16 kernel has no '
+                                  'indexed form')
+    dev = field.device
+    for x, name in ((live, "live"), (live_count, "live_count")):
+        _check_input(x, name)
+        _check(x.dtype == torch.int32 and x.device == dev, f"{name} must be an int32 tensor on the field's device")
+    _check(live.numel() >= n and live_count.numel() >= 1, "live must hold n entries, live_count one")
+    _check_count(count, S, n, "mlp_forward_gather_indexed")
+    m = fused_mlp(weights)
+    field_vm = field_vertex_major(field)
+    if sigma is None:
+        sigma = _empty((n,), dtype=torch.float32, device=dev)
+    if rgb is None and not density_only:
+        rgb = _empty((n, 3), dtype=torch.float32, device=dev)
+    _check_input(sigma, "sigma")
+    _check(sigma.dtype == torch.float32 and sigma.numel() == n and sigma.device == dev, "sigma must be f32 [n]")
+    if not density_only:
+        _check_input(rgb, "rgb")
+        _check(rgb.dtype == torch.float32 and rgb.numel() == 3 * n and rgb.device == dev, "rgb must be f32 [n, 3]")
+    with _on(dev):
+        _lib.check(_lib.load().tn_mlp_forward_gather_indexed(
+            m.handle, n, S, _ptr(live), _ptr(live_count), _ptr(vertex_indices), _ptr(barycentric_coordinates), _ptr(field_vm), _ptr(dirs),
+            _mode(mode), _ptr(sigma), None if density_only else _ptr(rgb),
+            _ptr(None if density_only else _ray_bias(ray_head_bias, n // S, dev)), _ptr(count), _stream(dev)))
+    return sigma if density_only else (sigma, rgb)
+
+
 class _RgbBackground(C.Structure):   # tn_rgb_background
     _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("clamp", C.c_int)]
 
