@@ -610,6 +610,38 @@ int tn_mlp_param_grads(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const f
 int tn_mlp_param_grads_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const float *dirs,
                           const tn_mlp_backward_buffers *buffers, const tn_mlp_grads *grads, int mode, void *stream);
 
+/* Occupancy-culled TRAINING (the reference has no counterpart: model.py:98-99,256-265 declares the occupancy field and leaves it
+ * unused).  The four entries below run a training batch on the n_live listed samples only; n_live is a HOST value (the caller
+ * reads tn_cull_samples' *live_count back: one synchronisation per culled batch), live u32 [n_live] is ascending, n_samples is
+ * the size of the uncompacted arrays.  Every tn_mlp_backward_buffers tensor holds n_live COMPACT columns in the usual quad-major
+ * layout with stride n_live: column i belongs to sample live[i].  tn_mlp_backward[_ex] runs unchanged on such buffers with n =
+ * n_live and compacted sigma / rgb / d_sigma / d_rgb (tn_compact_rows).  n_live == 0 is a valid call of each: no launch.
+ *
+ * tn_mlp_forward_gather_train_ex over the list (model.py:98-99,256-265): slot i gathers at s = live[i], takes the head term (and
+ * ray_head_bias row) of ray s / samples_per_ray, stores sigma[s] / rgb[s] -- the bits tn_mlp_forward_gather_train_ex gives that
+ * sample in the same mode -- and saves at column i.  Positions not listed are NOT written; a list entry >= n_samples stores no
+ * output.  vertex_indices, barycentric, sigma, rgb cover n_samples samples, dirs and ray_head_bias n_samples / samples_per_ray
+ * rays.  mode 0 (fp32 MFMA) or 1 (bf16x3 MFMA); 2 (plain bf16) is refused. */
+int tn_mlp_forward_gather_train_indexed(tn_mlp_t mlp, size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
+                                        const uint32_t *vertex_indices, const float *barycentric, const float *field_vm,
+                                        const float *dirs, int mode, float *sigma, float *rgb, const tn_mlp_backward_buffers *buffers,
+                                        const float *ray_head_bias, void *stream);
+/* tn_mlp_param_grads_ex on compact buffers (model.py:98-99,256-265): the twelve gradients, ACCUMULATED, summed over the listed
+ * samples; only the head layer's GEMM reads the list (the direction encoding of ray live[i] / samples_per_ray).  dirs f32
+ * [n_samples / samples_per_ray, 3].  n_live == 0: grads untouched. */
+int tn_mlp_param_grads_indexed(tn_mlp_t mlp, size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
+                               const float *dirs, const tn_mlp_backward_buffers *buffers, const tn_mlp_grads *grads, int mode,
+                               void *stream);
+/* tn_mlp_ray_head_grad on compact buffers (model.py:98-99,256-265): d_ray_head_bias f32 [n_samples / samples_per_ray, 128], row r =
+ * the sum of d4's columns whose sample belongs to ray r, in a fixed order; zeros for a ray without a live sample (all rows
+ * when n_live == 0). */
+int tn_mlp_ray_head_grad_indexed(size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
+                                 const tn_mlp_backward_buffers *buffers, float *d_ray_head_bias, void *stream);
+/* dst row i = src row live[i], i < n_live; rows of words_per_row = 1, 3 or 4 32-bit words (model.py:98-99,256-265: the vertex ids,
+ * barycentrics, outputs and output gradients of the listed samples, for the per-sample kernels that read them by position).
+ * Every list entry must be a row of src. */
+int tn_compact_rows(uint32_t words_per_row, size_t n_live, const uint32_t *live, const void *src, void *dst, void *stream);
+
 /* adjoint of tn_composite w.r.t. sigma [R,S] and rgb [R,S,3], given the gradients of the rendered rgb [R,3] and
  * accumulation [R] (either nullable); the median depth carries no gradient. */
 int tn_composite_backward(size_t num_rays, uint32_t num_samples, const float *sigma, const float *rgb, const float *edges,

@@ -29,6 +29,7 @@ SYMBOLS = (
     "tn_trace_ray_order",
     "tn_interpolate_values_backward_bary_vm", "tn_sample_positions_backward",
     "tn_occupancy_update", "tn_cull_samples", "tn_mlp_forward_gather_indexed",
+    "tn_mlp_forward_gather_train_indexed", "tn_mlp_param_grads_indexed", "tn_mlp_ray_head_grad_indexed", "tn_compact_rows",
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -111,6 +112,10 @@ def load():
     lib.tn_occupancy_update.argtypes = [u32, sz, vp, vp, C.c_float, vp, u32, vp, vp]
     lib.tn_cull_samples.argtypes = [sz, u32, vp, vp, u32, C.c_float, vp, vp, vp, vp, vp, sz, vp, vp]
     lib.tn_mlp_forward_gather_indexed.argtypes = [vp, sz, u32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.tn_mlp_forward_gather_train_indexed.argtypes = [vp, sz, sz, u32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.tn_mlp_param_grads_indexed.argtypes = [vp, sz, sz, u32, vp, vp, vp, vp, i32, vp]
+    lib.tn_mlp_ray_head_grad_indexed.argtypes = [sz, sz, u32, vp, vp, vp, vp]
+    lib.tn_compact_rows.argtypes = [u32, sz, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("tn_last_error", "tn_version", "tn_abi_version", "tn_num_faces"):

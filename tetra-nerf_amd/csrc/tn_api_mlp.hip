@@ -393,6 +393,82 @@ int tn_mlp_forward_gather_indexed(tn_mlp_t mlp, size_t n_max, uint32_t samples_p
     });
 }
 
+int tn_mlp_forward_gather_train_indexed(tn_mlp_t mlp, size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
+                                        const uint32_t *vertex_indices, const float *barycentric, const float *field_vm,
+                                        const float *dirs, int mode, float *sigma, float *rgb, const tn_mlp_backward_buffers *b,
+                                        const float *ray_head_bias, void *stream_) {
+    return guarded([&] {
+        tn_mlp *m = checked_mlp(mlp);
+        if (mode == 2)
+            throw tn::Error("mlp_forward_gather_train_indexed: mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA): the plain-bf16 kernel "
+                            "(mode 2) has neither a training nor an indexed form");
+        check_mode(mode);
+        if (n_live == 0) return;
+        if (!live || !vertex_indices || !barycentric || !field_vm || !dirs || !sigma || !rgb || !b) throw tn::Error("null pointer");
+        if (!b->x0 || !b->h1 || !b->h2 || !b->h3 || !b->h4 || !b->masks) throw tn::Error("null pointer");
+        if (samples_per_ray == 0 || n_samples == 0 || n_samples % samples_per_ray != 0)
+            throw tn::Error("n_samples must be a positive multiple of samples_per_ray");
+        if (n_samples >= 0xFFFFFFFFull || n_live >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
+        DeviceGuard g(m->device);
+        tn::MlpPacks pk = m->packs(n_samples / samples_per_ray);
+        pk.ray_bias = ray_head_bias;
+        tn::launch_mlp_forward_train_indexed(n_live, n_samples, samples_per_ray, live, vertex_indices, barycentric, field_vm, dirs, pk, mode,
+                                             sigma, rgb, training_buffers(b), (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_mlp_param_grads_indexed(tn_mlp_t mlp, size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
+                               const float *dirs, const tn_mlp_backward_buffers *b, const tn_mlp_grads *grads, int mode, void *stream_) {
+    return guarded([&] {
+        tn_mlp *m = checked_mlp(mlp);
+        check_mode(mode);
+        if (n_live == 0) return;   // (grads are accumulated into: untouched)
+        if (!live || !b || !grads || !dirs) throw tn::Error("null pointer");
+        if (samples_per_ray == 0 || n_samples == 0 || n_samples % samples_per_ray != 0)
+            throw tn::Error("n_samples must be a positive multiple of samples_per_ray");
+        if (n_samples >= 0xFFFFFFFFull || n_live >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
+        float *const gp[12] = {grads->w1, grads->b1, grads->w2, grads->b2, grads->w3, grads->b3,
+                               grads->wd, grads->bd, grads->wh, grads->bh, grads->wr, grads->br};
+        for (float *p : gp)
+            if (!p) throw tn::Error("null pointer");
+        if (!b->x0 || !b->h1 || !b->h2 || !b->h3 || !b->h4 || !b->d1 || !b->d2 || !b->d3 || !b->d4 || !b->dhead)
+            throw tn::Error("null pointer");
+        DeviceGuard g(m->device);
+        if (!m->grad_scratch.p) {   // first training call of this handle
+            TN_HIP(hipDeviceSynchronize());
+            m->grad_scratch.alloc(tn::mlp_param_grad_scratch_floats());
+        }
+        tn::MlpParamGrads pg{gp[0], gp[1], gp[2], gp[3], gp[4], gp[5], gp[6], gp[7], gp[8], gp[9], gp[10], gp[11]};
+        tn::launch_mlp_param_grads_indexed(n_live, n_samples, samples_per_ray, live, dirs, m->packs(n_samples / samples_per_ray),
+                                           training_buffers(b), pg, mode, (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_mlp_ray_head_grad_indexed(size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
+                                 const tn_mlp_backward_buffers *b, float *d_ray_head_bias, void *stream_) {
+    return guarded([&] {
+        if (n_samples == 0) return;
+        if (!d_ray_head_bias || (n_live && (!live || !b || !b->d4))) throw tn::Error("null pointer");
+        if (samples_per_ray == 0 || n_samples % samples_per_ray != 0) throw tn::Error("n_samples must be a multiple of samples_per_ray");
+        if (n_samples >= 0xFFFFFFFFull || n_live >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
+        tn::launch_ray_head_grad_indexed(n_live, n_samples, samples_per_ray, live, n_live ? b->d4 : nullptr, d_ray_head_bias,
+                                         (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_compact_rows(uint32_t words_per_row, size_t n_live, const uint32_t *live, const void *src, void *dst, void *stream_) {
+    return guarded([&] {
+        if (words_per_row != 1 && words_per_row != 3 && words_per_row != 4) throw tn::Error("compact_rows: rows of 1, 3 or 4 32-bit words");
+        if (n_live == 0) return;
+        if (!live || !src || !dst) throw tn::Error("null pointer");
+        tn::launch_compact_rows((int)words_per_row, n_live, live, src, dst, (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
 int tn_sample_coarse(size_t num_hit_rays, uint32_t num_samples, uint32_t M, const uint32_t *ray_index, const uint32_t *num_visited,
                      const float *hit_distances, const float *linspace, const float *t_rand, int biased, float *edges,
                      float *near_far, const uint32_t *count, void *stream_) {

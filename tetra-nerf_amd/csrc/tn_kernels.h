@@ -342,6 +342,23 @@ void launch_cull_samples(size_t n, uint32_t samples_per_ray, const uint32_t *cel
 void launch_mlp_forward_indexed(size_t n_max, uint32_t samples_per_ray, size_t num_rays, const uint32_t *live, const uint32_t *live_count,
                                 const uint32_t *vi, const float *bc, const float *fieldT, const float *dirs, const MlpPacks &w, int mode,
                                 float *sigma, float *rgb, hipStream_t stream, const uint32_t *count);
+// occupancy-culled TRAINING (tn_occupancy_train.hip, tn_occupancy_dw.hip): n_live (a host value) slots of the ascending list
+// `live` of samples < n_samples.  forward: launch_mlp_forward_train (mode 0) / launch_mlp_forward_x3_train (mode 1) over the list
+// -- sigma / rgb stored at the listed samples, `save` holds n_live compact columns, column i = sample live[i]; the dX kernels
+// run unchanged on such buffers with n = n_live.  param grads: launch_mlp_param_grads[_x3] on compact buffers (only the head
+// layer's GEMM reads the list; dirs over all n_samples / samples_per_ray rays).  ray head grad: out [n_samples /
+// samples_per_ray, 128] = per-ray sums of the compact d4, zeros for a ray without a live sample.  compact rows: dst row i = src
+// row live[i], rows of 1, 3 or 4 32-bit words.
+void launch_mlp_forward_train_indexed(size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live, const uint32_t *vi,
+                                      const float *bc, const float *fieldT, const float *dirs, const MlpPacks &w, int mode, float *sigma,
+                                      float *rgb, const MlpBackwardBuffers &save, hipStream_t stream);
+void launch_mlp_param_grads_indexed(size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live, const float *dirs,
+                                    const MlpPacks &w, const MlpBackwardBuffers &b, const MlpParamGrads &g, int mode, hipStream_t stream);
+void launch_dw_gemm_head_indexed(bool x3, unsigned grid, const DwGemmArgs &g, size_t n, uint32_t slice, const uint32_t *live,
+                                 uint32_t num_rays, hipStream_t stream);
+void launch_ray_head_grad_indexed(size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live, const float *d4,
+                                  float *out, hipStream_t stream);
+void launch_compact_rows(int words_per_row, size_t n_live, const uint32_t *live, const void *src, void *dst, hipStream_t stream);
 
 // uint32-indexed gather / EMA scatter (tn_uint32.hip); elem_size 4 = f32, 8 = f64
 void launch_gather_uint32(int elem_size, uint32_t num_values, uint32_t num_indices, const uint32_t *indices,

@@ -18,6 +18,7 @@ namespace mlp {
 // INDEXED (tn_occupancy.hip: the forward over a list of samples): n counts the SLOTS of the list, slot i stands for sample live[i]
 // < n_samples -- it gathers there, takes that sample's ray term and stores there; nothing else of the group changes, so a listed
 // sample gets the bits the plain kernel gives it.  A slot beyond the list, or one that names a sample >= n_samples, stores nothing.
+// TRAIN && INDEXED (tn_occupancy_train.hip): the saves go to the SLOT, with n -- the number of slots -- as the quad-major stride.
 template <bool GATHER, bool DENSITY_ONLY, int BLOCK, bool TRAIN, bool INDEXED = false>
 static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, size_t n, uint32_t samples_per_ray,
                                                          const float *__restrict__ feats, const uint32_t *__restrict__ vi,
@@ -26,7 +27,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
                                                          float *__restrict__ sigma, float *__restrict__ rgb, const FwdSave &sv,
                                                          FwdCarry *cy = nullptr, const uint32_t *__restrict__ live = nullptr,
                                                          size_t n_samples = 0) {
-    static_assert(!INDEXED || (GATHER && !TRAIN), "the indexed forward is the gathering inference forward");
+    static_assert(!INDEXED || GATHER, "the indexed forward gathers its samples itself");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     constexpr size_t GROUP = (BLOCK / 64) * 32;
     const size_t slot = g * GROUP + (size_t)wave * 32 + (lane & 31);
@@ -34,6 +35,8 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
     // s: where the lane stores (below ns, or not at all); sc: the sample it computes
     const IndexedSample ix = indexed_sample<INDEXED>(slot, slotc, n, live, n_samples);
     const size_t s = ix.s, sc = ix.sc, ns = ix.ns;
+    // TRAIN: the column of the save buffers.  INDEXED saves compactly: slot i of the buffers (n of them) is sample live[i]
+    const size_t col = INDEXED ? slotc : sc;
     float bin[KSH];
 
     // ---- layer 1: 64 -> 128, B operands straight from the feature-major input [64, n]
@@ -52,13 +55,13 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
         if constexpr (TRAIN) {
             // (the first group of a block has nothing to carry: it stores zeros where its own h4 and mask go -- the same lane
             //  stores the values there later, and a wave's stores to one address land in program order)
-            if (!cy->p) { cy->p = quad_ptr(sv.h4, n, sc, h); cy->m = sv.masks + ((size_t)3 * n + sc) * 2 + h; }
-            gemm_steps_store_carry<KS1, OT>(acc, bin, lds, lane, quad_ptr_x0(sv.x0, n, sc, h), n, *cy, 2 * n);
+            if (!cy->p) { cy->p = quad_ptr(sv.h4, n, col, h); cy->m = sv.masks + ((size_t)3 * n + col) * 2 + h; }
+            gemm_steps_store_carry<KS1, OT>(acc, bin, lds, lane, quad_ptr_x0(sv.x0, n, col, h), n, *cy, 2 * n);
         } else gemm_steps<KS1, 0, OT>(acc, bin, lds, lane);
         bias_step<KS1, OT>(acc, lds, lane);
         relu_to_bin(acc, bin);
     }
-    auto mask_ptr = [&](int layer) { return sv.masks + ((size_t)layer * n + sc) * 2 + h; };   // TRAIN only
+    auto mask_ptr = [&](int layer) { return sv.masks + ((size_t)layer * n + col) * 2 + h; };   // TRAIN only
     // ---- layers 2, 3: 128 -> 128, accumulators fed back as B operands
     __syncthreads();
     stage<BLOCK>(lds, pk + OFF_W2, lfloats(KSH, OT) / 4);
@@ -66,7 +69,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
     {
         f32x16 acc[OT];
         zero_acc(acc);
-        if constexpr (TRAIN) gemm_steps_store<KSH, 0, OT, KSH, true>(acc, bin, lds, lane, quad_ptr(sv.h1, n, sc, h), 2 * n, mask_ptr(0));
+        if constexpr (TRAIN) gemm_steps_store<KSH, 0, OT, KSH, true>(acc, bin, lds, lane, quad_ptr(sv.h1, n, col, h), 2 * n, mask_ptr(0));
         else gemm_steps<KSH, 0, OT>(acc, bin, lds, lane);
         bias_step<KSH, OT>(acc, lds, lane);
         relu_to_bin(acc, bin);
@@ -77,7 +80,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
     {
         f32x16 acc[OT];
         zero_acc(acc);
-        if constexpr (TRAIN) gemm_steps_store<KSH, 0, OT, KSH, true>(acc, bin, lds, lane, quad_ptr(sv.h2, n, sc, h), 2 * n, mask_ptr(1));
+        if constexpr (TRAIN) gemm_steps_store<KSH, 0, OT, KSH, true>(acc, bin, lds, lane, quad_ptr(sv.h2, n, col, h), 2 * n, mask_ptr(1));
         else gemm_steps<KSH, 0, OT>(acc, bin, lds, lane);
         bias_step<KSH, OT>(acc, lds, lane);
         relu_to_bin(acc, bin);  // mlp_base out_activation = ReLU
@@ -92,7 +95,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
     {
         f32x16 acc[OT];
         zero_acc(acc);
-        if constexpr (TRAIN) gemm_steps_store<KSH, 0, OT, KSH, true>(acc, bin, lds, lane, quad_ptr(sv.h3, n, sc, h), 2 * n, mask_ptr(2));
+        if constexpr (TRAIN) gemm_steps_store<KSH, 0, OT, KSH, true>(acc, bin, lds, lane, quad_ptr(sv.h3, n, col, h), 2 * n, mask_ptr(2));
         else gemm_steps<KSH, 0, OT>(acc, bin, lds, lane);
         bias_step<HEAD_KS, OT>(acc, lds, lane);
         add_ray_bias(acc, hterm + (sc / samples_per_ray) * HID, h);
@@ -101,7 +104,7 @@ static __device__ __forceinline__ void mlp_forward_group(float *lds, size_t g, s
     if constexpr (TRAIN) {   // h4 and its mask leave under the next group's first GEMM (or with flush_carry)
 #pragma unroll
         for (int j = 0; j < KSH; ++j) cy->h4[j] = bin[j];
-        cy->p = quad_ptr(sv.h4, n, sc, h);
+        cy->p = quad_ptr(sv.h4, n, col, h);
         cy->m = mask_ptr(3);
     }
     rgb_head(lds + lfloats(HEAD_KS, OT), bin, h, s, ns, rgb);

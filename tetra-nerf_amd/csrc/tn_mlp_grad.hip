@@ -31,7 +31,6 @@ using namespace mlp;
 namespace {
 
 constexpr int DW_GRID = 512;          // two blocks per CU
-constexpr int LD = 36;                // LDS row stride (floats): 16-byte aligned, LD / 4 odd -> conflict-free b128 reads
 
 struct DwArgs {
     const float *A;        // [128, n]
@@ -42,142 +41,13 @@ struct DwArgs {
     float *part;           // [gridDim.x][128 * 32 NB + 256]: dW tile, row sums of A, (EXTRA) the d wd vector
 };
 
+// (the body is tn_mlp_dw_body.inc, text shared with the indexed head-layer GEMM of occupancy-culled training)
 template <int NBM, bool EXTRA>
 __global__ __launch_bounds__(256, 2) void k_dw_gemm(DwArgs g, size_t n, uint32_t slice) {
-    constexpr int NB = NBM + (EXTRA ? 1 : 0);
-    constexpr int RA = 128, RBM = 32 * NBM, RB = 32 * NB;
-    __shared__ __attribute__((aligned(16))) float As[RA * LD];
-    __shared__ __attribute__((aligned(16))) float Bs[RB * LD];
-    __shared__ __attribute__((aligned(16))) float dhs[32];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int col = tid & 31, row0 = tid >> 5;            // staging: sample of the step, quad (4 feature rows) within a pass of 8
-    const int cpos = (col & 1) * 16 + (col >> 1);         // even samples first, then the odd ones
-    const size_t s_begin = (size_t)blockIdx.x * slice;
-    const size_t s_end = s_begin + slice < n ? s_begin + slice : n;
-    float *part = g.part + (size_t)blockIdx.x * (RA * RB + 256);
-    constexpr int QA = RA / 32, QBM = RBM / 32;           // quads per thread: the tiles are [F / 4][n][4] (tn_mlp_common.h)
-
-    f32x16 acc[NB];
-#pragma unroll
-    for (int c = 0; c < NB; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-    float rsum = 0.f, dv = 0.f;
-    if (s_begin < n) {
-        float4 ra[QA], rb[QBM];
-        float re[EXTRA ? 4 : 1] = {}, rdh = 0.f;
-        uint32_t e_ray = 0, e_rem = 0;   // EXTRA: ray of this thread's sample, offset of the sample within it
-        const float4 *A4 = reinterpret_cast<const float4 *>(g.A), *B4 = reinterpret_cast<const float4 *>(g.B);
-        auto fetch = [&](size_t s0) {
-            const size_t sidx = s0 + col;
-            const bool in = sidx < s_end;
-            const size_t sc = in ? sidx : s_end - 1;      // clamped: loads stay unconditional, A (and dh) are zeroed
-#pragma unroll
-            for (int p = 0; p < QA; ++p) ra[p] = A4[(size_t)(8 * p + row0) * n + sc];
-#pragma unroll
-            for (int p = 0; p < QBM; ++p) rb[p] = B4[(size_t)(8 * p + row0) * n + sc];
-            if constexpr (EXTRA) {
-                // the encoding of the sample's ray: a thread's sample advances by 32 per step, so its ray changes every
-                // spr / 32 steps -- the four values stay in registers and are re-read only then (per step: one division and
-                // four gathers less; 0.87 -> 0.7x ms per 2.1 M samples, profiles/r04r_dw_ablate.txt).  Lanes beyond the
-                // slice keep what they have (their A rows are zero).
-                bool reload = false;
-                if (s0 == s_begin) {
-                    e_ray = (uint32_t)sc / g.spr;                 // n < 2^32 (checked by the launcher)
-                    e_rem = (uint32_t)sc - e_ray * g.spr;
-                    reload = true;
-                } else if (in) {
-                    e_rem += 32u;
-                    while (e_rem >= g.spr) { e_rem -= g.spr; ++e_ray; reload = true; }
-                }
-                if (reload) {
-                    const float *e = g.enc + (size_t)e_ray * ENC_PAD;
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const int j = 8 * p + row0;
-                        re[p] = j < ENC_PAD ? e[j < ENC_PAD ? j : 0] : 0.f;
-                    }
-                }
-                rdh = row0 == 0 ? g.dh[sc] : 0.f;
-                if (!in) rdh = 0.f;
-            }
-            if (!in) {
-#pragma unroll
-                for (int p = 0; p < QA; ++p) ra[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        };
-        auto put4 = [&](float *tile, int quad, const float4 &v) {
-            float *q = tile + (4 * quad) * LD + cpos;
-            q[0] = v.x; q[LD] = v.y; q[2 * LD] = v.z; q[3 * LD] = v.w;
-        };
-        fetch(s_begin);
-        const int m = lane & 31, kk = lane >> 5;
-        const float4 *arow = reinterpret_cast<const float4 *>(As + (32 * w + m) * LD + kk * 16);
-        const float4 *brow = reinterpret_cast<const float4 *>(Bs + m * LD + kk * 16);
-        const int vf = tid >> 1, vh = tid & 1;             // d wd: feature row, sample parity
-        for (size_t s0 = s_begin; s0 < s_end; s0 += 32) {
-            __syncthreads();   // the previous step's reads of the tiles are done
-#pragma unroll
-            for (int p = 0; p < QA; ++p) put4(As, 8 * p + row0, ra[p]);
-#pragma unroll
-            for (int p = 0; p < QBM; ++p) put4(Bs, 8 * p + row0, rb[p]);
-            if constexpr (EXTRA) {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) Bs[(RBM + 8 * p + row0) * LD + cpos] = re[p];
-                if (row0 == 0) dhs[cpos] = rdh;
-            }
-            __syncthreads();
-            if (s0 + 32 < s_end) fetch(s0 + 32);
-            float4 a4[4], b4[2][4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a4[q] = arow[q];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b4[0][q] = brow[q];
-#pragma unroll
-            for (int c = 0; c < NB; ++c) {
-                if (c + 1 < NB) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) b4[(c + 1) & 1][q] = brow[(c + 1) * 32 * LD / 4 + q];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 a = a4[q], b = b4[c & 1][q];
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[c], 0, 0, 0);
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[c], 0, 0, 0);
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[c], 0, 0, 0);
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[c], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) rsum += (a4[q].x + a4[q].y) + (a4[q].z + a4[q].w);
-            if (EXTRA) {
-                const float4 *hr = reinterpret_cast<const float4 *>(Bs + vf * LD + vh * 16);
-                const float4 *dr = reinterpret_cast<const float4 *>(dhs + vh * 16);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 x = hr[q], d = dr[q];
-                    dv += (x.x * d.x + x.y * d.y) + (x.z * d.z + x.w * d.w);
-                }
-            }
-        }
-    }
-    // partial sums of this block (zeros when the block had no samples: the reduction adds every slot)
-    const int hh = lane >> 5;
-#pragma unroll
-    for (int c = 0; c < NB; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            part[(size_t)(32 * w + acc_feature(r, hh)) * RB + 32 * c + (lane & 31)] = acc[c][r];
-    rsum += __shfl_xor(rsum, 32);
-    if (lane < 32) part[RA * RB + 32 * w + lane] = rsum;
-    if (EXTRA) {
-        dv += __shfl_xor(dv, 1);
-        if ((tid & 1) == 0) part[RA * RB + 128 + (tid >> 1)] = dv;
-    } else if (tid < 128) {
-        part[RA * RB + 128 + tid] = 0.f;
-    }
+    constexpr bool INDEXED = false;        // (the indexed form: tn_occupancy_dw.hip)
+    const uint32_t *const live = nullptr;
+    constexpr uint32_t num_rays = 0;
+#include "tn_mlp_dw_body.inc"
 }
 
 // out[map(i)] += sum over the blocks' slots, in a fixed order (consecutive threads read consecutive floats of a slot).  Layout of a slot: [128][RB] tile, [128] row sums, [128] vector.
@@ -305,25 +175,29 @@ Slicing slicing(size_t n, uint32_t unit) {
 }
 
 // x3: the GEMM in bf16x3 (k_dw_gemm_x3, tn_mlp_x3_dw.hip: the same grid, slices and slots); the reduction is the same
+// live (EXTRA only; nullable): the n columns are the slots of a list of samples of num_rays rays (tn_occupancy_dw.hip)
 template <int NBM, bool EXTRA>
-void run_dw(size_t n, const DwArgs &g, ReduceArgs r, bool x3, hipStream_t stream) {
+void run_dw(size_t n, const DwArgs &g, ReduceArgs r, bool x3, hipStream_t stream, const uint32_t *live = nullptr, uint32_t num_rays = 0) {
     const Slicing sl = slicing(n, 32);
-    if (x3) launch_dw_gemm_x3(NBM, EXTRA, sl.grid, DwGemmArgs{g.A, g.B, g.enc, g.dh, g.spr, g.part}, n, sl.slice, stream);
+    if (live) launch_dw_gemm_head_indexed(x3, sl.grid, DwGemmArgs{g.A, g.B, g.enc, g.dh, g.spr, g.part}, n, sl.slice, live, num_rays, stream);
+    else if (x3) launch_dw_gemm_x3(NBM, EXTRA, sl.grid, DwGemmArgs{g.A, g.B, g.enc, g.dh, g.spr, g.part}, n, sl.slice, stream);
     else hipLaunchKernelGGL((k_dw_gemm<NBM, EXTRA>), dim3(sl.grid), dim3(256), 0, stream, g, n, sl.slice);
     r.part = g.part; r.nslots = sl.grid; r.RBM = 32 * NBM; r.RB = 32 * (NBM + (EXTRA ? 1 : 0));
     const uint32_t count = 128 * r.RB + 256;
     hipLaunchKernelGGL(k_reduce_partials, dim3((count + 63) / 64), dim3(256), 0, stream, r);
 }
 
+// live (nullable): the buffers hold n compact columns, column i = sample live[i] of n_samples (occupancy-culled training)
 void param_grads(size_t n, uint32_t samples_per_ray, const float *dirs, const MlpPacks &w, const MlpBackwardBuffers &b,
-                 const MlpParamGrads &g, bool x3, hipStream_t stream) {
+                 const MlpParamGrads &g, bool x3, hipStream_t stream, const uint32_t *live = nullptr, size_t n_samples = 0) {
     if (n == 0) return;
-    if (n > 0xFFFFFFFFull) throw Error("param_grads: more than 2^32 samples per call");
-    launch_dir_encoding(n / samples_per_ray, dirs, w.enc, ENC_PAD, stream);
+    if (n > 0xFFFFFFFFull || n_samples > 0xFFFFFFFFull) throw Error("param_grads: more than 2^32 samples per call");
+    const size_t num_rays = (live ? n_samples : n) / samples_per_ray;
+    launch_dir_encoding(num_rays, dirs, w.enc, ENC_PAD, stream);
     float *part = w.grad_scratch;
     // mlp_head: [enc(27) | base(128)] -> 128, and the density head's weight vector
     run_dw<4, true>(n, DwArgs{b.d4, b.h3, w.enc, b.dhead, samples_per_ray, part},
-                    ReduceArgs{nullptr, 0, 0, 0, g.wh + ENC, ENC + HID, g.wh, ENC, g.bh, g.wd}, x3, stream);
+                    ReduceArgs{nullptr, 0, 0, 0, g.wh + ENC, ENC + HID, g.wh, ENC, g.bh, g.wd}, x3, stream, live, (uint32_t)num_rays);
     run_dw<4, false>(n, DwArgs{b.d3, b.h2, nullptr, nullptr, 0, part},
                      ReduceArgs{nullptr, 0, 0, 0, g.w3, HID, nullptr, 0, g.b3, nullptr}, x3, stream);
     run_dw<4, false>(n, DwArgs{b.d2, b.h1, nullptr, nullptr, 0, part},
@@ -347,6 +221,11 @@ void launch_mlp_param_grads(size_t n, uint32_t samples_per_ray, const float *dir
 void launch_mlp_param_grads_x3(size_t n, uint32_t samples_per_ray, const float *dirs, const MlpPacks &w, const MlpBackwardBuffers &b,
                                const MlpParamGrads &g, hipStream_t stream) {
     param_grads(n, samples_per_ray, dirs, w, b, g, true, stream);
+}
+
+void launch_mlp_param_grads_indexed(size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live, const float *dirs,
+                                    const MlpPacks &w, const MlpBackwardBuffers &b, const MlpParamGrads &g, int mode, hipStream_t stream) {
+    param_grads(n_live, samples_per_ray, dirs, w, b, g, mode != 0, stream, live, n_samples);
 }
 
 }  // namespace tn

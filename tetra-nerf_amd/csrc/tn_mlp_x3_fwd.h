@@ -165,7 +165,8 @@ static __device__ __forceinline__ void init_bias(f32x16 (&acc)[TILES], const uin
 // does (mlp::FwdCarry), they cost this kernel -- which has no register to spare: 256 VGPRs at 2 waves per SIMD -- 30 spilled
 // registers and measured 3 % SLOWER (1.83 against 1.78 ms at 2.1 M samples, alternating processes).  The arithmetic, and so sigma / rgb, are those of
 // TRAIN = false.
-// INDEXED: as in mlp::mlp_forward_group -- n counts the slots of the list `live`, slot i stands for sample live[i] < n_samples.
+// INDEXED: as in mlp::mlp_forward_group -- n counts the slots of the list `live`, slot i stands for sample live[i] < n_samples;
+// with TRAIN the saves go to the slot (n slots: the quad-major stride).
 template <bool GATHER, bool DENSITY_ONLY, bool TRAIN = false, bool INDEXED = false>
 static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_t n, uint32_t samples_per_ray, const float *__restrict__ feats,
                                                      const uint32_t *__restrict__ vi, const float *__restrict__ bc,
@@ -174,13 +175,14 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
                                                      const float *__restrict__ ray_bias, const mlp::FwdSave *sv = nullptr,
                                                      const uint32_t *__restrict__ live = nullptr, size_t n_samples = 0) {
     static_assert(!TRAIN || (GATHER && !DENSITY_ONLY), "the training forward is the gathering, full network");
-    static_assert(!INDEXED || (GATHER && !TRAIN), "the indexed forward is the gathering inference forward");
+    static_assert(!INDEXED || GATHER, "the indexed forward gathers its samples itself");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
     constexpr size_t GROUP = (X3_BLOCK / 64) * 32;
     const size_t slot = g * GROUP + (size_t)wave * 32 + (lane & 31);
     const size_t slotc = slot < n ? slot : n - 1;
     const mlp::IndexedSample ix = mlp::indexed_sample<INDEXED>(slot, slotc, n, live, n_samples);
     const size_t s = ix.s, sc = ix.sc, ns = ix.ns;
+    const size_t col = INDEXED ? slotc : sc;   // TRAIN: the column of the save buffers (INDEXED: the slot, n slots in all)
     float bin[KSH];
 
     // ---- layer 1: this lane supplies features 32h .. 32h+31 of its sample
@@ -194,11 +196,11 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
     {
         f32x16 acc[4];
         init_bias(acc, lds + wu4(4, 4), h);
-        if constexpr (TRAIN) x3_steps_store<4, 4, 4, false>(acc, lds, bin, lane, mlp::quad_ptr_x0(sv->x0, n, sc, h), n);
+        if constexpr (TRAIN) x3_steps_store<4, 4, 4, false>(acc, lds, bin, lane, mlp::quad_ptr_x0(sv->x0, n, col, h), n);
         else x3_steps<4, 4>(acc, lds, bin, lane);
         relu_to_bin(acc, bin);
     }
-    auto mask_ptr = [&](int layer) { return sv->masks + ((size_t)layer * n + sc) * 2 + h; };   // TRAIN only
+    auto mask_ptr = [&](int layer) { return sv->masks + ((size_t)layer * n + col) * 2 + h; };   // TRAIN only
     // ---- layers 2, 3
 #pragma unroll
     for (int l = 0; l < 2; ++l) {
@@ -207,7 +209,7 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
         stage_wait();
         f32x16 acc[4];
         init_bias(acc, lds + wu4(8, 4), h);
-        if constexpr (TRAIN) x3_steps_store<8, 4, 4, true>(acc, lds, bin, lane, mlp::quad_ptr(l == 0 ? sv->h1 : sv->h2, n, sc, h), 2 * n, mask_ptr(l));
+        if constexpr (TRAIN) x3_steps_store<8, 4, 4, true>(acc, lds, bin, lane, mlp::quad_ptr(l == 0 ? sv->h1 : sv->h2, n, col, h), 2 * n, mask_ptr(l));
         else x3_steps<8, 4>(acc, lds, bin, lane);
         relu_to_bin(acc, bin);
     }
@@ -230,13 +232,13 @@ static __device__ __forceinline__ void forward_group(uint4 *lds, size_t g, size_
             ev[8 * q + 4] = e1.x; ev[8 * q + 5] = e1.y; ev[8 * q + 6] = e1.z; ev[8 * q + 7] = e1.w;
         }
         x3_steps<2, 4>(acc, lds, ev, lane);
-        if constexpr (TRAIN) x3_steps_store<8, 4, 4, true>(acc, lds + wu4(2, 4), bin, lane, mlp::quad_ptr(sv->h3, n, sc, h), 2 * n, mask_ptr(2));
+        if constexpr (TRAIN) x3_steps_store<8, 4, 4, true>(acc, lds + wu4(2, 4), bin, lane, mlp::quad_ptr(sv->h3, n, col, h), 2 * n, mask_ptr(2));
         else x3_steps<8, 4>(acc, lds + wu4(2, 4), bin, lane);
         if (ray_bias) mlp::add_ray_bias(acc, ray_bias + (sc / samples_per_ray) * HID, h);   // (appearance embedding) wave-uniform test
         relu_to_bin(acc, bin);
     }
     if constexpr (TRAIN) {
-        mlp::store_bin(sv->h4, n, sc, bin, h);
+        mlp::store_bin(sv->h4, n, col, bin, h);
         *mask_ptr(3) = mlp::mask_of(bin);
     }
     mlp::rgb_head(reinterpret_cast<const float *>(lds + wu4(2, 4) + wu4(8, 4) + bu4(4)), bin, h, s, ns, rgb);

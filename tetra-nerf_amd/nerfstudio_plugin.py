@@ -42,8 +42,9 @@ origins / directions / vertices), `train_mlp_mode` ("bf16x3": the forward kernel
 ("bf16x3": the dX chain of the MLP adjoint, independent of the forward's mode), `train_dw_mode` ("bf16x3": the four
 weight-gradient GEMMs of the MLP adjoint, independent of both), `eval_mlp_mode` ("bf16x3" / "bf16"), and -- only for a model that
 has the reference's own `tetrahedra_occupancy` buffer (`use_occupancy_field=True`, model.py:98-99,256-265: registered there, never
-used) -- `occupancy_threshold` (evaluation renders skip the network in tetrahedra below it) and `occupancy_decay` (training
-batches update the buffer: max(decay occupancy, max density seen)).
+used) -- `occupancy_threshold` (evaluation renders skip the network in tetrahedra below it), `occupancy_decay` (training
+batches update the buffer: max(decay occupancy, max density seen)) and `occupancy_train_threshold` (training batches skip the
+network in tetrahedra below it, except every `occupancy_refresh_every`-th one, default 16, which runs unculled).
 
 nerfstudio is not installed in this environment: the adapter is duck-typed (it only touches the attribute names listed
 above) and is tested with stand-ins of nerfstudio's MLP / FieldHead / RayBundle (tests/golden/nerfstudio_standins.py).
@@ -275,6 +276,16 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
             # opt-in (no such field in the reference's config; the BUFFER is the reference's own, registered under
             # use_occupancy_field=True and left unused there): updated in place once per batch; training itself is not culled
             kw["occupancy"], kw["occupancy_decay"] = occupancy, float(decay)
+        train_threshold = getattr(model.config, "occupancy_train_threshold", None)
+        if occupancy is not None and train_threshold is not None:
+            # opt-in, a field of its own (`occupancy_threshold` stays what it was: evaluation only): training batches skip the network
+            # in tetrahedra below it (TetraRenderer.render_train: occupancy_threshold; one host synchronisation per culled batch).
+            # A culled tetrahedron contributes sigma = 0, so the update can only decay it: every occupancy_refresh_every-th training
+            # batch of the renderer (default 16; below 1: never) runs UNCULLED, which is what lets such a tetrahedron come back
+            every = int(getattr(model.config, "occupancy_refresh_every", 16))
+            batch = rd._tn_train_batches = getattr(rd, "_tn_train_batches", 0) + 1
+            if every < 1 or batch % every != 0:
+                kw["occupancy"], kw["occupancy_threshold"] = occupancy, float(train_threshold)
         return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
                                ray_head_bias=hb, **kw)
     kw = {}

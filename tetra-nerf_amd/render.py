@@ -482,6 +482,47 @@ class _FusedMlpFunction(torch.autograd.Function):
         return (None, grad_bary, grad_field, grad_dirs, None, d_head if ctx.has_bias else None, *grads, *((None,) * ctx.num_modes))
 
 
+class _FusedMlpCulledFunction(torch.autograd.Function):
+    """_FusedMlpFunction on the listed samples only (occupancy-culled training): forward = tn_mlp_forward_gather_train_indexed over
+    `live[:n_live]` (cpp.cull_samples' ascending list; n_live a host integer), which stores into `out` = (sigma [n], rgb [n, 3]) --
+    the buffers cull_samples zeroed at the culled samples -- and saves 2.3 KB per LISTED sample; backward = the same adjoint kernels
+    on compact columns (cpp.mlp_backward with an MlpSavedIndexed).  sigma = 0 and rgb = 0 are constants at the samples not listed:
+    no gradient reaches or leaves them.  `live`, `n_live`, `out` lead the arguments of _FusedMlpFunction."""
+
+    @staticmethod
+    def forward(ctx, live, n_live, out, vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray, ray_head_bias, *weights):
+        from . import tetranerf_cpp_extension as cpp
+
+        ctx.num_modes = len(weights) - 12
+        mode = weights[12] if ctx.num_modes >= 1 else "fp32"
+        ctx.adjoint_mode = weights[13] if ctx.num_modes >= 2 else "fp32"
+        ctx.dw_mode = weights[14] if ctx.num_modes >= 3 else "fp32"
+        weights = weights[:12]
+        ctx.has_bias = ray_head_bias is not None
+        sigma, rgb, saved = cpp.mlp_forward_gather_train_indexed(live, n_live, vertex_indices, barycentric_coordinates, field, dirs,
+                                                                 list(weights), int(samples_per_ray), ray_head_bias=ray_head_bias,
+                                                                 mode=mode, sigma=out[0], rgb=out[1])
+        saved.sigma = saved.rgb = None     # (no cycle through the node's own outputs: see _FusedMlpFunction)
+        ctx.save_for_backward(vertex_indices, barycentric_coordinates, field, dirs, sigma, rgb, *weights)
+        ctx.saved = saved
+        return sigma, rgb
+
+    @staticmethod
+    def backward(ctx, d_sigma, d_rgb):
+        # _FusedMlpFunction's backward on the compact saves: the same arguments behind the three leading ones
+        return (None, None, None) + _FusedMlpFunction.backward(_TrailingInputs(ctx, 3), d_sigma, d_rgb)
+
+
+class _TrailingInputs:
+    """an autograd context as a node whose inputs start `skip` positions later sees it"""
+
+    def __init__(self, ctx, skip):
+        self._ctx, self.needs_input_grad = ctx, tuple(ctx.needs_input_grad[skip:])
+
+    def __getattr__(self, name):
+        return getattr(self._ctx, name)
+
+
 class _FusedCompositeFunction(torch.autograd.Function):
     """get_weights + RGB / accumulation / median-depth renderers as one node (tn_composite / tn_composite_backward)."""
 
@@ -526,9 +567,11 @@ class TetraRenderer:
                  mlp_mode: str = "fp32", background=1.0, cache_field: bool = True, device_samplers: bool = True,
                  interpolate_values=None, sync_free_train: bool = True, sync_free_min_hits: float = None,
                  bin_rays: bool = False, train_mlp_mode: str = "fp32", train_adjoint_mode: str = "fp32",
-                 train_dw_mode: str = "fp32"):
+                 train_dw_mode: str = "fp32", train_occupancy_threshold: Optional[float] = None):
         from . import tetranerf_cpp_extension as cpp
 
+        # render_train(occupancy=...) without an occupancy_threshold of its own culls below this one (None: training is not culled)
+        self.train_occupancy_threshold = None if train_occupancy_threshold is None else float(train_occupancy_threshold)
         # incoherent batches (random pixels over many cameras): the tracer walks the rays in a locality order of its own
         # and still writes row r for ray r (trace_rays(bin_rays=True): the same rows, bit for bit)
         self.bin_rays = bool(bin_rays)
@@ -797,7 +840,8 @@ class TetraRenderer:
                      ray_head_bias: Optional[torch.Tensor] = None, position_gradients: bool = False,
                      vertices: Optional[torch.Tensor] = None, mlp_mode: Optional[str] = None,
                      adjoint_mode: Optional[str] = None, dw_mode: Optional[str] = None,
-                     occupancy: Optional[torch.Tensor] = None, occupancy_decay: Optional[float] = None) -> Dict[str, torch.Tensor]:
+                     occupancy: Optional[torch.Tensor] = None, occupancy_decay: Optional[float] = None,
+                     occupancy_threshold: Optional[float] = None) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
         (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches
         them), gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) --
@@ -828,14 +872,36 @@ class TetraRenderer:
         (tn_mlp_param_grads_ex); neither the outputs nor the field gradient depend on it.
         occupancy f32 [num_cells] + occupancy_decay (opt-in; both or neither, fused path): the per-tetrahedron occupancy field is
         UPDATED in place once per batch, after the forward, from the final pass's matched cells and the detached final densities
-        (cpp.occupancy_update: occupancy[t] = max(decay occupancy[t], max sigma in t)).  Training itself is not culled: the outputs
-        and the gradients of the batch do not depend on the field.  (The padded duplicate rays of the sync-free form repeat
-        samples of a real ray: harmless to a maximum.)"""
+        (cpp.occupancy_update: occupancy[t] = max(decay occupancy[t], max sigma in t)).  Without a threshold training itself is not
+        culled: the outputs and the gradients of the batch do not depend on the field.  (The padded duplicate rays of the sync-free
+        form repeat samples of a real ray: harmless to a maximum.)
+        occupancy + occupancy_threshold (opt-in; None: the renderer's train_occupancy_threshold; needs `occupancy`, and makes
+        occupancy_decay optional -- cull without update): CULLED training.  ONE definition: the unculled training forward with
+        sigma = 0 and rgb = 0 as CONSTANTS at every culled sample of both passes, the culled samples being those
+        cull_mask_statement(cells, occupancy, threshold) names -- render()'s rule.  No gradient reaches or leaves a culled sample;
+        the samplers, GradientScaler, the composite node, the sync-free padding, position gradients and the three arithmetic
+        switches are unchanged and see full-size [r, S] tensors.  Every live sample gets, bit for bit, the outputs and per-sample
+        gradients of the unculled kernels; only sums over samples (field gradient, weight gradients, per-ray head-bias sums) run
+        over a shorter list of terms.  Fused path: the coarse pass culls as render() does; the final pass runs cpp.cull_samples,
+        READS THE LIVE COUNT BACK TO THE HOST -- one host synchronisation per culled batch, which sizes the saves (2.3 KB per live
+        sample instead of per sample) and every adjoint launch -- and records a _FusedMlpCulledFunction; the update, when asked for,
+        runs after the forward as without a threshold.  fused=False with a threshold and no decay is the PyTorch statement
+        (torch.where on the mask in both passes): the oracle of the fused path.  A culled tetrahedron contributes sigma = 0, so
+        an update can only decay it: a caller that wants it to come back runs some batches unculled
+        (nerfstudio_plugin: occupancy_refresh_every).
+        capture additionally receives cell_indices and, with a threshold, culled [r, S]."""
         cpp, S = self.cpp, self.S
-        if (occupancy is None) != (occupancy_decay is None):
-            raise RuntimeError("occupancy and occupancy_decay go together: pass both or neither")
-        if occupancy is not None and not fused:
+        thr = occupancy_threshold
+        if thr is None and occupancy is not None:
+            thr = self.train_occupancy_threshold
+        if thr is not None and occupancy is None:
+            raise RuntimeError("occupancy_threshold needs the occupancy field it is compared with: pass occupancy=")
+        if (occupancy is None) != (occupancy_decay is None) and thr is None:
+            raise RuntimeError("occupancy and occupancy_decay go together: pass both or neither (occupancy with an "
+                               "occupancy_threshold alone culls without updating)")
+        if occupancy_decay is not None and not fused:
             raise RuntimeError("the occupancy update is a kernel of the fused path (fused=True); its statement is occupancy_update_statement")
+        occ = None if thr is None else (occupancy.detach(), float(thr))
         mode = self.train_mlp_mode if mlp_mode is None else mlp_mode
         cpp._mode(mode, inference=False)
         amode = self.train_adjoint_mode if adjoint_mode is None else adjoint_mode
@@ -933,9 +999,13 @@ class TetraRenderer:
             def weights_torch(traced, e):       # model.py:577-582 in PyTorch
                 gather = self._interpolate_values or cpp.interpolate_values
                 feats_c = gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field)
-                return ray_weights(coarse_sigma(self.mlp, feats_c), e)
+                sigma_c = coarse_sigma(self.mlp, feats_c)
+                if occ is not None:
+                    sigma_c = torch.where(cull_mask_statement(traced["cell_indices"], *occ), torch.zeros_like(sigma_c), sigma_c)
+                return ray_weights(sigma_c, e)
 
-            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, pdf, coarse_weights=None if fused else weights_torch)
+            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, pdf, coarse_weights=None if fused else weights_torch,
+                                               occ=occ if fused else None)
             S = edges.shape[1] - 1
         dirs = directions[idx].contiguous()      # (a differentiable index: the view term of position_gradients)
         # per-ray bias of the head layer (appearance embedding; fused path only): differentiable w.r.t. the caller's tensor
@@ -954,8 +1024,30 @@ class TetraRenderer:
                 capture["barycentric_positions"] = bc
         if capture is not None:   # the (non-differentiable) sample placement, for tests that restate the rest in float64
             capture.update(idx=idx, vertex_indices=vi, barycentric_coordinates=traced["barycentric_coordinates"], edges=edges, dirs=dirs,
-                           near=near_r, far=far_r, samples_per_ray=S)
-        if record:
+                           near=near_r, far=far_r, samples_per_ray=S, cell_indices=traced["cell_indices"])
+            if occ is not None:
+                capture["culled"] = cull_mask_statement(traced["cell_indices"], *occ)
+        if record and occ is not None:
+            # culled: list the live samples (the zeros of the others are written here), read their number back -- the one host
+            # synchronisation of a culled batch: it sizes the saves and the adjoint launches -- and run the node on the list;
+            # lists beyond train_node_samples go through several nodes, one per range of SLOTS (slots are independent), each with
+            # output buffers of its own that are zero wherever it stores nothing: their sum is exact (a softplus / sigmoid output
+            # is never -0, the one value x + 0 would change); n_nodes full-size buffers, for the rare list beyond 2^22 samples
+            n = r * S
+            sigma = cpp._empty((n,), dtype=torch.float32, device=dev)
+            col = cpp._empty((n, 3), dtype=torch.float32, device=dev)
+            live, live_count = cpp.cull_samples(traced["cell_indices"], occ[0], occ[1], sigma, col, samples_per_ray=S)
+            n_live = int(live_count.item())
+            per_node = max(1, int(self.train_node_samples))
+            if n_live > per_node:     # (cull_samples left the live positions unwritten: the first range needs zeros at the others')
+                sigma, col = torch.zeros_like(sigma), torch.zeros_like(col)
+            sigma, col = _FusedMlpCulledFunction.apply(live, min(n_live, per_node), (sigma, col), vi, bc, self.field, dirs, S, hb, *w, *modes)
+            for a in range(per_node, n_live, per_node):
+                part = _FusedMlpCulledFunction.apply(live[a:], min(n_live - a, per_node), (torch.zeros_like(sigma), torch.zeros_like(col)),
+                                                     vi, bc, self.field, dirs, S, hb, *w, *modes)
+                sigma, col = sigma + part[0], col + part[1]
+            sigma, col = sigma.view(-1, S), col.view(-1, S, 3)
+        elif record:
             # the node keeps 2.3 KB per sample from forward to backward (and its backward writes as much again): batches
             # beyond 2^22 samples (nerfstudio trains on 4096 rays) go through several nodes, one per block of rays
             rays_per_node = max(1, int(self.train_node_samples) // S)
@@ -968,7 +1060,7 @@ class TetraRenderer:
                 sigma, col = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
             sigma, col = sigma.view(-1, S), col.view(-1, S, 3)
         elif fused:               # no graph: the plain forward kernel, nothing saved
-            sigma, col = self._final_forward(vi, bc, edges, dirs, w, mode, hb)
+            sigma, col = self._final_forward(vi, bc, edges, dirs, w, mode, hb, occ=occ, traced=traced)
         else:
             interpolate_values = self._interpolate_values
             if interpolate_values is None:
@@ -977,7 +1069,11 @@ class TetraRenderer:
             feats = interpolate_values(vi, bc, self.field)
             sg, col = self.mlp(feats, dirs[:, None, :].expand(-1, S, -1))
             sigma = sg[..., 0]
-        if occupancy is not None:
+            if occ is not None:      # the statement of culled training: zeros as constants at the culled samples
+                culled = cull_mask_statement(traced["cell_indices"], *occ)
+                sigma = torch.where(culled, torch.zeros_like(sigma), sigma)
+                col = torch.where(culled[..., None], torch.zeros_like(col), col)
+        if occupancy_decay is not None:
             with torch.no_grad():
                 cpp.occupancy_update(occupancy, traced["cell_indices"], sigma.detach().contiguous(), occupancy_decay)
         if gradient_scaling and torch.is_grad_enabled():

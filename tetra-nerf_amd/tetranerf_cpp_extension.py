@@ -1133,6 +1133,77 @@ def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dir
     return sv.sigma, sv.rgb, sv
 
 
+class MlpSavedIndexed(MlpSaved):
+    """What mlp_forward_gather_train_indexed leaves for mlp_backward: MlpSaved with COMPACT tensors -- n = n_live columns, column i
+    belongs to sample live[i] of the n_samples samples of the call (S per ray)."""
+    __slots__ = ("n_samples", "live")
+
+
+def _check_live_list(live, n_live, dev):
+    _check_input(live, "live")
+    _check(live.dtype == torch.int32 and live.device == dev, "live must be an int32 tensor on the field's device")
+    _check(0 <= n_live <= live.numel(), "n_live must be a host integer in [0, live.numel()]")
+
+
+def compact_rows(src, live, n_live):
+    """dst[i] = src[live[i]] for i < n_live (tn_compact_rows): src a contiguous 32-bit tensor [n] / [n, 3] / [n, 4] (any leading
+    shape), live i32 ascending list of rows (cull_samples), n_live a host integer.  Returns [n_live] / [n_live, 3] / [n_live, 4].
+    Every listed row must exist in src: the kernel has no bound to check against."""
+    _check_input(src, "src")
+    _check(src.element_size() == 4, "compact_rows: 32-bit elements")
+    W = 1 if src.dim() <= 1 else src.size(-1)
+    _check(W in (1, 3, 4), "compact_rows: rows of 1, 3 or 4 elements")
+    n_live = int(n_live)
+    _check_live_list(live, n_live, src.device)
+    dst = _empty((n_live,) if src.dim() <= 1 else (n_live, W), dtype=src.dtype, device=src.device)
+    with _on(src.device):
+        _lib.check(_lib.load().tn_compact_rows(W, n_live, _ptr(live), _ptr(src), _ptr(dst), _stream(src.device)))
+    return dst
+
+
+def mlp_forward_gather_train_indexed(live, n_live, vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray,
+                                     ray_head_bias=None, mode="fp32", sigma=None, rgb=None):
+    """mlp_forward_gather_train over the listed samples only (tn_mlp_forward_gather_train_indexed): slot i < n_live computes sample
+    live[i] -- gathers there, takes the head term of that sample's ray, stores sigma / rgb there -- and saves at column i of
+    COMPACT buffers (2.3 KB per LISTED sample).  live i32 (ascending: cull_samples), n_live a HOST integer (the caller has read
+    cull_samples' live_count back); all other arguments as mlp_forward_gather_train over all n samples.  sigma f32 [n] / rgb f32
+    [n, 3]: the tensors to store into (what cull_samples zeroed at the culled samples); positions that are not listed are NOT
+    written -- without them fresh (unwritten) tensors are returned.  For every listed sample the outputs and the saved column
+    are bit for bit mlp_forward_gather_train's in the same mode.  Returns (sigma, rgb, saved: MlpSavedIndexed) for mlp_backward.
+    The forward itself tolerates a list entry >= n (it stores no output for it); mlp_backward does NOT: it compacts rows by the
+    list without a bound (tn_compact_rows), so only a list whose every entry is a sample -- what cull_samples writes -- may go on
+    to the backward."""
+    mode = _mode(mode, inference=False)
+    _check_input(dirs, "dirs")
+    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
+    dev = field.device
+    n_live = int(n_live)
+    _check_live_list(live, n_live, dev)
+    m = fused_mlp(weights)
+    field_vm = field_vertex_major(field)
+    if sigma is None:
+        sigma = _empty((n,), dtype=torch.float32, device=dev)
+    if rgb is None:
+        rgb = _empty((n, 3), dtype=torch.float32, device=dev)
+    for x, name, k in ((sigma, "sigma", n), (rgb, "rgb", 3 * n)):
+        _check_input(x, name)
+        _check(x.dtype == torch.float32 and x.numel() == k and x.device == dev, f"{name} must be f32 with {k} elements")
+    sv = MlpSavedIndexed()
+    sv.n, sv.S, sv.n_samples, sv.live = n_live, S, n, live
+    sv.sigma, sv.rgb = sigma, rgb
+    sv.acts = _empty((64 + 4 * 128, n_live), dtype=torch.float32, device=dev)
+    sv.masks = _empty((4, n_live, 2), dtype=torch.int64, device=dev)
+    a = sv.acts
+    bs = _MlpBackwardBuffers(a[0:64].data_ptr(), a[64:192].data_ptr(), a[192:320].data_ptr(), a[320:448].data_ptr(),
+                             a[448:576].data_ptr(), sv.masks.data_ptr(), None, None, None, None, None, None)
+    with _on(dev):
+        _lib.check(_lib.load().tn_mlp_forward_gather_train_indexed(
+            m.handle, n_live, n, S, _ptr(live), _ptr(vertex_indices), _ptr(barycentric_coordinates), _ptr(field_vm),
+            _ptr(dirs.contiguous()), mode, _ptr(sigma), _ptr(rgb), C.byref(bs), _ptr(_ray_bias(ray_head_bias, n // S, dev)),
+            _stream(dev)))
+    return sigma, rgb, sv
+
+
 class MlpChain:
     """What the dX chain of one mlp_backward call produced (return_chain=True; for tests that follow the chain layer by layer):
     d1..d4 [128, n] slices of quad-major memory ([F/4][n][4], like MlpSaved.acts), dhead [4, n] (d sigma_raw, d rgb_raw) and
@@ -1160,21 +1231,35 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
     dw_mode: arithmetic of the four weight-gradient GEMMs, independent of the other two.  "fp32" (default): tn_mlp_param_grads.
     "bf16x3" (tn_mlp_param_grads_ex, mode 1): both streamed operands split into three bf16 pieces as they are staged, six
     products per multiply on the bf16 matrix cores, fp32 accumulation; the bias gradients, d wd and the rgb head stay fp32;
-    still without atomics, bit-reproducible.  grad_field does not depend on it.  "bf16" is not a training arithmetic."""
+    still without atomics, bit-reproducible.  grad_field does not depend on it.  "bf16" is not a training arithmetic.
+    saved an MlpSavedIndexed (mlp_forward_gather_train_indexed; occupancy-culled training): every argument still covers all
+    n_samples samples of the call.  The rows of the listed samples are compacted (tn_compact_rows), the dX chain and the gather
+    adjoints run unchanged on n_live columns, the parameter gradients and the per-ray sums through their indexed entries; the sums
+    run over the listed samples only, grad_bary is [n_samples, 3] with zeros at the samples not listed, the per-ray sums cover all
+    rays (zeros for a ray without a listed sample), dx0 and the MlpChain stay compact (slot i = sample live[i]).  Every entry
+    of the list must be a sample < n_samples (cull_samples' lists are): tn_compact_rows reads src[live[i]] without a bound."""
     amode = _mode(adjoint_mode, inference=False)
     wmode = _mode(dw_mode, inference=False)
     mh = fused_mlp(weights)
     keep = [w.detach() for w in weights]
     n, S = saved.n, saved.S
-    _check(vertex_indices.numel() == 4 * n, "vertex_indices do not belong to the saved forward pass")
-    _check(d_sigma.numel() == n and d_rgb.numel() == 3 * n, "d_sigma / d_rgb must have n / 3n elements")
+    # an MlpSavedIndexed (mlp_forward_gather_train_indexed): all arguments cover the nfull samples of the call; the rows of the
+    # n listed ones are compacted first, the per-sample kernels then run unchanged on n columns
+    live = getattr(saved, "live", None)
+    nfull = n if live is None else saved.n_samples
+    _check(vertex_indices.numel() == 4 * nfull, "vertex_indices do not belong to the saved forward pass")
+    _check(d_sigma.numel() == nfull and d_rgb.numel() == 3 * nfull, "d_sigma / d_rgb must have n / 3n elements")
     dev = field.device
     V = field.size(1)
-    vi = vertex_indices.reshape(n, 4)
-    bc = barycentric_coordinates.reshape(n, 3)
-    d_sigma = d_sigma.reshape(n).contiguous().float()
-    d_rgb = d_rgb.reshape(n, 3).contiguous().float()
+    vi = vertex_indices.reshape(nfull, 4)
+    bc = barycentric_coordinates.reshape(nfull, 3)
+    d_sigma = d_sigma.reshape(nfull).contiguous().float()
+    d_rgb = d_rgb.reshape(nfull, 3).contiguous().float()
     dirs = dirs.contiguous()
+    if live is not None:
+        vi, bc = compact_rows(vi.contiguous(), live, n), compact_rows(bc.contiguous(), live, n)
+        sigma, rgb = compact_rows(sigma.reshape(nfull).contiguous(), live, n), compact_rows(rgb.reshape(nfull, 3).contiguous(), live, n)
+        d_sigma, d_rgb = compact_rows(d_sigma, live, n), compact_rows(d_rgb, live, n)
     lib = _lib.load()
     # the twelve gradients as views of ONE zero-filled buffer (tn_mlp_param_grads accumulates): one fill launch, not twelve
     sizes = [w.numel() for w in keep]
@@ -1192,25 +1277,40 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
                              a[448:576].data_ptr(), saved.masks.data_ptr(), buf[0:128].data_ptr(), buf[128:256].data_ptr(),
                              buf[256:384].data_ptr(), buf[384:512].data_ptr(), buf[512:516].data_ptr(), rows.data_ptr())
     stream = _stream(dev)
+    some = n > 0 or live is None      # (an empty list: nothing to launch, every sum is empty)
     with _on(dev):
         head = (mh.handle, n, _ptr(sigma.contiguous()), _ptr(rgb.contiguous()), _ptr(d_sigma), _ptr(d_rgb), C.byref(bs))
-        if amode == 0:      # the default goes through the entry it always went through
+        if not some:
+            pass
+        elif amode == 0:    # the default goes through the entry it always went through
             _lib.check(lib.tn_mlp_backward(*head, stream))
         else:
             _lib.check(lib.tn_mlp_backward_ex(*head, amode, stream))
-        if wmode == 0:      # the default goes through the entry it always went through
+        if live is not None:
+            _lib.check(lib.tn_mlp_param_grads_indexed(mh.handle, n, nfull, S, _ptr(live), _ptr(dirs), C.byref(bs), C.byref(gs), wmode,
+                                                      stream))
+        elif wmode == 0:    # the default goes through the entry it always went through
             _lib.check(lib.tn_mlp_param_grads(mh.handle, n, S, _ptr(dirs), C.byref(bs), C.byref(gs), stream))
         else:
             _lib.check(lib.tn_mlp_param_grads_ex(mh.handle, n, S, _ptr(dirs), C.byref(bs), C.byref(gs), wmode, stream))
         d_ray_bias = None
         if want_ray_head_grad:      # gradient of the per-ray head bias: per-ray sums of d4
-            d_ray_bias = _empty((n // S, 128), dtype=torch.float32, device=dev)
-            _lib.check(lib.tn_mlp_ray_head_grad(n, S, C.byref(bs), _ptr(d_ray_bias), stream))
+            d_ray_bias = _empty((nfull // S, 128), dtype=torch.float32, device=dev)
+            if live is not None:
+                _lib.check(lib.tn_mlp_ray_head_grad_indexed(n, nfull, S, _ptr(live), C.byref(bs), _ptr(d_ray_bias), stream))
+            else:
+                _lib.check(lib.tn_mlp_ray_head_grad(n, S, C.byref(bs), _ptr(d_ray_bias), stream))
         # gradient of the gathered features -> field (vertex-major accumulation)
-        _gather_adjoint_vm(lib, 4, V, n, 64, vi, bc, rows, grad_vm, stream)
+        if some:
+            _gather_adjoint_vm(lib, 4, V, n, 64, vi, bc, rows, grad_vm, stream)
         grad_field = _empty((64, V), dtype=torch.float32, device=dev)
         _lib.check(lib.tn_transpose_f32(V, 64, _ptr(grad_vm), _ptr(grad_field), stream))
-        grad_bary = _bary_adjoint_vm(lib, 4, n, 64, vi, rows, field_vertex_major(field), stream) if want_bary_grad else None
+        grad_bary = None
+        if want_bary_grad and some:
+            grad_bary = _bary_adjoint_vm(lib, 4, n, 64, vi, rows, field_vertex_major(field), stream)
+        if want_bary_grad and live is not None:      # rows of the listed samples -> [nfull, 3], zeros at the culled ones
+            full = torch.zeros((nfull, 3), dtype=torch.float32, device=dev)
+            grad_bary = full if n == 0 else full.index_copy_(0, live[:n].long(), grad_bary.view(n, 3))
     res = (grad_field, grads)
     if want_ray_head_grad:
         res += (d_ray_bias,)
