@@ -66,6 +66,24 @@ int tn_tracer_destroy(tn_tracer_t tracer);
 int tn_load_tetrahedra(tn_tracer_t tracer, size_t num_vertices, size_t num_cells,
                        const float *xyz, const uint32_t *cells, void *stream);
 
+/* Refit (no reference counterpart: the reference reloads).  The vertices of the loaded mesh moved and `cells` did not: everything
+ * tn_load_tetrahedra built that holds positions is recomputed in place from xyz (csrc/tn_refit.hip) -- the position and the
+ * thin-neighbourhood exponent of the 4T walk records, the face BVH's boxes and leaf triangles over the kept tree, the hull tree,
+ * max |coordinate| and the mesh box of binned calls -- and everything that depends on `cells` alone is kept (face table, Morton
+ * order of the records, adjacency codes, shape and face order of the BVH).  Afterwards every query answers as a tracer freshly
+ * loaded on xyz does, row for row; only the ORDER of records and BVH leaves stays that of the vertices of the load, so locality
+ * degrades with large deformation: reload every so often.
+ * xyz  f32 [V,3] device: the buffer given to tn_load_tetrahedra, modified in place, or another one; borrowed from now on.
+ * Needs a tracer loaded with option "refit_tables" = 1 by the device build.  Blocking, like the load (two small read-backs);
+ * launches on `stream`; allocates nothing on the device.  The call makes no promise the load does not make: a move after which
+ * tetrahedra overlap gives a mesh the walk's certification does not cover, refitted or freshly loaded.
+ * Errors (nothing is touched): tracer not loaded; num_vertices != the loaded V; xyz null; loaded without "refit_tables";
+ * loaded by the host build ("gpu_build" = 0). */
+int tn_update_vertices(tn_tracer_t tracer, size_t num_vertices, const float *xyz, void *stream);
+
+/* device bytes the loaded mesh keeps for tn_update_vertices beyond its tables (0: loaded without "refit_tables", or not loaded) */
+size_t tn_refit_table_bytes(tn_tracer_t tracer);
+
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);
 
@@ -363,6 +381,8 @@ int tn_fill_rows(size_t num_rays, uint32_t max_ray_triangles, uint32_t first_slo
  *             0 (default) = the overlapped four-stream schedule
  *   "writer_table"  0 (default) = the segment writer's record table by mesh size (one record per (tet, entry face) below
  *             500k tets, one per tet above), 1 / 2 force either (applies at the next tn_load_tetrahedra; tests, A/B)
+ *   "refit_tables"  0 (default) / 1 = the next tn_load_tetrahedra (device build) keeps what tn_update_vertices needs
+ *             (tn_refit_table_bytes; 26 .. 35 B per tet); 0 = a load launches and keeps exactly what it does without the option
  * Unknown names are an error. */
 int tn_set_option(tn_tracer_t tracer, const char *name, int value);
 

@@ -112,8 +112,8 @@ def sample_positions_grad(barycentrics, vertex_indices, vertices, origins, direc
         vertices [V,3] receive -w_k m (w = (1 - sum b, b0, b1, b2)),  origins [R,3] sum_s m,  directions [R,3] sum_s t_s m
     with t = `distances` f32 [R, S], the sample distances handed to find_visited_cells.  One HIP kernel
     (tn_sample_positions_backward); the role of add_barycentrics_grad for whole ray batches.  Tet membership, t, near / far
-    and the sampler draws are CONSTANTS of the gradient; after the vertices moved the tracer must be reloaded
-    (load_tetrahedra).  Under cpp.deterministic_gradients() the vertex sum is taken without float atomics."""
+    and the sampler draws are CONSTANTS of the gradient; after the vertices moved the tracer must follow them
+    (TetrahedraTracer.update_vertices while the cells stay, load_tetrahedra otherwise).  Under cpp.deterministic_gradients() the vertex sum is taken without float atomics."""
     return _SamplePositionsGrad.apply(barycentrics, vertex_indices, vertices, origins, directions, distances)
 
 

@@ -30,6 +30,7 @@ SYMBOLS = (
     "tn_interpolate_values_backward_bary_vm", "tn_sample_positions_backward",
     "tn_occupancy_update", "tn_cull_samples", "tn_mlp_forward_gather_indexed",
     "tn_mlp_forward_gather_train_indexed", "tn_mlp_param_grads_indexed", "tn_mlp_ray_head_grad_indexed", "tn_compact_rows",
+    "tn_update_vertices", "tn_refit_table_bytes",
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -60,6 +61,9 @@ def load():
     lib.tn_tracer_create.argtypes = [i32, C.POINTER(vp)]
     lib.tn_tracer_destroy.argtypes = [vp]
     lib.tn_load_tetrahedra.argtypes = [vp, sz, sz, vp, vp, vp]
+    lib.tn_update_vertices.argtypes = [vp, sz, vp, vp]
+    lib.tn_refit_table_bytes.restype = sz
+    lib.tn_refit_table_bytes.argtypes = [vp]
     lib.tn_num_faces.restype = sz
     lib.tn_num_faces.argtypes = [vp]
     lib.tn_get_faces.argtypes = [vp, vp, vp]
@@ -118,7 +122,7 @@ def load():
     lib.tn_compact_rows.argtypes = [u32, sz, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
-        if fn.restype is C.c_int and name not in ("tn_last_error", "tn_version", "tn_abi_version", "tn_num_faces"):
+        if fn.restype is C.c_int and name not in ("tn_last_error", "tn_version", "tn_abi_version", "tn_num_faces", "tn_refit_table_bytes"):
             fn.restype = C.c_int
     _lib = lib
     return lib

@@ -37,6 +37,8 @@ struct tn_tracer {
         tn::DevBuf<tn::WalkTet> tets;
         tn::DevBuf<tn::WalkFid> fidt;
         tn::DevBuf<float> hull_nodes, hull_tris;
+        tn::RefitTables refit;               // option "refit_tables": what tn_update_vertices needs beyond the tables above, else empty
+        bool device_built = false;
     } mesh;
 
     // ---- exactly what tn_set_option writes.  include/tetranerf_hip.h documents the values; the measurements that chose
@@ -45,6 +47,7 @@ struct tn_tracer {
         bool gpu_build = true;               // structures built on the device (tn_build.hip); false: the host build (tn_mesh.cpp)
         unsigned leaf_width = 16;            // faces per BVH leaf block (applies at the next load_tetrahedra)
         int writer_table = 0;                // 0: by mesh size (WALK_TET_MIN_TETS), 1: per (tet, entry face), 2: per tet
+        bool refit_tables = false;           // the next device build keeps tn::RefitTables (tn_update_vertices)
         int use_walk = 1;                    // 0 never, 1 from walk_min_rays rays on, 2 always
         size_t walk_min_rays = 12288;        // crossover of BVH path and walk on 100k ... 1M tets (r02t_crossover.txt, r06y_batch_crossover.txt)
         bool walk_min_auto = true;           // ... and by mesh size above that until the option is set (TraceCall::walk_min_rays)
@@ -506,12 +509,15 @@ int tn_load_tetrahedra(tn_tracer_t tracer, size_t V, size_t T, const float *xyz,
         tn_tracer::Mesh &b = t->mesh;
         b.loaded = false;
         b.host.faces.clear(); b.host.face_tets.clear();
+        b.refit.release();
+        b.device_built = t->opt.gpu_build && T > 0;
         BuildCounts n;
-        if (t->opt.gpu_build && T > 0) {
+        if (b.device_built) {
             // everything is built on the device from the caller's buffers (tn_build.hip)
             tn::BuildInfo bi;
             tn::device_build(V, T, xyz, cells, stream,
-                             tn::BuildTargets{b.faces, b.face_tets, b.vars, b.hull_nodes, b.hull_tris, b.bvh}, bi, t->opt.leaf_width);
+                             tn::BuildTargets{b.faces, b.face_tets, b.vars, b.hull_nodes, b.hull_tris, b.bvh}, bi, t->opt.leaf_width,
+                             t->opt.refit_tables ? &b.refit : nullptr);
             check_bvh_depth(bi.max_stack);
             b.host.scene_max = bi.scene_max;
             b.bvh_max_stack = bi.max_stack;
@@ -544,6 +550,39 @@ int tn_load_tetrahedra(tn_tracer_t tracer, size_t V, size_t T, const float *xyz,
         tn::mesh_box(V, T, xyz, cells, m.box_lo, m.box_hi, stream);   // one kernel for both builds: the same six numbers
         b.loaded = true;
     });
+}
+
+int tn_update_vertices(tn_tracer_t tracer, size_t V, const float *xyz, void *stream_) {
+    return guarded([&] {
+        tn_tracer *t = checked(tracer);
+        std::lock_guard<std::mutex> lock(t->mu);
+        tn_tracer::Mesh &b = t->mesh;
+        if (!b.loaded) throw tn::Error("tn_update_vertices: no mesh is loaded; call load_tetrahedra first");
+        if (!b.device_built)
+            throw tn::Error("tn_update_vertices: the mesh was built on the host (option \"gpu_build\" = 0); the refit is part of the "
+                            "device build: set \"gpu_build\" = 1 and load again, or reload after every move");
+        if (!b.refit.valid)
+            throw tn::Error("tn_update_vertices: the mesh was loaded without the refit tables; set option \"refit_tables\" = 1 "
+                            "(Python: load_tetrahedra(..., refittable=True)) and load again");
+        if (V != b.view.V)
+            throw tn::Error("tn_update_vertices: " + std::to_string(V) + " vertices given, the loaded mesh has " +
+                            std::to_string(b.view.V) + "; a mesh with other vertices or cells needs load_tetrahedra");
+        if (!xyz) throw tn::Error("tn_update_vertices: xyz must not be null");
+        DeviceGuard g(t->device);
+        hipStream_t stream = (hipStream_t)stream_;
+        tn::DeviceMesh &m = b.view;
+        float smax = 0.f;
+        tn::device_refit(V, m.T, xyz, m.cells, stream, tn::RefitTargets{b.hot.p, b.faces.p, b.hull_nodes, b.hull_tris, b.bvh}, b.refit,
+                         smax, m.box_lo, m.box_hi);
+        // what is cached by value: max |coordinate| (the BVH view every parameter block copies) and the key box of binned calls
+        b.host.scene_max = smax;
+        m.bvh = b.bvh.view;
+        m.xyz = xyz;
+    });
+}
+
+size_t tn_refit_table_bytes(tn_tracer_t tracer) {
+    return tracer && tracer->mesh.loaded && tracer->mesh.refit.valid ? tracer->mesh.refit.bytes() : 0;
 }
 
 size_t tn_num_faces(tn_tracer_t tracer) { return tracer && tracer->mesh.loaded ? tracer->mesh.view.F : 0; }
@@ -854,6 +893,7 @@ int tn_set_option(tn_tracer_t tracer, const char *name, int value) {
             o.lds_cap = (unsigned)value;
         }
         else if (k == "writer_table") o.writer_table = value;   // applies at the next load_tetrahedra
+        else if (k == "refit_tables") o.refit_tables = value != 0;   // applies at the next load_tetrahedra
         else if (k == "cert_ends") { if (value < 0 || value > 3) throw tn::Error("cert_ends must be 0 .. 3"); o.cert_ends = value; }
         else if (k == "verify_inject") o.verify_inject = value != 0;
         else if (k == "literal_sort_passes") o.literal_sort_passes = value < 0 ? 0u : (unsigned)value;

@@ -19,11 +19,52 @@ struct BuildInfo {
     uint32_t F = 0, n_hull = 0, n_hull_nodes = 0, max_stack = 1;
     float scene_max = 0.f;
 };
+// What a load with the tracer option "refit_tables" keeps for tn_update_vertices (tn_refit.hip): the part of the build that is
+// a function of `cells` alone and that the tables the kernels read do not already hold, and the refit's two work arrays (so a
+// refit allocates nothing on the device).  Empty after a load without the option.
+constexpr size_t REFIT_STAT_WORDS = 7 * 32;   // seven reduced numbers, one 128-byte line each (tn_refit.hip)
+struct RefitTables {
+    DevBuf<uint32_t> order;        // [T]  tet of walk record r (inverse of rec_of_tet)
+    DevBuf<uint32_t> hull_info;    // [n_hull][12]  core::hull_face_info: words 3 / 7 / 11 = face id, tet record, local face
+    DevBuf<core::BinNode> bn;      // binary tree over the faces (shape: build_bin_topology) ...
+    DevBuf<uint32_t> face_order;   // [F]  ... the face order its (first, count) ranges index ...
+    DevBuf<uint32_t> leaf_nodes;   // [n_leaves]  ... its leaves by leaf index ...
+    DevBuf<uint32_t> wide_sub;     // [n_wide]  ... and the root of the binary subtree each 64-wide node was collapsed from
+    std::vector<uint32_t> level_start;   // binary nodes of level l: [level_start[l], level_start[l + 1])
+    DevBuf<float> node_lo, node_hi;      // work: [nodes][3] boxes of the binary nodes
+    DevBuf<uint32_t> vmin;               // work: [V + REFIT_STAT_WORDS] star minima of the thin pass, then max |coordinate| and the mesh box
+    bool valid = false;
+    size_t bytes() const {
+        return 4 * (order.n + hull_info.n + face_order.n + leaf_nodes.n + wide_sub.n + node_lo.n + node_hi.n + vmin.n) +
+               sizeof(core::BinNode) * bn.n;
+    }
+    void release() {
+        order.release(); hull_info.release(); bn.release(); face_order.release(); leaf_nodes.release(); wide_sub.release();
+        node_lo.release(); node_hi.release(); vmin.release(); level_start.clear();
+        valid = false;
+    }
+};
+
 // Everything load_tetrahedra owns, built on the device from the caller's (device) xyz / cells on `stream`:
 // face table in first-seen order, face -> tets, Morton-ordered walk records, hull tree, 64-wide face BVH.
 // Blocking (a handful of small D2H reads: counts, the hull faces, the child rows for the stack bound).
 // Throws the reference's errors ("A triangle is shared by more than two tetrahedra!", out-of-bounds vertex ids).
+// `keep` (may be null): filled for a later device_refit; with null the build launches and keeps exactly what it did without it.
 void device_build(size_t V, size_t T, const float *xyz, const uint32_t *cells, hipStream_t stream, BuildTargets out,
-                  BuildInfo &info, uint32_t leaf_w = WIDE);
+                  BuildInfo &info, uint32_t leaf_w = WIDE, RefitTables *keep = nullptr);
+
+// The tables of a device build whose `cells` stay and whose vertices moved (tn_refit.hip): everything that holds positions is
+// recomputed in place from `xyz` -- pn and the thin exponent of the 4T walk records, the face BVH's boxes and leaf triangles
+// over the kept tree, the hull tree -- with the build's expressions, so every table equals a fresh build's up to the order the
+// fresh build would give records, faces and hull slots.  Blocking (two small D2H reads: the hull faces; max |coordinate| and the box of the
+// referenced vertices, which come back in scene_max / box_lo / box_hi = what tn::mesh_box computes).
+struct RefitTargets {
+    WalkHot *hot;                              // [4T]
+    const uint32_t *faces;                     // [F,3]
+    DevBuf<float> &hull_nodes, &hull_tris;     // sizes stay (n_hull is topological)
+    DevWideBvh &bvh;                           // boxes and leaf_tri rewritten; child, leaf_id, n_nodes stay
+};
+void device_refit(size_t V, size_t T, const float *xyz, const uint32_t *cells, hipStream_t stream, RefitTargets out,
+                  RefitTables &kept, float &scene_max, float box_lo[3], float box_hi[3]);
 
 }  // namespace tn

@@ -346,7 +346,8 @@ unsigned bit_length(uint64_t v) { unsigned b = 0; while (v) { ++b; v >>= 1; } re
 }  // namespace
 
 void device_build(size_t V, size_t T, const float *xyz, const uint32_t *cells, hipStream_t s, BuildTargets out, BuildInfo &info,
-                  uint32_t leaf_w) {
+                  uint32_t leaf_w, RefitTables *keep) {
+    if (keep) keep->release();
     if (leaf_w != 16 && leaf_w != 32 && leaf_w != 64) throw Error("leaf width must be 16, 32 or 64");
     const uint32_t leaf_shift = leaf_w == 16 ? 4u : (leaf_w == 32 ? 5u : 6u);
     if (T == 0) throw Error("device_build needs at least one tetrahedron");
@@ -406,8 +407,8 @@ void device_build(size_t V, size_t T, const float *xyz, const uint32_t *cells, h
 
     // ------------------------------------------------------------ hull tree (host threading of the downloaded faces)
     std::vector<float> hinfo(n_hull * 12);
+    DevBuf<uint32_t> dinfo;
     if (n_hull) {
-        DevBuf<uint32_t> dinfo;
         dinfo.alloc(n_hull * 12);
         hipLaunchKernelGGL(k_hull_info, dim3(grid_for(F)), dim3(BT), 0, s, F, hflag.p, hidx.p, out.faces.p, out.face_tets.p, tet_face.p,
                            rec_of_tet.p, xyz, dinfo.p, flags.p);
@@ -523,6 +524,16 @@ void device_build(size_t V, size_t T, const float *xyz, const uint32_t *cells, h
         std::memcpy(&info.scene_max, &bits, 4);
     }
     out.bvh.set_view(n_wide, info.scene_max, leaf_w);
+    if (keep) {   // option "refit_tables": what tn_refit.hip needs and no table above holds (everything else is freed here)
+        keep->order.swap(order); keep->hull_info.swap(dinfo); keep->bn.swap(dbn); keep->face_order.swap(ord_a);
+        keep->leaf_nodes.swap(dleaf_nodes); keep->node_lo.swap(node_lo); keep->node_hi.swap(node_hi);
+        keep->wide_sub.alloc(n_wide);
+        TN_HIP(hipMemcpyAsync(keep->wide_sub.p, wide_sub.p, n_wide * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        TN_HIP(hipStreamSynchronize(s));
+        keep->vmin.alloc(V + REFIT_STAT_WORDS);
+        keep->level_start = level_start;
+        keep->valid = true;
+    }
 }
 
 }  // namespace tn

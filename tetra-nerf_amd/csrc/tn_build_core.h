@@ -423,5 +423,69 @@ TN_HD int split_axis(const float clo[3], const float chi[3]) {
     return ax;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Element functions of the refit (tn_refit.hip, tests/host/refit_emul.cpp): the vertices moved, `cells` did not.  Each one
+// recomputes a value that holds positions with the expression the build above uses for it, so that a refitted table equals
+// the table of a fresh build on the same vertices bit for bit; nothing topological is read-modified.
+
+// k_tet_thin's element: the star minima of the smallest tet height (vmin preset to +inf = 0x7F800000)
+TN_HD void tet_thin_star(uint32_t i, const uint32_t *cells, const float *xyz, uint32_t *vmin) {
+    const uint32_t *c = cells + 4 * (size_t)i;
+    float p[4][3];
+    for (int k = 0; k < 4; ++k) for (int a = 0; a < 3; ++a) p[k][a] = xyz[3 * (size_t)c[k] + a];
+    const uint32_t bits = tet_min_height_bits(p);
+    for (int k = 0; k < 4; ++k) atomic_min_u32(vmin + c[k], bits);
+}
+// The two geometry fields of the record of (tet with vertex ids c[0..4), entry face e): pn = the vertex opposite e
+// (walk_var_of) and the thin exponent in bits 8..15 of code_hi (k_thin_patch).  Rec: WalkVar or WalkHot.
+template <class Rec>
+TN_HD void refit_walk_record(Rec &rec, uint32_t e, const uint32_t *c, const float *xyz, const uint32_t *vmin) {
+    for (int a = 0; a < 3; ++a) rec.pn[a] = xyz[3 * (size_t)c[e] + a];
+    const uint32_t thin = thin_exponent(vmin[c[0]], vmin[c[1]], vmin[c[2]], vmin[c[3]]);
+    rec.code_hi = (rec.code_hi & ~(0xFFu << THIN_SHIFT)) | (thin << THIN_SHIFT);
+}
+// the nine floats of a hull face's 12-word info (hull_face_info); the face id in word 3 and the (record, local face)
+// words 7 and 11 are topological and stay
+TN_HD void hull_face_refit(const uint32_t *faces, const float *xyz, uint32_t *io12) {
+    const uint32_t *f = faces + 3 * (size_t)io12[3];
+    for (int v = 0; v < 3; ++v)
+        for (int k = 0; k < 3; ++k) {
+            const float x = xyz[3 * (size_t)f[v] + k];
+            uint32_t u;
+#if defined(__HIP_DEVICE_COMPILE__)
+            u = __float_as_uint(x);
+#else
+            std::memcpy(&u, &x, 4);
+#endif
+            io12[v * 4 + k] = u;
+        }
+}
+// box of binary node k over the kept face order (k_face_boxes + k_node_boxes: the same minima in the same order); the
+// children of an internal node must have been done (levels bottom up)
+TN_HD void refit_node_box(size_t k, const BinNode *bn, const uint32_t *order, const uint32_t *faces, const float *xyz,
+                          float *node_lo, float *node_hi) {
+    const BinNode nd = bn[k];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (nd.left < 0) {
+        for (uint32_t i = nd.first; i < nd.first + nd.count; ++i) {
+            float b[6], cen[3];
+            face_box(order[i], faces, xyz, b, cen);
+            for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], b[a]); hi[a] = fmaxf(hi[a], b[3 + a]); }
+        }
+    } else {
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fminf(node_lo[3 * (size_t)nd.left + a], node_lo[3 * (size_t)nd.right + a]);
+            hi[a] = fmaxf(node_hi[3 * (size_t)nd.left + a], node_hi[3 * (size_t)nd.right + a]);
+        }
+    }
+    for (int a = 0; a < 3; ++a) { node_lo[3 * k + a] = lo[a]; node_hi[3 * k + a] = hi[a]; }
+}
+// binary node behind child reference `ch` of a wide node (k_collapse: bit 31 = leaf index, else a wide node whose binary
+// subtree root is wide_sub[ch]); -1: no child
+TN_HD int wide_child_node(uint32_t ch, const uint32_t *leaf_nodes, const uint32_t *wide_sub) {
+    if (ch == TN_EMPTY) return -1;
+    return (int)((ch & 0x80000000u) ? leaf_nodes[ch & 0x7FFFFFFFu] : wide_sub[ch]);
+}
+
 }  // namespace core
 }  // namespace tn

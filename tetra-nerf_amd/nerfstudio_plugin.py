@@ -44,7 +44,8 @@ weight-gradient GEMMs of the MLP adjoint, independent of both), `eval_mlp_mode` 
 has the reference's own `tetrahedra_occupancy` buffer (`use_occupancy_field=True`, model.py:98-99,256-265: registered there, never
 used) -- `occupancy_threshold` (evaluation renders skip the network in tetrahedra below it), `occupancy_decay` (training
 batches update the buffer: max(decay occupancy, max density seen)) and `occupancy_train_threshold` (training batches skip the
-network in tetrahedra below it, except every `occupancy_refresh_every`-th one, default 16, which runs unculled).
+network in tetrahedra below it, except every `occupancy_refresh_every`-th one, default 16, which runs unculled); and
+`refit_vertices` (the tracer follows a vertex table an optimiser moves: `_follow_vertices` below).
 
 nerfstudio is not installed in this environment: the adapter is duck-typed (it only touches the attribute names listed
 above) and is tested with stand-ins of nerfstudio's MLP / FieldHead / RayBundle (tests/golden/nerfstudio_standins.py).
@@ -226,6 +227,24 @@ def _renderer_for(model, tracer):
     return rd
 
 
+def _follow_vertices(tracer):
+    """`config.refit_vertices` (opt-in; no such field in the reference's config): the tracer's tables follow the vertex table
+    it borrows.  The (version counter, storage) of `tracer.tetrahedra_vertices` is remembered at load / refit and the tracer is
+    refitted (`update_vertices`: the cells stay, everything that holds positions is recomputed) before the trace whenever
+    either moved -- the rule the field shadow cache uses.  The model's own `get_tetrahedra_tracer` loads without the refit
+    tables, so the first call loads once more with them.  A write through `.data` bumps no counter: call
+    `tracer.update_vertices(v)` yourself after one."""
+    if not getattr(tracer, "supports_refit", False):
+        raise RuntimeError("config.refit_vertices needs a tracer with update_vertices (tetranerf_cpp_extension.TetrahedraTracer)")
+    v = tracer.tetrahedra_vertices
+    key = (v._version, v.data_ptr())
+    if not getattr(tracer, "_refittable", False):
+        tracer.load_tetrahedra(v, tracer.tetrahedra_cells, refittable=True)
+    elif getattr(tracer, "_tn_vertex_key", None) != key:
+        tracer.update_vertices(v)
+    tracer._tn_vertex_key = key
+
+
 def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
     """Drop-in body of TetrahedraNerf.get_outputs (model.py:520-662) on the fused kernels: training mode = stratified
     samples + autograd through the HIP adjoints (`render_train`), evaluation = `render`; same output dictionary
@@ -242,6 +261,8 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
     if model.mlp_base is None:
         raise ValueError("populate_fields() must be called before get_outputs")
     tracer = model.get_tetrahedra_tracer()          # lazy mesh initialisation + structure build (model.py:394-407)
+    if getattr(model.config, "refit_vertices", False):
+        _follow_vertices(tracer)
     rd = _renderer_for(model, tracer)
     o = ray_bundle.origins.reshape(-1, 3).contiguous()
     d = ray_bundle.directions.reshape(-1, 3).contiguous()

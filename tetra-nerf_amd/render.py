@@ -859,7 +859,9 @@ class TetraRenderer:
         sample_positions_grad before the MLP node (fused) or the gather (fused=False), and the view directions of the head
         layer are differentiable too.  Tet membership, the sample distances t, near / far and the sampler draws are
         CONSTANTS of that gradient: the coarse pass and the samplers stay under no_grad, nothing flows through the
-        tracer's hit distances.  After the vertices moved, the tracer must be reloaded (load_tetrahedra).
+        tracer's hit distances.  After the vertices moved the tracer must follow them: tracer.update_vertices(vertices) while
+        the cells stay (a tracer loaded with refittable=True), load_tetrahedra after a re-triangulation, with the host build, and
+        every so often over a long optimisation (records and BVH keep the order of the loaded positions).
         mlp_mode (fused path; None: the renderer's train_mlp_mode, "fp32" unless chosen otherwise): "bf16x3" runs the forward
         kernels of this call -- the coarse density pass, the recorded fine node and the no-graph fine forward -- in the
         split-operand bf16 arithmetic (same 1e-5 bar against fp32 as in render()); the adjoints take that forward's

@@ -133,7 +133,9 @@ class TetrahedraTracer:
         _check(x.dtype == torch.float32, f"{name} must have float32 type")
         _check(x.dim() >= 1 and x.size(-1) == 3, f"{name} must have last dimension with size 3")
 
-    def load_tetrahedra(self, xyz, cells):
+    def load_tetrahedra(self, xyz, cells, refittable: bool = False):
+        """PyTetrahedraTracer::load_tetrahedra (py_binding.cpp:144-161).  refittable (no reference counterpart; keyword; for THIS
+        load): the tracer keeps what update_vertices needs (option "refit_tables"; tn_refit_table_bytes tells how much)."""
         self._check_float_dim3(xyz, "xyz")
         _check_input(cells, "cells")
         _check(cells.device == self._device, "cells must be on the same device")
@@ -143,8 +145,30 @@ class TetrahedraTracer:
         self.tetrahedra_cells = cells
         self.tetrahedra_vertices = xyz
         invalidate_field_cache()   # a new mesh comes with a (re-)initialised field (model.py:349-392 writes it through .data)
+        if refittable or self._refittable:
+            self.set_option("refit_tables", int(bool(refittable)))
+            self._refittable = bool(refittable)
         _lib.check(self._lib.tn_load_tetrahedra(
             self._h, xyz.numel() // 3, cells.numel() // 4, _ptr(xyz), _ptr(cells), _stream(self._device)))
+
+    _refittable = False          # what the last load_tetrahedra(refittable=...) set the option to
+    supports_refit = True
+
+    def update_vertices(self, xyz):
+        """The vertices moved, the cells did not (no reference counterpart: the reference reloads): tn_update_vertices recomputes
+        what the tracer's tables hold of the positions and keeps everything topological, so every query answers as a tracer
+        freshly loaded on `xyz` would, at a fraction of the load's cost.  xyz: float32 [V, 3] on the tracer's device with the
+        loaded V -- the loaded tensor after an in-place update, or another one; borrowed from now on, like load_tetrahedra's.
+        Needs load_tetrahedra(..., refittable=True) and the device build.  The field cache is NOT invalidated (the field did not
+        change).  Records and BVH leaves keep the order the LOADED positions gave them: after large deformation, or when the
+        cells change, load again."""
+        self._check_float_dim3(xyz, "xyz")
+        _lib.check(self._lib.tn_update_vertices(self._h, xyz.numel() // 3, _ptr(xyz), _stream(self._device)))
+        self.tetrahedra_vertices = xyz
+
+    def refit_table_bytes(self) -> int:
+        """device bytes kept for update_vertices beyond the tracer's tables (0 after a load without refittable=True)"""
+        return int(self._lib.tn_refit_table_bytes(self._h))
 
     supports_compact_rows = True
     supports_bin_rays = True
