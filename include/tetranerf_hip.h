@@ -76,13 +76,43 @@ int tn_load_tetrahedra(tn_tracer_t tracer, size_t num_vertices, size_t num_cells
  * xyz  f32 [V,3] device: the buffer given to tn_load_tetrahedra, modified in place, or another one; borrowed from now on.
  * Needs a tracer loaded with option "refit_tables" = 1 by the device build.  Blocking, like the load (two small read-backs);
  * launches on `stream`; allocates nothing on the device.  The call makes no promise the load does not make: a move after which
- * tetrahedra overlap gives a mesh the walk's certification does not cover, refitted or freshly loaded.
+ * tetrahedra overlap gives a mesh the walk's certification does not cover, refitted or freshly loaded.  tn_limit_vertex_step
+ * (below) shortens a move so that no tetrahedron inverts; call it on the new vertices before this.
  * Errors (nothing is touched): tracer not loaded; num_vertices != the loaded V; xyz null; loaded without "refit_tables";
  * loaded by the host build ("gpu_build" = 0). */
 int tn_update_vertices(tn_tracer_t tracer, size_t num_vertices, const float *xyz, void *stream);
 
 /* device bytes the loaded mesh keeps for tn_update_vertices beyond its tables (0: loaded without "refit_tables", or not loaded) */
 size_t tn_refit_table_bytes(tn_tracer_t tracer);
+
+/* Vertex step limiter (no reference counterpart: the reference never moves vertices).  An optimiser's step can turn a tetrahedron
+ * inside out; these two entries bound it on the device, with no host synchronisation (csrc/tn_vertex_guard.hip, DESIGN.md
+ * section 4.11).  The WIDTH w of a tetrahedron is its smallest extent over all directions = the smallest of its four heights and
+ * its three distances between opposite edges, evaluated in double on the fp32 coordinates.  If every vertex of a tetrahedron moves
+ * by less than w / 2, its signed volume keeps its sign along the whole straight move.  star_width[v] = the smallest fl32(w) over
+ * the tetrahedra around v (+inf, bits 0x7F800000, where no tetrahedron names v).
+ *
+ * tn_tet_quality: of the loaded cells on `xyz` f32 [V,3] (any positions: the loaded ones, or candidates), each output optional:
+ *   width f32 [T], orient i8 [T] (sign of ((p1-p0) x (p2-p0)) . (p3-p0): -1, 0, 1), star_width f32 [V].
+ * tn_limit_vertex_step: xyz_new f32 [V,3] (in, out) is the move an optimiser wants from xyz_old f32 [V,3].  Per vertex, in fp32:
+ *   limit = fraction * star_width[v] (star widths of xyz_old; written to star_width, which is required: it is the call's scratch);
+ *   star_width[v] < 2^-17 max(|x|,|y|,|z|) of the old position: FROZEN, new = old bit for bit (the rounding of new coordinates
+ *   must stay a small part of the budget; the vertices of zero-volume tetrahedra are frozen by this rule);
+ *   |new - old| <= limit: untouched;  otherwise new = old + (new - old) (limit / |new - old|), or old where |new - old| is not finite.
+ *   counters u32 [4] (zeroed by the call): vertices clamped, frozen vertices that were asked to move, and -- the call's own
+ *   cross-check, unless TN_LIMIT_STEP_NO_VERIFY is set -- tetrahedra whose orientation changed sign from xyz_old to the clamped
+ *   xyz_new (flipped) and those that went from non-zero to zero (collapsed).  Both are 0 whenever the bound applies.
+ *   fraction must be in (0, 0.45].
+ * The bound is per tetrahedron: parts of the hull that are far apart in the mesh and move INTO each other are not covered.
+ * Both work on any loaded tracer (they read the borrowed `cells` only; neither "refit_tables" nor the device build is needed),
+ * leave the tracer's tables alone (tn_update_vertices makes it follow), launch on `stream`, read nothing back and allocate nothing.
+ * Errors (nothing is touched): tracer not loaded; num_vertices != the loaded V; xyz / xyz_old / xyz_new / star_width / counters
+ * null; fraction not in (0, 0.45] (NaN included); unknown flags. */
+#define TN_LIMIT_STEP_NO_VERIFY 1u
+int tn_tet_quality(tn_tracer_t tracer, size_t num_vertices, const float *xyz, float *width, int8_t *orient, float *star_width,
+                   void *stream);
+int tn_limit_vertex_step(tn_tracer_t tracer, size_t num_vertices, const float *xyz_old, float *xyz_new, float fraction,
+                         float *star_width, uint32_t *counters, uint32_t flags, void *stream);
 
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);

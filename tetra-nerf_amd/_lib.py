@@ -31,6 +31,7 @@ SYMBOLS = (
     "tn_occupancy_update", "tn_cull_samples", "tn_mlp_forward_gather_indexed",
     "tn_mlp_forward_gather_train_indexed", "tn_mlp_param_grads_indexed", "tn_mlp_ray_head_grad_indexed", "tn_compact_rows",
     "tn_update_vertices", "tn_refit_table_bytes",
+    "tn_tet_quality", "tn_limit_vertex_step",      # the vertex step limiter: the reference has no counterpart (it never moves vertices)
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -62,6 +63,8 @@ def load():
     lib.tn_tracer_destroy.argtypes = [vp]
     lib.tn_load_tetrahedra.argtypes = [vp, sz, sz, vp, vp, vp]
     lib.tn_update_vertices.argtypes = [vp, sz, vp, vp]
+    lib.tn_tet_quality.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.tn_limit_vertex_step.argtypes = [vp, sz, vp, vp, C.c_float, vp, vp, u32, vp]
     lib.tn_refit_table_bytes.restype = sz
     lib.tn_refit_table_bytes.argtypes = [vp]
     lib.tn_num_faces.restype = sz

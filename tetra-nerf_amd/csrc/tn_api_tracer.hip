@@ -585,6 +585,47 @@ size_t tn_refit_table_bytes(tn_tracer_t tracer) {
     return tracer && tracer->mesh.loaded && tracer->mesh.refit.valid ? tracer->mesh.refit.bytes() : 0;
 }
 
+namespace {
+// the checks both vertex-guard entries share (nothing is touched when one fails)
+void check_guard_mesh(tn_tracer *t, const char *who, size_t V) {
+    tn_tracer::Mesh &b = t->mesh;
+    if (!b.loaded) throw tn::Error(std::string(who) + ": no mesh is loaded; call load_tetrahedra first");
+    if (V != b.view.V)
+        throw tn::Error(std::string(who) + ": " + std::to_string(V) + " vertices given, the loaded mesh has " + std::to_string(b.view.V));
+}
+}  // namespace
+
+int tn_tet_quality(tn_tracer_t tracer, size_t V, const float *xyz, float *width, int8_t *orient, float *star_width, void *stream_) {
+    return guarded([&] {
+        tn_tracer *t = checked(tracer);
+        std::lock_guard<std::mutex> lock(t->mu);
+        check_guard_mesh(t, "tn_tet_quality", V);
+        const tn::DeviceMesh &m = t->mesh.view;
+        if (!xyz) throw tn::Error("tn_tet_quality: xyz must not be null");
+        DeviceGuard g(t->device);
+        tn::launch_tet_quality(V, m.T, m.cells, xyz, width, orient, star_width, (hipStream_t)stream_);
+    });
+}
+
+int tn_limit_vertex_step(tn_tracer_t tracer, size_t V, const float *xyz_old, float *xyz_new, float fraction, float *star_width,
+                         uint32_t *counters, uint32_t flags, void *stream_) {
+    return guarded([&] {
+        tn_tracer *t = checked(tracer);
+        std::lock_guard<std::mutex> lock(t->mu);
+        check_guard_mesh(t, "tn_limit_vertex_step", V);
+        const tn::DeviceMesh &m = t->mesh.view;
+        if (!xyz_old || !xyz_new || !star_width || !counters)
+            throw tn::Error("tn_limit_vertex_step: xyz_old, xyz_new, star_width and counters must not be null");
+        if (!(fraction > 0.f && fraction <= 0.45f))   // NaN fails both
+            throw tn::Error("tn_limit_vertex_step: fraction must be in (0, 0.45]: the bound is proved for moves below half a width, "
+                            "and 0.45 leaves room for the rounding of the new coordinates");
+        if (flags & ~(uint32_t)TN_LIMIT_STEP_NO_VERIFY) throw tn::Error("tn_limit_vertex_step: unknown flags");
+        DeviceGuard g(t->device);
+        tn::launch_limit_vertex_step(V, m.T, m.cells, xyz_old, xyz_new, fraction, star_width, counters,
+                                     !(flags & TN_LIMIT_STEP_NO_VERIFY), (hipStream_t)stream_);
+    });
+}
+
 size_t tn_num_faces(tn_tracer_t tracer) { return tracer && tracer->mesh.loaded ? tracer->mesh.view.F : 0; }
 
 int tn_get_faces(tn_tracer_t tracer, uint32_t *faces_host, uint32_t *face_tets_host) {

@@ -67,4 +67,13 @@ struct RefitTargets {
 void device_refit(size_t V, size_t T, const float *xyz, const uint32_t *cells, hipStream_t stream, RefitTargets out,
                   RefitTables &kept, float &scene_max, float box_lo[3], float box_hi[3]);
 
+// The vertex step limiter (tn_vertex_guard.hip; the rule: tn_vertex_guard_core.h).  Both enqueue on `s` and return: no read-back,
+// no device allocation.  launch_tet_quality: width f32 [T] / orient i8 [T] / star_width f32 [V], each may be null; star_width is
+// preset to +inf by a fill.  launch_limit_vertex_step: star widths of xyz_old into star_width, xyz_new clamped in place,
+// counters u32 [4] zeroed and then = clamped, frozen but asked to move, flipped, collapsed (the last two only with `verify`).
+void launch_tet_quality(size_t V, size_t T, const uint32_t *cells, const float *xyz, float *width, int8_t *orient, float *star_width,
+                        hipStream_t s);
+void launch_limit_vertex_step(size_t V, size_t T, const uint32_t *cells, const float *xyz_old, float *xyz_new, float fraction,
+                              float *star_width, uint32_t *counters, bool verify, hipStream_t s);
+
 }  // namespace tn

@@ -1,4 +1,4 @@
-"""The position gradients, stated once in plain torch (any device, any floating dtype).
+"""The position gradients, and the vertex step limiter (at the end of the file), stated once in plain torch (any device).
 
 What csrc/tn_position_grad.hip computes on the device, as the definition the tests hold it to -- the way ray_order.py
 states the binning key.  Nothing here needs a GPU or the library.
@@ -89,3 +89,115 @@ def barycentrics_of(points: torch.Tensor, tet_vertices: torch.Tensor) -> torch.T
     """The forward statement b = solve(T^T, p - x0).  points [n, 3], tet_vertices [n, 4, 3] -> [n, 3]."""
     T = tet_vertices[:, 1:] - tet_vertices[:, :1]
     return torch.linalg.solve(T.transpose(-1, -2), (points - tet_vertices[:, 0]).unsqueeze(-1)).squeeze(-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The vertex step limiter (csrc/tn_vertex_guard_core.h, csrc/tn_vertex_guard.hip; DESIGN.md section 4.11), stated in torch.
+#
+# The WIDTH w of a tetrahedron is its smallest extent over all directions.  It is attained on one of seven slabs: the four
+# heights and the three distances between opposite edges, |vol6| / |a x b| with a, b two edges of a face or two opposite edges.
+# If every vertex of a tetrahedron moves by less than w / 2 the four points are coplanar at no fraction of the straight move, so
+# the signed volume keeps its sign.  Widths are float64 on the float32 coordinates, one rounding per operation in the order
+# written here (no fused multiply-add: every product is a statement of its own); the clamp is float32 in the order written.
+# With float32 inputs the results are, bit for bit, what the kernels give.
+
+MAX_STEP_FRACTION = 0.45         # 0.45 (1 + 2^-20) + 1/32 < 1/2
+FREEZE_RATIO = 2.0 ** -17        # star width below this part of the vertex's largest |coordinate|: the vertex does not move
+
+_SLABS = ((1, 2, 1, 3), (0, 2, 0, 3), (0, 1, 0, 3), (0, 1, 0, 2),      # faces: two edges out of one corner
+          (0, 1, 2, 3), (0, 2, 1, 3), (0, 3, 1, 2))                    # pairs of opposite edges
+
+
+def _cross3(u, v):
+    return (u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1], u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2], u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0])
+
+
+def _vol6(p):
+    """signed ((p1-p0) x (p2-p0)) . (p3-p0) of p float64 [T, 4, 3]"""
+    n0, n1, n2 = _cross3(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    e3 = p[:, 3] - p[:, 0]
+    return (n0 * e3[:, 0] + n1 * e3[:, 1]) + n2 * e3[:, 2]
+
+
+def tet_orient(vertices: torch.Tensor, cells: torch.Tensor) -> torch.Tensor:
+    """int8 [T]: the sign of the signed volume of every tetrahedron (0 also where it is NaN)"""
+    v = _vol6(vertices.double()[cells.long()])
+    return (v > 0).to(torch.int8) - (v < 0).to(torch.int8)
+
+
+def tet_slabs(p: torch.Tensor):
+    """p float64 [T, 4, 3] -> (vol6 [T] signed, norms [T, 7]): slab k has thickness |vol6| / norms[:, k] and the unit normal of
+    its cross product; the width is the thinnest of the seven.  (torch's float64 square root on the CPU may be a vector-library
+    call that is off in the last bit; the float32 rounding of the width absorbs that except about once in 1e8 tetrahedra.)"""
+    norms = []
+    for a, b, c, d in _SLABS:
+        w0, w1, w2 = _cross3(p[:, b] - p[:, a], p[:, d] - p[:, c])
+        norms.append(torch.sqrt((w0 * w0 + w1 * w1) + w2 * w2))
+    return _vol6(p), torch.stack(norms, -1)
+
+
+def tet_width64(p: torch.Tensor) -> torch.Tensor:
+    """float64 [T]: |vol6| / den with den the largest of the seven norms (taken with `>`, so a NaN norm is passed over), 0 where den is 0"""
+    vol6, norms = tet_slabs(p)
+    den = torch.zeros_like(vol6)
+    for k in range(7):
+        den = torch.where(norms[:, k] > den, norms[:, k], den)
+    return torch.where(den > 0, vol6.abs() / den, torch.zeros_like(den))
+
+
+def tet_width_orient(vertices: torch.Tensor, cells: torch.Tensor):
+    """vertices [V, 3], cells integer [T, 4] -> (width float32 [T], orient int8 [T]).  width = fl32(tet_width64); anything that is
+    not 0 <= width < inf counts as 0."""
+    p = vertices.double()[cells.long()]
+    w = tet_width64(p).to(torch.float32)
+    w = torch.where((w >= 0) & (w < float("inf")), w, torch.zeros_like(w))
+    vol6 = _vol6(p)
+    return w, (vol6 > 0).to(torch.int8) - (vol6 < 0).to(torch.int8)
+
+
+def star_width(vertices: torch.Tensor, cells: torch.Tensor, width: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 [V]: the smallest width over the tetrahedra around each vertex; +inf where no tetrahedron names it"""
+    if width is None:
+        width = tet_width_orient(vertices, cells)[0]
+    out = torch.full((vertices.shape[0],), float("inf"), dtype=torch.float32, device=vertices.device)
+    return out.scatter_reduce_(0, cells.long().reshape(-1), width.repeat_interleave(4), "amin", include_self=True)
+
+
+def _sqrt_f32(x: torch.Tensor) -> torch.Tensor:
+    """the correctly rounded float32 square root (what sqrtf is on the device and in C).  torch.sqrt on a float32 CPU tensor
+    is not that: above a few hundred elements it is a vector-library call whose last bit depends on the machine.  Through float64
+    it is: the root of a float32 is never close enough to the middle of two float32 for the float64 rounding to matter."""
+    return torch.sqrt(x.double()).to(torch.float32)
+
+
+def limit_vertex_step_statement(xyz_old: torch.Tensor, xyz_new: torch.Tensor, cells: torch.Tensor, fraction: float = 0.25,
+                                _check_range: bool = True):
+    """What tn_limit_vertex_step computes.  xyz_old / xyz_new float32 [V, 3] (xyz_new is NOT modified), cells integer [T, 4].
+    Returns a dict: "xyz" float32 [V, 3] the limited positions, "star_width" float32 [V] (of xyz_old), "frozen" / "clamped" bool
+    [V], "counters" int64 [4] = clamped, frozen but asked to move, flipped, collapsed (tetrahedra, xyz_old against "xyz").
+    `_check_range=False` (tests only) lifts both the range of `fraction` and the freeze rule: it shows what the same step does
+    when it is clamped to more than the bound allows."""
+    if _check_range and not 0.0 < fraction <= MAX_STEP_FRACTION:
+        raise ValueError("fraction must be in (0, 0.45]")
+    old, new = xyz_old.to(torch.float32), xyz_new.to(torch.float32)
+    star = star_width(old, cells)
+    a = old.abs()
+    m = a[:, 0]
+    m = torch.where(a[:, 1] > m, a[:, 1], m)
+    m = torch.where(a[:, 2] > m, a[:, 2], m)
+    frozen = ~(star >= torch.tensor(FREEZE_RATIO, dtype=torch.float32, device=old.device) * m)
+    if not _check_range:
+        frozen = torch.zeros_like(frozen)
+    d = new - old
+    n = _sqrt_f32((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    lim = torch.tensor(fraction, dtype=torch.float32, device=old.device) * star
+    finite = n < float("inf")
+    kept = finite & (n <= lim)
+    s = lim / n
+    shortened = old + d * s[:, None]
+    out = torch.where(frozen[:, None], old, torch.where(kept[:, None], new, torch.where(finite[:, None], shortened, old)))
+    clamped = ~frozen & ~kept
+    before, after = tet_orient(old, cells).long(), tet_orient(out, cells).long()
+    counters = torch.stack([clamped.sum(), (frozen & (new != old).any(-1)).sum(), (before * after < 0).sum(),
+                            ((before != 0) & (after == 0)).sum()])
+    return {"xyz": out, "star_width": star, "frozen": frozen, "clamped": clamped, "counters": counters}

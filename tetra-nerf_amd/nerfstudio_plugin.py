@@ -45,7 +45,8 @@ has the reference's own `tetrahedra_occupancy` buffer (`use_occupancy_field=True
 used) -- `occupancy_threshold` (evaluation renders skip the network in tetrahedra below it), `occupancy_decay` (training
 batches update the buffer: max(decay occupancy, max density seen)) and `occupancy_train_threshold` (training batches skip the
 network in tetrahedra below it, except every `occupancy_refresh_every`-th one, default 16, which runs unculled); and
-`refit_vertices` (the tracer follows a vertex table an optimiser moves: `_follow_vertices` below).
+`refit_vertices` (the tracer follows a vertex table an optimiser moves: `_follow_vertices` below) with `vertex_step_fraction`
+(each followed move is first shortened so that no tetrahedron turns inside out: `TetrahedraTracer.limit_vertex_step`).
 
 nerfstudio is not installed in this environment: the adapter is duck-typed (it only touches the attribute names listed
 above) and is tested with stand-ins of nerfstudio's MLP / FieldHead / RayBundle (tests/golden/nerfstudio_standins.py).
@@ -227,21 +228,47 @@ def _renderer_for(model, tracer):
     return rd
 
 
-def _follow_vertices(tracer):
+def _follow_vertices(tracer, model=None, fraction=None):
     """`config.refit_vertices` (opt-in; no such field in the reference's config): the tracer's tables follow the vertex table
     it borrows.  The (version counter, storage) of `tracer.tetrahedra_vertices` is remembered at load / refit and the tracer is
     refitted (`update_vertices`: the cells stay, everything that holds positions is recomputed) before the trace whenever
     either moved -- the rule the field shadow cache uses.  The model's own `get_tetrahedra_tracer` loads without the refit
     tables, so the first call loads once more with them.  A write through `.data` bumps no counter: call
-    `tracer.update_vertices(v)` yourself after one."""
+    `tracer.update_vertices(v)` yourself after one.
+
+    `config.vertex_step_fraction` (opt-in, with refit_vertices; absent or None: the route above, call for call): a snapshot of the
+    vertices is kept at every load / refit, and a move is first shortened against it -- `limit_vertex_step(snapshot, v.data,
+    fraction)` writes the vertex tensor in place, so the optimiser's parameter itself holds the limited positions -- then the
+    tracer is refitted and the snapshot updated.  The key is taken again after the in-place write.  The call's counters
+    (clamped, frozen but asked to move, flipped, collapsed) accumulate in `model._tn_vertex_step_counters`, an int64 tensor on
+    the device; nothing is read back here."""
     if not getattr(tracer, "supports_refit", False):
         raise RuntimeError("config.refit_vertices needs a tracer with update_vertices (tetranerf_cpp_extension.TetrahedraTracer)")
+    if fraction is not None and not getattr(tracer, "supports_vertex_step_limit", False):
+        raise RuntimeError("config.vertex_step_fraction needs a tracer with limit_vertex_step (tetranerf_cpp_extension.TetrahedraTracer)")
     v = tracer.tetrahedra_vertices
     key = (v._version, v.data_ptr())
+    snapshot = getattr(tracer, "_tn_vertex_snapshot", None) if fraction is not None else None
     if not getattr(tracer, "_refittable", False):
         tracer.load_tetrahedra(v, tracer.tetrahedra_cells, refittable=True)
+        snapshot = None
     elif getattr(tracer, "_tn_vertex_key", None) != key:
+        if snapshot is not None and snapshot.shape == v.shape:
+            counters, _ = tracer.limit_vertex_step(snapshot, v.data, float(fraction))
+            total = getattr(model, "_tn_vertex_step_counters", None) if model is not None else None
+            if total is None or total.device != counters.device:
+                total = torch.zeros(4, dtype=torch.int64, device=counters.device)
+                if model is not None:
+                    model._tn_vertex_step_counters = total
+            total += counters
+        else:
+            snapshot = None          # first sight of a tracer someone else loaded: nothing valid to limit against
         tracer.update_vertices(v)
+        if snapshot is not None:
+            snapshot.copy_(v.detach())
+        key = (v._version, v.data_ptr())
+    if fraction is not None and snapshot is None:
+        tracer._tn_vertex_snapshot = v.detach().clone()
     tracer._tn_vertex_key = key
 
 
@@ -261,8 +288,12 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
     if model.mlp_base is None:
         raise ValueError("populate_fields() must be called before get_outputs")
     tracer = model.get_tetrahedra_tracer()          # lazy mesh initialisation + structure build (model.py:394-407)
+    step_fraction = getattr(model.config, "vertex_step_fraction", None)
     if getattr(model.config, "refit_vertices", False):
-        _follow_vertices(tracer)
+        _follow_vertices(tracer, model, step_fraction)
+    elif step_fraction is not None:
+        raise ValueError("config.vertex_step_fraction needs config.refit_vertices = True: the limiter shortens a move against "
+                         "the vertices of the last refit, and only a tracer that follows the vertices has one")
     rd = _renderer_for(model, tracer)
     o = ray_bundle.origins.reshape(-1, 3).contiguous()
     d = ray_bundle.directions.reshape(-1, 3).contiguous()

@@ -161,7 +161,8 @@ class TetrahedraTracer:
         loaded V -- the loaded tensor after an in-place update, or another one; borrowed from now on, like load_tetrahedra's.
         Needs load_tetrahedra(..., refittable=True) and the device build.  The field cache is NOT invalidated (the field did not
         change).  Records and BVH leaves keep the order the LOADED positions gave them: after large deformation, or when the
-        cells change, load again."""
+        cells change, load again.  A move after which tetrahedra overlap leaves a mesh the walk's certification does not cover,
+        refitted or freshly loaded: limit_vertex_step(old, xyz) before this call shortens a move so that no tetrahedron inverts."""
         self._check_float_dim3(xyz, "xyz")
         _lib.check(self._lib.tn_update_vertices(self._h, xyz.numel() // 3, _ptr(xyz), _stream(self._device)))
         self.tetrahedra_vertices = xyz
@@ -169,6 +170,56 @@ class TetrahedraTracer:
     def refit_table_bytes(self) -> int:
         """device bytes kept for update_vertices beyond the tracer's tables (0 after a load without refittable=True)"""
         return int(self._lib.tn_refit_table_bytes(self._h))
+
+    supports_vertex_step_limit = True
+    VERTEX_GUARD_GRID_LANES = 1024 * 256     # lanes of the limiter's kernels at their grid cap (tn_vertex_guard.hip: GUARD_BLOCKS * BT)
+
+    def _check_loaded_vertices(self, x, name):
+        self._check_float_dim3(x, name)
+        _check(self.tetrahedra_vertices is not None, "no mesh is loaded; call load_tetrahedra first")
+        _check(x.dim() == 2 and x.size(0) == self.tetrahedra_vertices.numel() // 3,
+               f"{name} must have shape [V, 3] with the V of the loaded mesh")
+
+    def tet_quality(self, xyz=None):
+        """Width and orientation of every loaded tetrahedron on `xyz` (None: the loaded vertices), and the star width of every
+        vertex (no reference counterpart; tn_tet_quality, geometry.tet_width_orient / star_width).  xyz: float32 [V, 3] on the
+        tracer's device, any positions of the loaded mesh's vertices.  Returns {"width": f32 [T] -- the smallest extent of the
+        tetrahedron over all directions, "orient": int8 [T] -- sign of its signed volume, "star_width": f32 [V] -- the smallest
+        width around the vertex, +inf where no tetrahedron names it}.  No synchronisation."""
+        with torch.no_grad():
+            if xyz is None:
+                xyz = self.tetrahedra_vertices
+                _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
+            self._check_loaded_vertices(xyz, "xyz")
+            V, T, dev = xyz.size(0), self.tetrahedra_cells.numel() // 4, self._device
+            width = _empty((T,), dtype=torch.float32, device=dev)
+            orient = _empty((T,), dtype=torch.int8, device=dev)
+            star = _empty((V,), dtype=torch.float32, device=dev)
+            with _on(dev):
+                _lib.check(self._lib.tn_tet_quality(self._h, V, _ptr(xyz), _ptr(width), _ptr(orient), _ptr(star), _stream(dev)))
+            return {"width": width, "orient": orient, "star_width": star}
+
+    def limit_vertex_step(self, xyz_old, xyz_new, fraction: float = 0.25, verify: bool = True):
+        """Shorten the move xyz_old -> xyz_new per vertex so that no tetrahedron of the loaded mesh turns inside out (no
+        reference counterpart; tn_limit_vertex_step, geometry.limit_vertex_step_statement; the rule and its proof: DESIGN.md
+        section 4.11).  xyz_old: float32 [V, 3], the positions the mesh is valid on (the tracer's, at the last load or refit);
+        xyz_new: float32 [V, 3], WRITTEN IN PLACE (pass `param.data` of an optimised tensor: the call runs under no_grad and bumps
+        no version counter).  A vertex moves by at most fraction * its star width (fraction in (0, 0.45]); vertices whose star
+        width is below 2^-17 of their largest |coordinate| stay where they were.  verify: also count the tetrahedra that flipped
+        or collapsed all the same (one more pass; both 0 whenever the bound applies).
+        Returns (counters int32 [4] on the device: clamped, frozen but asked to move, flipped, collapsed; star_width f32 [V]).
+        Nothing is read back: look at the counters when you would synchronise anyway.  The tracer's tables are not touched --
+        update_vertices(xyz_new) makes it follow.  Not covered: far-apart parts of the hull moving into each other."""
+        with torch.no_grad():
+            self._check_loaded_vertices(xyz_old, "xyz_old")
+            self._check_loaded_vertices(xyz_new, "xyz_new")
+            V, dev = xyz_old.size(0), self._device
+            star = _empty((V,), dtype=torch.float32, device=dev)
+            counters = _empty((4,), dtype=torch.int32, device=dev)
+            with _on(dev):
+                _lib.check(self._lib.tn_limit_vertex_step(self._h, V, _ptr(xyz_old), _ptr(xyz_new), float(fraction), _ptr(star),
+                                                          _ptr(counters), 0 if verify else 1, _stream(dev)))
+            return counters, star
 
     supports_compact_rows = True
     supports_bin_rays = True
