@@ -59,13 +59,11 @@ def _raw_chain(tn, c, fwd, mode):
     cpp = tn.cpp
     lib = cpp._lib.load()
     sigma, rgb, saved = fwd
-    n, a = c["n"], saved.acts
+    n = c["n"]
     dev = sigma.device
     buf = torch.full((4 * 128 + 4, n), float("nan"), dtype=torch.float32, device=dev)
     rows = torch.full((n, 64), float("nan"), dtype=torch.float32, device=dev)
-    bs = cpp._MlpBackwardBuffers(a[0:64].data_ptr(), a[64:192].data_ptr(), a[192:320].data_ptr(), a[320:448].data_ptr(),
-                                 a[448:576].data_ptr(), saved.masks.data_ptr(), buf[0:128].data_ptr(), buf[128:256].data_ptr(),
-                                 buf[256:384].data_ptr(), buf[384:512].data_ptr(), buf[512:516].data_ptr(), rows.data_ptr())
+    bs = cpp._backward_buffers(saved.acts, saved.masks, buf, rows)
     mh = cpp.fused_mlp(c["w"])
     head = (mh.handle, n, sigma.data_ptr(), rgb.data_ptr(), c["d_sigma"].data_ptr(), c["d_rgb"].data_ptr(), C.byref(bs))
     stream = cpp._stream(dev)

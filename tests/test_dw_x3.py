@@ -90,12 +90,16 @@ def test_module_hands_the_dw_mode_to_its_renderer():
     assert rd.train_dw_mode == "fp32"
 
 
-def test_the_autograd_node_is_absent_safe():
-    """the node reads its trailing modes by position: none, one or two of them leave the weight-gradient mode at fp32"""
-    render = importlib.import_module("tetra-nerf_amd.render")
-    src = inspect.getsource(render._FusedMlpFunction.forward)
-    assert 'ctx.dw_mode = weights[14] if ctx.num_modes >= 3 else "fp32"' in src
-    assert "dw_mode=ctx.dw_mode" in inspect.getsource(render._FusedMlpFunction.backward)
+def test_the_autograd_node_is_absent_safe(tn, monkeypatch):
+    """the nodes read their trailing modes by position: none, one or two of them leave the weight-gradient mode at fp32, a third
+    one is the weight-gradient mode (run on recorders of the ops: tests/test_mlp_node_modes.py)"""
+    import test_mlp_node_modes as nodes
+
+    calls = nodes.install_recorders(tn.cpp, monkeypatch)
+    for node in ("dense", "indexed"):
+        for trailing in ((), ("bf16x3",), ("bf16x3", "bf16x3")):
+            assert nodes.run_node(tn, calls, node, trailing, bias=False)[2] == "fp32"
+        assert nodes.run_node(tn, calls, node, ("fp32", "fp32", "bf16x3"), bias=False) == ("fp32", "fp32", "bf16x3")
 
 
 class _Recorder:

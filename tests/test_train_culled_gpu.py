@@ -316,8 +316,7 @@ def test_entry_arguments(tn, device):
     h = tn.cpp.fused_mlp(p["w"]).handle
     a = torch.empty(576, 10, device=device)
     m = torch.empty(4, 10, 2, dtype=torch.int64, device=device)
-    bs = tn.cpp._MlpBackwardBuffers(a[0:64].data_ptr(), a[64:192].data_ptr(), a[192:320].data_ptr(), a[320:448].data_ptr(),
-                                    a[448:576].data_ptr(), m.data_ptr(), None, None, None, None, None, None)
+    bs = tn.cpp._backward_buffers(a, m)
     rc = lib.tn_mlp_forward_gather_train_indexed(h, 10, p["n"], p["S"], live.data_ptr(), p["vi"].data_ptr(), p["bc"].data_ptr(),
                                                  tn.cpp.field_vertex_major(p["field"]).data_ptr(), p["dirs"].data_ptr(), 2,
                                                  torch.empty(p["n"], device=device).data_ptr(),

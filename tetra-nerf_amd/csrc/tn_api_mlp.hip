@@ -29,6 +29,12 @@ struct tn_mlp {
         }
         return tn::MlpPacks{pk_plain.p, pk_gather.p, pt.p, blob.p, wenc.p, hterm.p, enc.p, nullptr, grad_scratch.p, blob_bf16.p, blob_t.p};
     }
+    // the partial sums of the parameter gradients: allocated by the first training call of this handle
+    void ensure_grad_scratch() {
+        if (grad_scratch.p) return;
+        TN_HIP(hipDeviceSynchronize());
+        grad_scratch.alloc(tn::mlp_param_grad_scratch_floats());
+    }
 };
 
 namespace {
@@ -40,13 +46,15 @@ tn_mlp *checked_mlp(tn_mlp_t m) {
     if (!m) throw tn::Error("mlp handle is null");
     return m;
 }
-// inference: the evaluation forwards, which also run in plain bf16; everything else (training forward, tn_render_rays) does not
-void check_mode(int mode, bool inference = false) {
+// inference: the evaluation forwards, which also run in plain bf16; everything else (training forward, tn_render_rays) does not.
+// no_mode_2: the wording of an entry that refuses mode 2 in words of its own
+void check_mode(int mode, bool inference = false, const char *no_mode_2 = nullptr) {
     if (inference) {
         if (mode < 0 || mode > 2) throw tn::Error("mlp mode must be 0 (fp32 MFMA), 1 (bf16x3 MFMA) or 2 (plain bf16 MFMA)");
     } else if (mode == 2) {
-        throw tn::Error("mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA) here: mode 2 (plain bf16 MFMA) is an arithmetic of "
-                        "tn_mlp_forward and tn_mlp_forward_gather only");
+        throw tn::Error(no_mode_2 ? no_mode_2
+                                  : "mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA) here: mode 2 (plain bf16 MFMA) is an arithmetic of "
+                                    "tn_mlp_forward and tn_mlp_forward_gather only");
     } else if (mode != 0 && mode != 1) {
         throw tn::Error("mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA)");
     }
@@ -55,9 +63,147 @@ void check_mode(int mode, bool inference = false) {
 auto forward_of(int mode) {
     return mode == 2 ? tn::launch_mlp_forward_bf16 : mode ? tn::launch_mlp_forward_x3 : tn::launch_mlp_forward;
 }
+void require(bool all_given) {
+    if (!all_given) throw tn::Error("null pointer");
+}
+// what the training forward saves (the masks aside: the weight gradients do not read them)
+void require_saved(const tn_mlp_backward_buffers *b) { require(b->x0 && b->h1 && b->h2 && b->h3 && b->h4); }
+// what the dX chain leaves for the weight gradients (d x0 aside: it belongs to the gather adjoint)
+void require_chain(const tn_mlp_backward_buffers *b) { require(b->d1 && b->d2 && b->d3 && b->d4 && b->dhead); }
 tn::MlpBackwardBuffers training_buffers(const tn_mlp_backward_buffers *b) {
     return tn::MlpBackwardBuffers{{b->x0, b->h1, b->h2, b->h3, b->h4, (unsigned long long *)b->masks},
                                   b->d1, b->d2, b->d3, b->d4, b->dhead, b->dx0};
+}
+tn::MlpParamGrads checked_grads(const tn_mlp_grads *g) {
+    float *const gp[12] = {g->w1, g->b1, g->w2, g->b2, g->w3, g->b3, g->wd, g->bd, g->wh, g->bh, g->wr, g->br};
+    for (float *p : gp) require(p);
+    return tn::MlpParamGrads{gp[0], gp[1], gp[2], gp[3], gp[4], gp[5], gp[6], gp[7], gp[8], gp[9], gp[10], gp[11]};
+}
+// The training stages, one host path each.  listed: slot i < n of the call is sample live[i] of n_samples (the _indexed
+// entries); otherwise slot i is sample i and n_samples = n.  -> the rays of the call; the two forms word the condition differently
+size_t checked_rays(bool listed, size_t n, size_t n_samples, uint32_t samples_per_ray) {
+    if (!listed) {
+        if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
+    } else {
+        if (samples_per_ray == 0 || n_samples == 0 || n_samples % samples_per_ray != 0)
+            throw tn::Error("n_samples must be a positive multiple of samples_per_ray");
+        if (n_samples >= 0xFFFFFFFFull || n >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
+    }
+    return n_samples / samples_per_ray;
+}
+
+int forward_gather(tn_mlp_t mlp, bool listed, size_t n, uint32_t samples_per_ray, const uint32_t *live, const uint32_t *live_count,
+                   const uint32_t *vertex_indices, const float *barycentric, const float *field_vm, const float *dirs, int mode,
+                   float *sigma, float *rgb, const float *ray_head_bias, const uint32_t *count, void *stream_) {
+    return guarded([&] {
+        tn_mlp *m = checked_mlp(mlp);
+        check_mode(mode, !listed, "mlp_forward_gather_indexed: mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA): the plain-bf16 kernel "
+                                  "(mode 2) has no indexed form");
+        if (n == 0) return;
+        require(vertex_indices && barycentric && field_vm && sigma && (!rgb || dirs) && (!listed || (live && live_count)));
+        if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
+        if (listed && n >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
+        DeviceGuard g(m->device);
+        const size_t rays = n / samples_per_ray;
+        tn::MlpPacks pk = m->packs(rays);
+        pk.ray_bias = rgb ? ray_head_bias : nullptr;
+        if (listed)
+            tn::launch_mlp_forward_indexed(n, samples_per_ray, rays, live, live_count, vertex_indices, barycentric, field_vm, dirs, pk, mode,
+                                           sigma, rgb, (hipStream_t)stream_, count);
+        else
+            forward_of(mode)(n, samples_per_ray, rays, nullptr, vertex_indices, barycentric, field_vm, dirs, pk, sigma, rgb,
+                             (hipStream_t)stream_, count);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int forward_train(tn_mlp_t mlp, bool listed, size_t n, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
+                  const uint32_t *vertex_indices, const float *barycentric, const float *field_vm, const float *dirs, int mode,
+                  float *sigma, float *rgb, const tn_mlp_backward_buffers *b, const float *ray_head_bias, void *stream_) {
+    return guarded([&] {
+        tn_mlp *m = checked_mlp(mlp);
+        check_mode(mode, false, !listed ? nullptr
+                                        : "mlp_forward_gather_train_indexed: mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA): the "
+                                          "plain-bf16 kernel (mode 2) has neither a training nor an indexed form");
+        if (n == 0) return;
+        require(vertex_indices && barycentric && field_vm && dirs && sigma && rgb && b && (!listed || live));
+        require_saved(b);
+        require(b->masks);
+        const size_t rays = checked_rays(listed, n, n_samples, samples_per_ray);
+        DeviceGuard g(m->device);
+        tn::MlpPacks pk = m->packs(rays);
+        pk.ray_bias = ray_head_bias;
+        if (listed)
+            tn::launch_mlp_forward_train_indexed(n, n_samples, samples_per_ray, live, vertex_indices, barycentric, field_vm, dirs, pk, mode,
+                                                 sigma, rgb, training_buffers(b), (hipStream_t)stream_);
+        else
+            (mode ? tn::launch_mlp_forward_x3_train : tn::launch_mlp_forward_train)(
+                n, samples_per_ray, rays, vertex_indices, barycentric, field_vm, dirs, pk, sigma, rgb, training_buffers(b),
+                (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+// (runs unchanged on the compact columns of a listed forward: there is no listed form)
+int backward(tn_mlp_t mlp, size_t n, const float *sigma, const float *rgb, const float *d_sigma, const float *d_rgb,
+             const tn_mlp_backward_buffers *b, int mode, void *stream_) {
+    return guarded([&] {
+        tn_mlp *m = checked_mlp(mlp);
+        check_mode(mode);
+        if (n == 0) return;
+        require(b && sigma && rgb && d_sigma && d_rgb);
+        require(b->masks && b->dx0);
+        require_chain(b);
+        DeviceGuard g(m->device);
+        (mode ? tn::launch_mlp_backward_x3 : tn::launch_mlp_backward)(n, sigma, rgb, m->packs(0), d_sigma, d_rgb, training_buffers(b),
+                                                                      (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+// d_ray_head_bias covers all rays of the call, so a listed call returns early on n_samples == 0, not on an empty list: an empty
+// list still writes the zeros, and reads neither the list nor d4
+int ray_head_grad(bool listed, size_t n, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
+                  const tn_mlp_backward_buffers *b, float *d_ray_head_bias, void *stream_) {
+    return guarded([&] {
+        if (n_samples == 0) return;
+        const bool reads = !listed || n;
+        require(d_ray_head_bias && (!reads || (b && b->d4 && (!listed || live))));
+        if (samples_per_ray == 0 || n_samples % samples_per_ray != 0)
+            throw tn::Error(listed ? "n_samples must be a multiple of samples_per_ray" : "n must be a multiple of samples_per_ray");
+        if (listed) {
+            if (n_samples >= 0xFFFFFFFFull || n >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
+            tn::launch_ray_head_grad_indexed(n, n_samples, samples_per_ray, live, reads ? b->d4 : nullptr, d_ray_head_bias,
+                                             (hipStream_t)stream_);
+        } else {
+            tn::launch_ray_head_grad(n, samples_per_ray, b->d4, d_ray_head_bias, (hipStream_t)stream_);
+        }
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int param_grads(tn_mlp_t mlp, bool listed, size_t n, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live, const float *dirs,
+                const tn_mlp_backward_buffers *b, const tn_mlp_grads *grads, int mode, void *stream_) {
+    return guarded([&] {
+        tn_mlp *m = checked_mlp(mlp);
+        check_mode(mode);
+        if (n == 0) return;   // (grads are accumulated into: untouched)
+        require(b && grads && dirs && (!listed || live));
+        const size_t rays = checked_rays(listed, n, n_samples, samples_per_ray);
+        const tn::MlpParamGrads pg = checked_grads(grads);
+        require_saved(b);
+        require_chain(b);
+        DeviceGuard g(m->device);
+        m->ensure_grad_scratch();
+        const tn::MlpPacks pk = m->packs(rays);
+        if (listed)
+            tn::launch_mlp_param_grads_indexed(n, n_samples, samples_per_ray, live, dirs, pk, training_buffers(b), pg, mode,
+                                               (hipStream_t)stream_);
+        else
+            (mode ? tn::launch_mlp_param_grads_x3 : tn::launch_mlp_param_grads)(n, samples_per_ray, dirs, pk, training_buffers(b), pg,
+                                                                                (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
 }
 }  // namespace
 
@@ -132,21 +278,8 @@ int tn_mlp_forward(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const float
 int tn_mlp_forward_gather(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
                           const float *barycentric, const float *field_vm, const float *dirs, int mode, float *sigma,
                           float *rgb, const float *ray_head_bias, const uint32_t *count, void *stream_) {
-    return guarded([&] {
-        tn_mlp *m = checked_mlp(mlp);
-        check_mode(mode, true);
-        if (n == 0) return;
-        if (!vertex_indices || !barycentric || !field_vm || !sigma || (rgb && !dirs)) throw tn::Error("null pointer");
-        if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
-        DeviceGuard g(m->device);
-        const size_t rays = n / samples_per_ray;
-        tn::MlpPacks pk = m->packs(rays);
-        pk.ray_bias = rgb ? ray_head_bias : nullptr;
-        forward_of(mode)(
-            n, samples_per_ray, rays, nullptr, vertex_indices, barycentric, field_vm, dirs, pk, sigma, rgb,
-            (hipStream_t)stream_, count);
-        TN_HIP(hipGetLastError());
-    });
+    return forward_gather(mlp, false, n, samples_per_ray, nullptr, nullptr, vertex_indices, barycentric, field_vm, dirs, mode, sigma, rgb,
+                          ray_head_bias, count, stream_);
 }
 
 int tn_render_rays(tn_mlp_t mlp, uint32_t M, const uint32_t *num_visited, const float *hit_distances, const float *barycentric,
@@ -216,120 +349,40 @@ int tn_render_rays_ex(tn_mlp_t mlp, uint32_t M, const uint32_t *num_visited, con
 int tn_mlp_forward_gather_train(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
                                 const float *barycentric, const float *field_vm, const float *dirs, float *sigma, float *rgb,
                                 const tn_mlp_backward_buffers *b, const float *ray_head_bias, void *stream_) {
-    return tn_mlp_forward_gather_train_ex(mlp, n, samples_per_ray, vertex_indices, barycentric, field_vm, dirs, 0, sigma, rgb, b,
-                                          ray_head_bias, stream_);
+    return forward_train(mlp, false, n, n, samples_per_ray, nullptr, vertex_indices, barycentric, field_vm, dirs, 0, sigma, rgb, b,
+                         ray_head_bias, stream_);
 }
 
 int tn_mlp_forward_gather_train_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const uint32_t *vertex_indices,
                                    const float *barycentric, const float *field_vm, const float *dirs, int mode, float *sigma,
                                    float *rgb, const tn_mlp_backward_buffers *b, const float *ray_head_bias, void *stream_) {
-    return guarded([&] {
-        tn_mlp *m = checked_mlp(mlp);
-        check_mode(mode);
-        if (n == 0) return;
-        if (!vertex_indices || !barycentric || !field_vm || !dirs || !sigma || !rgb || !b) throw tn::Error("null pointer");
-        if (!b->x0 || !b->h1 || !b->h2 || !b->h3 || !b->h4 || !b->masks) throw tn::Error("null pointer");
-        if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
-        DeviceGuard g(m->device);
-        const size_t rays = n / samples_per_ray;
-        tn::MlpPacks pk = m->packs(rays);
-        pk.ray_bias = ray_head_bias;
-        (mode ? tn::launch_mlp_forward_x3_train : tn::launch_mlp_forward_train)(
-            n, samples_per_ray, rays, vertex_indices, barycentric, field_vm, dirs, pk, sigma, rgb, training_buffers(b),
-            (hipStream_t)stream_);
-        TN_HIP(hipGetLastError());
-    });
+    return forward_train(mlp, false, n, n, samples_per_ray, nullptr, vertex_indices, barycentric, field_vm, dirs, mode, sigma, rgb, b,
+                         ray_head_bias, stream_);
 }
 
 int tn_mlp_backward(tn_mlp_t mlp, size_t n, const float *sigma, const float *rgb, const float *d_sigma, const float *d_rgb,
                     const tn_mlp_backward_buffers *b, void *stream_) {
-    return guarded([&] {
-        tn_mlp *m = checked_mlp(mlp);
-        if (n == 0) return;
-        if (!b || !sigma || !rgb || !d_sigma || !d_rgb) throw tn::Error("null pointer");
-        if (!b->masks || !b->d1 || !b->d2 || !b->d3 || !b->d4 || !b->dhead || !b->dx0) throw tn::Error("null pointer");
-        DeviceGuard g(m->device);
-        tn::launch_mlp_backward(n, sigma, rgb, m->packs(0), d_sigma, d_rgb, training_buffers(b), (hipStream_t)stream_);
-        TN_HIP(hipGetLastError());
-    });
+    return backward(mlp, n, sigma, rgb, d_sigma, d_rgb, b, 0, stream_);
 }
 
 int tn_mlp_backward_ex(tn_mlp_t mlp, size_t n, const float *sigma, const float *rgb, const float *d_sigma, const float *d_rgb,
                        const tn_mlp_backward_buffers *b, int mode, void *stream_) {
-    if (mode == 0) return tn_mlp_backward(mlp, n, sigma, rgb, d_sigma, d_rgb, b, stream_);
-    return guarded([&] {
-        tn_mlp *m = checked_mlp(mlp);
-        check_mode(mode);
-        if (n == 0) return;
-        if (!b || !sigma || !rgb || !d_sigma || !d_rgb) throw tn::Error("null pointer");
-        if (!b->masks || !b->d1 || !b->d2 || !b->d3 || !b->d4 || !b->dhead || !b->dx0) throw tn::Error("null pointer");
-        DeviceGuard g(m->device);
-        tn::launch_mlp_backward_x3(n, sigma, rgb, m->packs(0), d_sigma, d_rgb, training_buffers(b), (hipStream_t)stream_);
-        TN_HIP(hipGetLastError());
-    });
+    return backward(mlp, n, sigma, rgb, d_sigma, d_rgb, b, mode, stream_);
 }
 
 int tn_mlp_ray_head_grad(size_t n, uint32_t samples_per_ray, const tn_mlp_backward_buffers *b, float *d_ray_head_bias,
                          void *stream_) {
-    return guarded([&] {
-        if (n == 0) return;
-        if (!b || !b->d4 || !d_ray_head_bias) throw tn::Error("null pointer");
-        if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
-        tn::launch_ray_head_grad(n, samples_per_ray, b->d4, d_ray_head_bias, (hipStream_t)stream_);
-        TN_HIP(hipGetLastError());
-    });
+    return ray_head_grad(false, n, n, samples_per_ray, nullptr, b, d_ray_head_bias, stream_);
 }
 
 int tn_mlp_param_grads(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const float *dirs, const tn_mlp_backward_buffers *b,
                        const tn_mlp_grads *grads, void *stream_) {
-    return guarded([&] {
-        tn_mlp *m = checked_mlp(mlp);
-        if (n == 0) return;
-        if (!b || !grads || !dirs) throw tn::Error("null pointer");
-        if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
-        float *const gp[12] = {grads->w1, grads->b1, grads->w2, grads->b2, grads->w3, grads->b3,
-                               grads->wd, grads->bd, grads->wh, grads->bh, grads->wr, grads->br};
-        for (float *p : gp)
-            if (!p) throw tn::Error("null pointer");
-        if (!b->x0 || !b->h1 || !b->h2 || !b->h3 || !b->h4 || !b->d1 || !b->d2 || !b->d3 || !b->d4 || !b->dhead)
-            throw tn::Error("null pointer");
-        DeviceGuard g(m->device);
-        if (!m->grad_scratch.p) {   // first training call of this handle
-            TN_HIP(hipDeviceSynchronize());
-            m->grad_scratch.alloc(tn::mlp_param_grad_scratch_floats());
-        }
-        const tn::MlpBackwardBuffers bb = training_buffers(b);
-        tn::MlpParamGrads pg{gp[0], gp[1], gp[2], gp[3], gp[4], gp[5], gp[6], gp[7], gp[8], gp[9], gp[10], gp[11]};
-        tn::launch_mlp_param_grads(n, samples_per_ray, dirs, m->packs(n / samples_per_ray), bb, pg, (hipStream_t)stream_);
-        TN_HIP(hipGetLastError());
-    });
+    return param_grads(mlp, false, n, n, samples_per_ray, nullptr, dirs, b, grads, 0, stream_);
 }
 
 int tn_mlp_param_grads_ex(tn_mlp_t mlp, size_t n, uint32_t samples_per_ray, const float *dirs, const tn_mlp_backward_buffers *b,
                           const tn_mlp_grads *grads, int mode, void *stream_) {
-    if (mode == 0) return tn_mlp_param_grads(mlp, n, samples_per_ray, dirs, b, grads, stream_);
-    return guarded([&] {
-        tn_mlp *m = checked_mlp(mlp);
-        check_mode(mode);
-        if (n == 0) return;
-        if (!b || !grads || !dirs) throw tn::Error("null pointer");
-        if (samples_per_ray == 0 || n % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
-        float *const gp[12] = {grads->w1, grads->b1, grads->w2, grads->b2, grads->w3, grads->b3,
-                               grads->wd, grads->bd, grads->wh, grads->bh, grads->wr, grads->br};
-        for (float *p : gp)
-            if (!p) throw tn::Error("null pointer");
-        if (!b->x0 || !b->h1 || !b->h2 || !b->h3 || !b->h4 || !b->d1 || !b->d2 || !b->d3 || !b->d4 || !b->dhead)
-            throw tn::Error("null pointer");
-        DeviceGuard g(m->device);
-        if (!m->grad_scratch.p) {   // first training call of this handle
-            TN_HIP(hipDeviceSynchronize());
-            m->grad_scratch.alloc(tn::mlp_param_grad_scratch_floats());
-        }
-        const tn::MlpBackwardBuffers bb = training_buffers(b);
-        tn::MlpParamGrads pg{gp[0], gp[1], gp[2], gp[3], gp[4], gp[5], gp[6], gp[7], gp[8], gp[9], gp[10], gp[11]};
-        tn::launch_mlp_param_grads_x3(n, samples_per_ray, dirs, m->packs(n / samples_per_ray), bb, pg, (hipStream_t)stream_);
-        TN_HIP(hipGetLastError());
-    });
+    return param_grads(mlp, false, n, n, samples_per_ray, nullptr, dirs, b, grads, mode, stream_);
 }
 
 int tn_compact_hits(size_t num_rays, const uint32_t *num_visited, uint32_t *order, uint32_t *count, uint32_t *padded,
@@ -373,90 +426,26 @@ int tn_mlp_forward_gather_indexed(tn_mlp_t mlp, size_t n_max, uint32_t samples_p
                                   const uint32_t *live_count, const uint32_t *vertex_indices, const float *barycentric,
                                   const float *field_vm, const float *dirs, int mode, float *sigma, float *rgb,
                                   const float *ray_head_bias, const uint32_t *count, void *stream_) {
-    return guarded([&] {
-        tn_mlp *m = checked_mlp(mlp);
-        if (mode == 2)
-            throw tn::Error("mlp_forward_gather_indexed: mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA): the plain-bf16 kernel "
-                            "(mode 2) has no indexed form");
-        check_mode(mode);
-        if (n_max == 0) return;
-        if (!live || !live_count || !vertex_indices || !barycentric || !field_vm || !sigma || (rgb && !dirs)) throw tn::Error("null pointer");
-        if (samples_per_ray == 0 || n_max % samples_per_ray != 0) throw tn::Error("n must be a multiple of samples_per_ray");
-        if (n_max >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
-        DeviceGuard g(m->device);
-        const size_t rays = n_max / samples_per_ray;
-        tn::MlpPacks pk = m->packs(rays);
-        pk.ray_bias = rgb ? ray_head_bias : nullptr;
-        tn::launch_mlp_forward_indexed(n_max, samples_per_ray, rays, live, live_count, vertex_indices, barycentric, field_vm, dirs, pk, mode,
-                                       sigma, rgb, (hipStream_t)stream_, count);
-        TN_HIP(hipGetLastError());
-    });
+    return forward_gather(mlp, true, n_max, samples_per_ray, live, live_count, vertex_indices, barycentric, field_vm, dirs, mode, sigma, rgb,
+                          ray_head_bias, count, stream_);
 }
 
 int tn_mlp_forward_gather_train_indexed(tn_mlp_t mlp, size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
                                         const uint32_t *vertex_indices, const float *barycentric, const float *field_vm,
                                         const float *dirs, int mode, float *sigma, float *rgb, const tn_mlp_backward_buffers *b,
                                         const float *ray_head_bias, void *stream_) {
-    return guarded([&] {
-        tn_mlp *m = checked_mlp(mlp);
-        if (mode == 2)
-            throw tn::Error("mlp_forward_gather_train_indexed: mlp mode must be 0 (fp32 MFMA) or 1 (bf16x3 MFMA): the plain-bf16 kernel "
-                            "(mode 2) has neither a training nor an indexed form");
-        check_mode(mode);
-        if (n_live == 0) return;
-        if (!live || !vertex_indices || !barycentric || !field_vm || !dirs || !sigma || !rgb || !b) throw tn::Error("null pointer");
-        if (!b->x0 || !b->h1 || !b->h2 || !b->h3 || !b->h4 || !b->masks) throw tn::Error("null pointer");
-        if (samples_per_ray == 0 || n_samples == 0 || n_samples % samples_per_ray != 0)
-            throw tn::Error("n_samples must be a positive multiple of samples_per_ray");
-        if (n_samples >= 0xFFFFFFFFull || n_live >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
-        DeviceGuard g(m->device);
-        tn::MlpPacks pk = m->packs(n_samples / samples_per_ray);
-        pk.ray_bias = ray_head_bias;
-        tn::launch_mlp_forward_train_indexed(n_live, n_samples, samples_per_ray, live, vertex_indices, barycentric, field_vm, dirs, pk, mode,
-                                             sigma, rgb, training_buffers(b), (hipStream_t)stream_);
-        TN_HIP(hipGetLastError());
-    });
+    return forward_train(mlp, true, n_live, n_samples, samples_per_ray, live, vertex_indices, barycentric, field_vm, dirs, mode, sigma, rgb,
+                         b, ray_head_bias, stream_);
 }
 
 int tn_mlp_param_grads_indexed(tn_mlp_t mlp, size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
                                const float *dirs, const tn_mlp_backward_buffers *b, const tn_mlp_grads *grads, int mode, void *stream_) {
-    return guarded([&] {
-        tn_mlp *m = checked_mlp(mlp);
-        check_mode(mode);
-        if (n_live == 0) return;   // (grads are accumulated into: untouched)
-        if (!live || !b || !grads || !dirs) throw tn::Error("null pointer");
-        if (samples_per_ray == 0 || n_samples == 0 || n_samples % samples_per_ray != 0)
-            throw tn::Error("n_samples must be a positive multiple of samples_per_ray");
-        if (n_samples >= 0xFFFFFFFFull || n_live >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
-        float *const gp[12] = {grads->w1, grads->b1, grads->w2, grads->b2, grads->w3, grads->b3,
-                               grads->wd, grads->bd, grads->wh, grads->bh, grads->wr, grads->br};
-        for (float *p : gp)
-            if (!p) throw tn::Error("null pointer");
-        if (!b->x0 || !b->h1 || !b->h2 || !b->h3 || !b->h4 || !b->d1 || !b->d2 || !b->d3 || !b->d4 || !b->dhead)
-            throw tn::Error("null pointer");
-        DeviceGuard g(m->device);
-        if (!m->grad_scratch.p) {   // first training call of this handle
-            TN_HIP(hipDeviceSynchronize());
-            m->grad_scratch.alloc(tn::mlp_param_grad_scratch_floats());
-        }
-        tn::MlpParamGrads pg{gp[0], gp[1], gp[2], gp[3], gp[4], gp[5], gp[6], gp[7], gp[8], gp[9], gp[10], gp[11]};
-        tn::launch_mlp_param_grads_indexed(n_live, n_samples, samples_per_ray, live, dirs, m->packs(n_samples / samples_per_ray),
-                                           training_buffers(b), pg, mode, (hipStream_t)stream_);
-        TN_HIP(hipGetLastError());
-    });
+    return param_grads(mlp, true, n_live, n_samples, samples_per_ray, live, dirs, b, grads, mode, stream_);
 }
 
 int tn_mlp_ray_head_grad_indexed(size_t n_live, size_t n_samples, uint32_t samples_per_ray, const uint32_t *live,
                                  const tn_mlp_backward_buffers *b, float *d_ray_head_bias, void *stream_) {
-    return guarded([&] {
-        if (n_samples == 0) return;
-        if (!d_ray_head_bias || (n_live && (!live || !b || !b->d4))) throw tn::Error("null pointer");
-        if (samples_per_ray == 0 || n_samples % samples_per_ray != 0) throw tn::Error("n_samples must be a multiple of samples_per_ray");
-        if (n_samples >= 0xFFFFFFFFull || n_live >= 0xFFFFFFFFull) throw tn::Error("too many samples for one call");
-        tn::launch_ray_head_grad_indexed(n_live, n_samples, samples_per_ray, live, n_live ? b->d4 : nullptr, d_ray_head_bias,
-                                         (hipStream_t)stream_);
-        TN_HIP(hipGetLastError());
-    });
+    return ray_head_grad(true, n_live, n_samples, samples_per_ray, live, b, d_ray_head_bias, stream_);
 }
 
 int tn_compact_rows(uint32_t words_per_row, size_t n_live, const uint32_t *live, const void *src, void *dst, void *stream_) {

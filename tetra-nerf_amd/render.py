@@ -426,60 +426,81 @@ class GradientScaler(torch.autograd.Function):
         return grad_colors * scaling, grad_sigmas * scaling, grad_ray_dist
 
 
+def _node_modes(weights):
+    """(weights12, mode, adjoint_mode, dw_mode, num_modes) of what trails a fused MLP node's arguments: the 12 weight tensors,
+    optionally followed by the forward's mode, then the dX chain's, then the weight-gradient GEMMs' ("fp32" when absent)."""
+    num_modes = len(weights) - 12
+    mode, adjoint_mode, dw_mode = (tuple(weights[12:]) + ("fp32",) * 3)[:3]
+    return weights[:12], mode, adjoint_mode, dw_mode, num_modes
+
+
+def _fused_mlp_forward(ctx, listed, vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray, ray_head_bias, weights):
+    """forward of both fused MLP nodes; listed: None, or the (live, n_live, out) of _FusedMlpCulledFunction"""
+    from . import tetranerf_cpp_extension as cpp
+
+    weights, mode, ctx.adjoint_mode, ctx.dw_mode, ctx.num_modes = _node_modes(weights)
+    ctx.has_bias = ray_head_bias is not None
+    if listed is None:
+        sigma, rgb, saved = cpp.mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dirs, list(weights),
+                                                         int(samples_per_ray), ray_head_bias=ray_head_bias, mode=mode)
+    else:
+        live, n_live, out = listed
+        sigma, rgb, saved = cpp.mlp_forward_gather_train_indexed(live, n_live, vertex_indices, barycentric_coordinates, field, dirs,
+                                                                 list(weights), int(samples_per_ray), ray_head_bias=ray_head_bias,
+                                                                 mode=mode, sigma=out[0], rgb=out[1])
+    # the outputs go through save_for_backward (which knows how to hold a node's own outputs); `saved` must not
+    # reference them: node -> saved -> output -> grad_fn -> node is a cycle no collector sees through, i.e. 5 GB
+    # leaked per iteration
+    saved.sigma = saved.rgb = None
+    ctx.save_for_backward(vertex_indices, barycentric_coordinates, field, dirs, sigma, rgb, *weights)
+    ctx.saved = saved
+    return sigma, rgb
+
+
+def _fused_mlp_backward(ctx, d_sigma, d_rgb, leading=0):
+    """backward of both fused MLP nodes (cpp.mlp_backward tells the compact saves of a listed forward by their type); leading:
+    how many inputs without a gradient the node has in front of vertex_indices"""
+    from . import tetranerf_cpp_extension as cpp
+
+    vi, bc, field, dirs, sigma, rgb, *weights = ctx.saved_tensors
+    saved = ctx.saved          # (kept: a second backward through a retained graph reads the same activations)
+    need_bary, need_dirs = ctx.needs_input_grad[leading + 1], ctx.needs_input_grad[leading + 3]
+    res = cpp.mlp_backward(saved, vi, bc, field, dirs, list(weights), sigma, rgb, d_sigma.contiguous(), d_rgb.contiguous(),
+                           want_ray_head_grad=ctx.has_bias or need_dirs, want_bary_grad=need_bary,
+                           adjoint_mode=ctx.adjoint_mode, dw_mode=ctx.dw_mode)
+    grad_field, grads = res[0], res[1]
+    # the per-ray head bias (appearance embedding): its gradient = per-ray sums of the head pre-activation's gradient
+    d_head = res[2] if (ctx.has_bias or need_dirs) else None
+    grad_bary = res[-1].view_as(bc) if need_bary else None
+    grad_dirs = None
+    if need_dirs:
+        # the view direction enters through the head layer's per-ray term Wh[:, :27] enc(dir): the same per-ray sums times
+        # those columns, chained through the Jacobian of the encoding (recomputed: 27 values per ray)
+        g_enc = d_head @ weights[8][:, :DIR_ENC]
+        with torch.enable_grad():
+            d_leaf = dirs.detach().requires_grad_(True)
+            (grad_dirs,) = torch.autograd.grad(direction_encoding(d_leaf), d_leaf, g_enc)
+    return ((None,) * leading + (None, grad_bary, grad_field, grad_dirs, None, d_head if ctx.has_bias else None, *grads)
+            + (None,) * ctx.num_modes)
+
+
 class _FusedMlpFunction(torch.autograd.Function):
     """gather + MLP + heads as ONE autograd node: forward = tn_mlp_forward_gather_train_ex (`mode`: "fp32" or "bf16x3"; saves the
-    layer inputs and the ReLU masks, 2.3 KB per sample), backward = tn_mlp_backward + tn_mlp_param_grads + tn_interpolate_values_backward (dX
-    chain and weight gradients on the fp32 matrix cores, nothing recomputed; with the adjoint mode "bf16x3" the dX chain is
-    tn_mlp_backward_ex(mode 1), its four matrix products on the bf16 matrix cores; with the weight-gradient mode "bf16x3" the
-    four weight-gradient GEMMs are tn_mlp_param_grads_ex(mode 1), both operands split as they are staged).  Gradients flow to the field and the 12
+    layer inputs and the ReLU masks, 2.3 KB per sample), backward = tn_mlp_backward_ex + tn_mlp_param_grads_ex +
+    tn_interpolate_values_backward (dX chain and weight gradients on the fp32 matrix cores, nothing recomputed; with the adjoint
+    mode "bf16x3" the four matrix products of the dX chain run on the bf16 matrix cores; with the weight-gradient mode "bf16x3" so
+    do the four weight-gradient GEMMs, both operands split as they are staged).  Gradients flow to the field and the 12
     weight tensors, and -- when they require it -- to the barycentrics (tn_interpolate_values_backward_bary_vm on the same
-    d x0 rows; the vertex indices are constants) and to the view directions (through the head layer's per-ray term)."""
+    d x0 rows; the vertex indices are constants) and to the view directions (through the head layer's per-ray term).
+    `weights`: the 12 tensors and up to three modes (_node_modes)."""
 
     @staticmethod
     def forward(ctx, vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray, ray_head_bias, *weights):
-        from . import tetranerf_cpp_extension as cpp
-
-        # weights: the 12 tensors, optionally followed by the forward's mode, then the adjoint's, then the weight-gradient GEMMs'
-        # ("fp32" when absent)
-        ctx.num_modes = len(weights) - 12
-        mode = weights[12] if ctx.num_modes >= 1 else "fp32"
-        ctx.adjoint_mode = weights[13] if ctx.num_modes >= 2 else "fp32"
-        ctx.dw_mode = weights[14] if ctx.num_modes >= 3 else "fp32"
-        weights = weights[:12]
-        ctx.has_bias = ray_head_bias is not None
-        sigma, rgb, saved = cpp.mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dirs, list(weights),
-                                                         int(samples_per_ray), ray_head_bias=ray_head_bias, mode=mode)
-        # the outputs go through save_for_backward (which knows how to hold a node's own outputs); `saved` must not
-        # reference them: node -> saved -> output -> grad_fn -> node is a cycle no collector sees through, i.e. 5 GB
-        # leaked per iteration
-        saved.sigma = saved.rgb = None
-        ctx.save_for_backward(vertex_indices, barycentric_coordinates, field, dirs, sigma, rgb, *weights)
-        ctx.saved = saved
-        return sigma, rgb
+        return _fused_mlp_forward(ctx, None, vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray, ray_head_bias, weights)
 
     @staticmethod
     def backward(ctx, d_sigma, d_rgb):
-        from . import tetranerf_cpp_extension as cpp
-
-        vi, bc, field, dirs, sigma, rgb, *weights = ctx.saved_tensors
-        saved = ctx.saved          # (kept: a second backward through a retained graph reads the same activations)
-        need_bary, need_dirs = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
-        res = cpp.mlp_backward(saved, vi, bc, field, dirs, list(weights), sigma, rgb, d_sigma.contiguous(), d_rgb.contiguous(),
-                               want_ray_head_grad=ctx.has_bias or need_dirs, want_bary_grad=need_bary,
-                               adjoint_mode=ctx.adjoint_mode, dw_mode=ctx.dw_mode)
-        grad_field, grads = res[0], res[1]
-        # the per-ray head bias (appearance embedding): its gradient = per-ray sums of the head pre-activation's gradient
-        d_head = res[2] if (ctx.has_bias or need_dirs) else None
-        grad_bary = res[-1].view_as(bc) if need_bary else None
-        grad_dirs = None
-        if need_dirs:
-            # the view direction enters through the head layer's per-ray term Wh[:, :27] enc(dir): the same per-ray sums times
-            # those columns, chained through the Jacobian of the encoding (recomputed: 27 values per ray)
-            g_enc = d_head @ weights[8][:, :DIR_ENC]
-            with torch.enable_grad():
-                d_leaf = dirs.detach().requires_grad_(True)
-                (grad_dirs,) = torch.autograd.grad(direction_encoding(d_leaf), d_leaf, g_enc)
-        return (None, grad_bary, grad_field, grad_dirs, None, d_head if ctx.has_bias else None, *grads, *((None,) * ctx.num_modes))
+        return _fused_mlp_backward(ctx, d_sigma, d_rgb)
 
 
 class _FusedMlpCulledFunction(torch.autograd.Function):
@@ -491,36 +512,12 @@ class _FusedMlpCulledFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, live, n_live, out, vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray, ray_head_bias, *weights):
-        from . import tetranerf_cpp_extension as cpp
-
-        ctx.num_modes = len(weights) - 12
-        mode = weights[12] if ctx.num_modes >= 1 else "fp32"
-        ctx.adjoint_mode = weights[13] if ctx.num_modes >= 2 else "fp32"
-        ctx.dw_mode = weights[14] if ctx.num_modes >= 3 else "fp32"
-        weights = weights[:12]
-        ctx.has_bias = ray_head_bias is not None
-        sigma, rgb, saved = cpp.mlp_forward_gather_train_indexed(live, n_live, vertex_indices, barycentric_coordinates, field, dirs,
-                                                                 list(weights), int(samples_per_ray), ray_head_bias=ray_head_bias,
-                                                                 mode=mode, sigma=out[0], rgb=out[1])
-        saved.sigma = saved.rgb = None     # (no cycle through the node's own outputs: see _FusedMlpFunction)
-        ctx.save_for_backward(vertex_indices, barycentric_coordinates, field, dirs, sigma, rgb, *weights)
-        ctx.saved = saved
-        return sigma, rgb
+        return _fused_mlp_forward(ctx, (live, n_live, out), vertex_indices, barycentric_coordinates, field, dirs, samples_per_ray,
+                                  ray_head_bias, weights)
 
     @staticmethod
     def backward(ctx, d_sigma, d_rgb):
-        # _FusedMlpFunction's backward on the compact saves: the same arguments behind the three leading ones
-        return (None, None, None) + _FusedMlpFunction.backward(_TrailingInputs(ctx, 3), d_sigma, d_rgb)
-
-
-class _TrailingInputs:
-    """an autograd context as a node whose inputs start `skip` positions later sees it"""
-
-    def __init__(self, ctx, skip):
-        self._ctx, self.needs_input_grad = ctx, tuple(ctx.needs_input_grad[skip:])
-
-    def __getattr__(self, name):
-        return getattr(self._ctx, name)
+        return _fused_mlp_backward(ctx, d_sigma, d_rgb, leading=3)
 
 
 class _FusedCompositeFunction(torch.autograd.Function):
@@ -834,6 +831,58 @@ class TetraRenderer:
             depth[idx] = depth_r
         return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask}
 
+    def _train_final_pass(self, vi, bc, edges, dirs, w, modes, hb, occ, traced, record, fused):
+        """The network on the final samples of a training call -> (sigma [r,S], col [r,S,3]).  record: as autograd nodes backed by
+        the saving forward and the adjoint kernels (fused, a graph is being recorded), several beyond train_node_samples; fused
+        without a graph: the plain forward kernel; otherwise the PyTorch statement.  occ = (occupancy, threshold): culled."""
+        cpp, S, r = self.cpp, edges.shape[1] - 1, vi.shape[0]
+        if record and occ is not None:
+            # culled: list the live samples (the zeros of the others are written here), read their number back -- the one host
+            # synchronisation of a culled batch: it sizes the saves and the adjoint launches -- and run the node on the list;
+            # lists beyond train_node_samples go through several nodes, one per range of SLOTS (slots are independent), each with
+            # output buffers of its own that are zero wherever it stores nothing: their sum is exact (a softplus / sigmoid output
+            # is never -0, the one value x + 0 would change); n_nodes full-size buffers, for the rare list beyond 2^22 samples
+            n, dev = r * S, vi.device
+            sigma = cpp._empty((n,), dtype=torch.float32, device=dev)
+            col = cpp._empty((n, 3), dtype=torch.float32, device=dev)
+            live, live_count = cpp.cull_samples(traced["cell_indices"], occ[0], occ[1], sigma, col, samples_per_ray=S)
+            n_live = int(live_count.item())
+            per_node = max(1, int(self.train_node_samples))
+            if n_live > per_node:     # (cull_samples left the live positions unwritten: the first range needs zeros at the others')
+                sigma, col = torch.zeros_like(sigma), torch.zeros_like(col)
+            sigma, col = _FusedMlpCulledFunction.apply(live, min(n_live, per_node), (sigma, col), vi, bc, self.field, dirs, S, hb, *w, *modes)
+            for a in range(per_node, n_live, per_node):
+                part = _FusedMlpCulledFunction.apply(live[a:], min(n_live - a, per_node), (torch.zeros_like(sigma), torch.zeros_like(col)),
+                                                     vi, bc, self.field, dirs, S, hb, *w, *modes)
+                sigma, col = sigma + part[0], col + part[1]
+        elif record:
+            # the node keeps 2.3 KB per sample from forward to backward (and its backward writes as much again): batches
+            # beyond 2^22 samples (nerfstudio trains on 4096 rays) go through several nodes, one per block of rays
+            rays_per_node = max(1, int(self.train_node_samples) // S)
+            if r <= rays_per_node:
+                sigma, col = _FusedMlpFunction.apply(vi, bc, self.field, dirs, S, hb, *w, *modes)
+            else:
+                parts = [_FusedMlpFunction.apply(vi[a:a + rays_per_node], bc[a:a + rays_per_node], self.field,
+                                                 dirs[a:a + rays_per_node], S, None if hb is None else hb[a:a + rays_per_node], *w, *modes)
+                         for a in range(0, r, rays_per_node)]
+                sigma, col = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+        elif fused:               # no graph: the plain forward kernel, nothing saved
+            return self._final_forward(vi, bc, edges, dirs, w, modes[0], hb, occ=occ, traced=traced)
+        else:
+            interpolate_values = self._interpolate_values
+            if interpolate_values is None:
+                from . import interpolate_values
+
+            feats = interpolate_values(vi, bc, self.field)
+            sg, col = self.mlp(feats, dirs[:, None, :].expand(-1, S, -1))
+            sigma = sg[..., 0]
+            if occ is not None:      # the statement of culled training: zeros as constants at the culled samples
+                culled = cull_mask_statement(traced["cell_indices"], *occ)
+                sigma = torch.where(culled, torch.zeros_like(sigma), sigma)
+                col = torch.where(culled[..., None], torch.zeros_like(col), col)
+            return sigma, col
+        return sigma.view(-1, S), col.view(-1, S, 3)
+
     def render_train(self, origins: torch.Tensor, directions: torch.Tensor, gradient_scaling: bool = False,
                      generator: Optional[torch.Generator] = None, rand: Optional[Dict[str, torch.Tensor]] = None,
                      fused: bool = True, capture: Optional[dict] = None, background=None,
@@ -904,16 +953,12 @@ class TetraRenderer:
         if occupancy_decay is not None and not fused:
             raise RuntimeError("the occupancy update is a kernel of the fused path (fused=True); its statement is occupancy_update_statement")
         occ = None if thr is None else (occupancy.detach(), float(thr))
-        mode = self.train_mlp_mode if mlp_mode is None else mlp_mode
-        cpp._mode(mode, inference=False)
-        amode = self.train_adjoint_mode if adjoint_mode is None else adjoint_mode
-        wmode = self.train_dw_mode if dw_mode is None else dw_mode
-        # (the default node is built as it always was: a trailing mode is passed only when it, or one behind it, is chosen)
-        if cpp._mode(wmode, inference=False) != 0:
-            cpp._mode(amode, inference=False)
-            modes = (mode, amode, wmode)
-        else:
-            modes = (mode,) if cpp._mode(amode, inference=False) == 0 else (mode, amode)
+        # the arithmetic of the forward kernels, of the recorded node's dX chain and of its weight-gradient GEMMs
+        modes = tuple(own if given is None else given for given, own in
+                      ((mlp_mode, self.train_mlp_mode), (adjoint_mode, self.train_adjoint_mode), (dw_mode, self.train_dw_mode)))
+        for m in modes:
+            cpp._mode(m, inference=False)
+        mode = modes[0]
         R, dev = origins.shape[0], origins.device
         rand = rand or {}
         # SYNC-FREE form (default for the fused path): the reference compacts the hitting rays with boolean indexing
@@ -1029,52 +1074,7 @@ class TetraRenderer:
                            near=near_r, far=far_r, samples_per_ray=S, cell_indices=traced["cell_indices"])
             if occ is not None:
                 capture["culled"] = cull_mask_statement(traced["cell_indices"], *occ)
-        if record and occ is not None:
-            # culled: list the live samples (the zeros of the others are written here), read their number back -- the one host
-            # synchronisation of a culled batch: it sizes the saves and the adjoint launches -- and run the node on the list;
-            # lists beyond train_node_samples go through several nodes, one per range of SLOTS (slots are independent), each with
-            # output buffers of its own that are zero wherever it stores nothing: their sum is exact (a softplus / sigmoid output
-            # is never -0, the one value x + 0 would change); n_nodes full-size buffers, for the rare list beyond 2^22 samples
-            n = r * S
-            sigma = cpp._empty((n,), dtype=torch.float32, device=dev)
-            col = cpp._empty((n, 3), dtype=torch.float32, device=dev)
-            live, live_count = cpp.cull_samples(traced["cell_indices"], occ[0], occ[1], sigma, col, samples_per_ray=S)
-            n_live = int(live_count.item())
-            per_node = max(1, int(self.train_node_samples))
-            if n_live > per_node:     # (cull_samples left the live positions unwritten: the first range needs zeros at the others')
-                sigma, col = torch.zeros_like(sigma), torch.zeros_like(col)
-            sigma, col = _FusedMlpCulledFunction.apply(live, min(n_live, per_node), (sigma, col), vi, bc, self.field, dirs, S, hb, *w, *modes)
-            for a in range(per_node, n_live, per_node):
-                part = _FusedMlpCulledFunction.apply(live[a:], min(n_live - a, per_node), (torch.zeros_like(sigma), torch.zeros_like(col)),
-                                                     vi, bc, self.field, dirs, S, hb, *w, *modes)
-                sigma, col = sigma + part[0], col + part[1]
-            sigma, col = sigma.view(-1, S), col.view(-1, S, 3)
-        elif record:
-            # the node keeps 2.3 KB per sample from forward to backward (and its backward writes as much again): batches
-            # beyond 2^22 samples (nerfstudio trains on 4096 rays) go through several nodes, one per block of rays
-            rays_per_node = max(1, int(self.train_node_samples) // S)
-            if r <= rays_per_node:
-                sigma, col = _FusedMlpFunction.apply(vi, bc, self.field, dirs, S, hb, *w, *modes)
-            else:
-                parts = [_FusedMlpFunction.apply(vi[a:a + rays_per_node], bc[a:a + rays_per_node], self.field,
-                                                 dirs[a:a + rays_per_node], S, None if hb is None else hb[a:a + rays_per_node], *w, *modes)
-                         for a in range(0, r, rays_per_node)]
-                sigma, col = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
-            sigma, col = sigma.view(-1, S), col.view(-1, S, 3)
-        elif fused:               # no graph: the plain forward kernel, nothing saved
-            sigma, col = self._final_forward(vi, bc, edges, dirs, w, mode, hb, occ=occ, traced=traced)
-        else:
-            interpolate_values = self._interpolate_values
-            if interpolate_values is None:
-                from . import interpolate_values
-
-            feats = interpolate_values(vi, bc, self.field)
-            sg, col = self.mlp(feats, dirs[:, None, :].expand(-1, S, -1))
-            sigma = sg[..., 0]
-            if occ is not None:      # the statement of culled training: zeros as constants at the culled samples
-                culled = cull_mask_statement(traced["cell_indices"], *occ)
-                sigma = torch.where(culled, torch.zeros_like(sigma), sigma)
-                col = torch.where(culled[..., None], torch.zeros_like(col), col)
+        sigma, col = self._train_final_pass(vi, bc, edges, dirs, w, modes, hb, occ, traced, record, fused)
         if occupancy_decay is not None:
             with torch.no_grad():
                 cpp.occupancy_update(occupancy, traced["cell_indices"], sigma.detach().contiguous(), occupancy_decay)
@@ -1090,16 +1090,12 @@ class TetraRenderer:
             rgb_r, acc_r, depth_r = cpp.composite(sigma.contiguous(), col.contiguous(), edges, background=bg)
         else:
             rgb_r, acc_r, depth_r, _ = composite(sigma[..., None], col, edges[:, :-1, None], edges[:, 1:, None], background=bg)
+        acc_r, depth_r = acc_r.reshape(-1, 1), depth_r.reshape(-1, 1).detach()
         if sync_free:     # `order` is a permutation of the rays: every row is written once, padded entries get the miss values
             v = valid[:, None]
-            rgb = rgb.index_copy(0, order, torch.where(v, rgb_r, rgb))
-            acc = acc.index_copy(0, order, torch.where(v, acc_r.reshape(-1, 1), acc))
-            depth = depth.index_copy(0, order, torch.where(v, depth_r.reshape(-1, 1).detach(), depth))
-            return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask}
-        rgb = rgb.index_copy(0, idx, rgb_r)
-        acc = acc.index_copy(0, idx, acc_r.reshape(-1, 1))
-        depth = depth.index_copy(0, idx, depth_r.reshape(-1, 1).detach())
-        return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask}
+            idx, rgb_r, acc_r, depth_r = order, torch.where(v, rgb_r, rgb), torch.where(v, acc_r, acc), torch.where(v, depth_r, depth)
+        return {"rgb": rgb.index_copy(0, idx, rgb_r), "accumulation": acc.index_copy(0, idx, acc_r),
+                "depth": depth.index_copy(0, idx, depth_r), "ray_mask": ray_mask}
 
 
 class TetraNerfModule(torch.nn.Module):

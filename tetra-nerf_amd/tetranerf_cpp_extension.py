@@ -21,6 +21,7 @@ nothing imports oracle/.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import torch
@@ -90,6 +91,18 @@ def _on(device):
     if device.index is None or torch.cuda.current_device() == device.index:
         return _NO_GUARD
     return torch.cuda.device(device)
+
+
+def _trace_rows(R, M, dev):
+    """The five unwritten arrays of a trace over R rays with M slots each, under trace_rays' keys and in the order the C entries
+    take them (`*map(_ptr, rows.values())`)."""
+    return {
+        "num_visited_cells": _empty((R,), dtype=torch.int32, device=dev),
+        "visited_cells": _empty((R, M), dtype=torch.int32, device=dev),
+        "barycentric_coordinates": _empty((R, M, 2, 3), dtype=torch.float32, device=dev),
+        "hit_distances": _empty((R, M, 2), dtype=torch.float32, device=dev),
+        "vertex_indices": _empty((R, M, 4), dtype=torch.int32, device=dev),
+    }
 
 
 class TetrahedraTracer:
@@ -239,23 +252,11 @@ class TetrahedraTracer:
             self._check_float_dim3(ray_directions, "ray_directions")
             R = ray_origins.numel() // 3
             _check(ray_directions.numel() // 3 == R, "ray_origins and ray_directions must have the same number of rays")
-            dev = self._device
-            num_visited_cells = _empty((R,), dtype=torch.int32, device=dev)
-            visited_cells = _empty((R, M), dtype=torch.int32, device=dev)
-            barycentric_coordinates = _empty((R, M, 2, 3), dtype=torch.float32, device=dev)
-            hit_distances = _empty((R, M, 2), dtype=torch.float32, device=dev)
-            vertex_indices = _empty((R, M, 4), dtype=torch.int32, device=dev)
+            out = _trace_rows(R, M, self._device)
             _lib.check(self._lib.tn_trace_rays_ex(
-                self._h, R, M, _ptr(ray_origins), _ptr(ray_directions), _ptr(num_visited_cells),
-                _ptr(visited_cells), _ptr(barycentric_coordinates), _ptr(hit_distances),
-                _ptr(vertex_indices), (1 if compact_rows else 0) | (2 if bin_rays else 0), _stream(dev)))
-        return {
-            "num_visited_cells": num_visited_cells,
-            "visited_cells": visited_cells,
-            "barycentric_coordinates": barycentric_coordinates,
-            "vertex_indices": vertex_indices,
-            "hit_distances": hit_distances,
-        }
+                self._h, R, M, _ptr(ray_origins), _ptr(ray_directions), *map(_ptr, out.values()),
+                (1 if compact_rows else 0) | (2 if bin_rays else 0), _stream(self._device)))
+        return out
 
     def trace_rays_triangles(self, ray_origins, ray_directions, max_ray_triangles):
         """PyTetrahedraTracer::trace_rays_triangles (py_binding.cpp:78-113): the sorted all-hits list."""
@@ -420,26 +421,15 @@ class TetrahedraTracer:
         (int32) on those tables instead of the loaded mesh's."""
         R, M = hit_ids.shape
         dev = self._device
-        out = {
-            "num_visited_cells": _empty((R,), dtype=torch.int32, device=dev),
-            "visited_cells": _empty((R, M), dtype=torch.int32, device=dev),
-            "barycentric_coordinates": _empty((R, M, 2, 3), dtype=torch.float32, device=dev),
-            "hit_distances": _empty((R, M, 2), dtype=torch.float32, device=dev),
-            "vertex_indices": _empty((R, M, 4), dtype=torch.int32, device=dev),
-        }
+        out = _trace_rows(R, M, dev)
+        hits = (_ptr(hit_count), _ptr(hit_ids), _ptr(hit_t), _ptr(hit_uv))
         if faces is not None:
             _check(face_tets is not None and faces.dtype == torch.int32 and face_tets.dtype == torch.int32
                    and faces.is_contiguous() and face_tets.is_contiguous(), "faces / face_tets must be contiguous int32")
-            _lib.check(self._lib.tn_postprocess_hits_tables(
-                dev.index or 0, R, M, _ptr(faces), _ptr(face_tets), _ptr(hit_count), _ptr(hit_ids), _ptr(hit_t),
-                _ptr(hit_uv), _ptr(out["num_visited_cells"]), _ptr(out["visited_cells"]),
-                _ptr(out["barycentric_coordinates"]), _ptr(out["hit_distances"]), _ptr(out["vertex_indices"]),
-                _stream(dev)))
+            _lib.check(self._lib.tn_postprocess_hits_tables(dev.index or 0, R, M, _ptr(faces), _ptr(face_tets), *hits,
+                                                            *map(_ptr, out.values()), _stream(dev)))
             return out
-        _lib.check(self._lib.tn_postprocess_hits(
-            self._h, R, M, _ptr(hit_count), _ptr(hit_ids), _ptr(hit_t), _ptr(hit_uv),
-            _ptr(out["num_visited_cells"]), _ptr(out["visited_cells"]), _ptr(out["barycentric_coordinates"]),
-            _ptr(out["hit_distances"]), _ptr(out["vertex_indices"]), _stream(dev)))
+        _lib.check(self._lib.tn_postprocess_hits(self._h, R, M, *hits, *map(_ptr, out.values()), _stream(dev)))
         return out
 
 
@@ -859,25 +849,54 @@ def _check_gather_args(field, dirs, samples=None, rays=None):
     return n, S
 
 
+def _given_or_fresh(t, name, shape, dev, wording):
+    """The f32 output tensor of `shape` a caller handed in to be stored into, checked (`wording`: the caller's own), or a fresh
+    unwritten one."""
+    if t is None:
+        return _empty(shape, dtype=torch.float32, device=dev)
+    _check_input(t, name)
+    _check(t.dtype == torch.float32 and t.numel() == math.prod(shape) and t.device == dev, wording)
+    return t
+
+
+def _forward_gather(listed, live, live_count, vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray, mode,
+                    ray_head_bias, count, sigma, rgb):
+    """mlp_forward_gather (listed=False: tn_mlp_forward_gather, fresh outputs) and mlp_forward_gather_indexed (listed=True:
+    tn_mlp_forward_gather_indexed over live / live_count, outputs given or fresh)."""
+    density_only = dirs is None
+    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
+    dev = field.device
+    if listed:
+        _check(_MODES.get(mode) != 2, 'mlp_forward_gather_indexed: mlp mode must be "fp32" or "bf16x3": the plain-bf16 kernel has no '
+                                      'indexed form')
+        for x, name in ((live, "live"), (live_count, "live_count")):
+            _check_input(x, name)
+            _check(x.dtype == torch.int32 and x.device == dev, f"{name} must be an int32 tensor on the field's device")
+        _check(live.numel() >= n and live_count.numel() >= 1, "live must hold n entries, live_count one")
+        _check_count(count, S, n, "mlp_forward_gather_indexed")
+    m = fused_mlp(weights)
+    field_vm = field_vertex_major(field)
+    sigma = _given_or_fresh(sigma, "sigma", (n,), dev, "sigma must be f32 [n]")
+    rgb = None if density_only else _given_or_fresh(rgb, "rgb", (n, 3), dev, "rgb must be f32 [n, 3]")
+    lib = _lib.load()
+    with _on(dev):
+        args = (_ptr(vertex_indices), _ptr(barycentric_coordinates), _ptr(field_vm), _ptr(dirs), _mode(mode), _ptr(sigma), _ptr(rgb),
+                _ptr(None if density_only else _ray_bias(ray_head_bias, n // S, dev)), _ptr(count), _stream(dev))
+        if listed:
+            _lib.check(lib.tn_mlp_forward_gather_indexed(m.handle, n, S, _ptr(live), _ptr(live_count), *args))
+        else:
+            _lib.check(lib.tn_mlp_forward_gather(m.handle, n, S, *args))
+    return sigma if density_only else (sigma, rgb)
+
+
 def mlp_forward_gather(vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray, mode="fp32",
                        ray_head_bias=None, count=None):
     """interpolate_values + mlp_forward in ONE kernel: the wave gathers its samples' features from the
     (vertex-major shadow of the) field straight into MFMA operand registers; the [64, n] feature buffer is never
     written.  vertex_indices i32 [..., 4], barycentric_coordinates f32 [..., 3], field f32 [64, V].
     dirs=None: density only (the coarse pass of the model, model.py:577-581) -> sigma [n]."""
-    density_only = dirs is None
-    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
-    m = fused_mlp(weights)
-    dev = field.device
-    field_vm = field_vertex_major(field)
-    sigma = _empty((n,), dtype=torch.float32, device=dev)
-    rgb = None if density_only else _empty((n, 3), dtype=torch.float32, device=dev)
-    with _on(dev):
-        _lib.check(_lib.load().tn_mlp_forward_gather(m.handle, n, S, _ptr(vertex_indices), _ptr(barycentric_coordinates),
-                                                     _ptr(field_vm), _ptr(dirs), _mode(mode), _ptr(sigma), _ptr(rgb),
-                                                     _ptr(None if density_only else _ray_bias(ray_head_bias, n // S, dev)),
-                                                     _ptr(count), _stream(dev)))
-    return sigma if density_only else (sigma, rgb)
+    return _forward_gather(False, None, None, vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray, mode,
+                           ray_head_bias, count, None, None)
 
 
 # ---- per-tetrahedron occupancy field (the reference registers `tetrahedra_occupancy`, model.py:98-99,256-265, and never uses it)
@@ -969,33 +988,8 @@ def mlp_forward_gather_indexed(live, live_count, vertex_indices, barycentric_coo
     tensors to store into (what cull_samples zeroed at the culled samples); positions that are not listed are NOT written --
     without them fresh (unwritten) tensors are returned.  For every listed sample the result is bit for bit mlp_forward_gather's
     in the same mode; mode "fp32" or "bf16x3" ("bf16" has no indexed kernel).  dirs=None: density only -> sigma."""
-    density_only = dirs is None
-    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
-    _check(_MODES.get(mode) != 2, 'mlp_forward_gather_indexed: mlp mode must be "fp32" or "bf16x3": the plain-bf16 kernel has no '
-                                  'indexed form')
-    dev = field.device
-    for x, name in ((live, "live"), (live_count, "live_count")):
-        _check_input(x, name)
-        _check(x.dtype == torch.int32 and x.device == dev, f"{name} must be an int32 tensor on the field's device")
-    _check(live.numel() >= n and live_count.numel() >= 1, "live must hold n entries, live_count one")
-    _check_count(count, S, n, "mlp_forward_gather_indexed")
-    m = fused_mlp(weights)
-    field_vm = field_vertex_major(field)
-    if sigma is None:
-        sigma = _empty((n,), dtype=torch.float32, device=dev)
-    if rgb is None and not density_only:
-        rgb = _empty((n, 3), dtype=torch.float32, device=dev)
-    _check_input(sigma, "sigma")
-    _check(sigma.dtype == torch.float32 and sigma.numel() == n and sigma.device == dev, "sigma must be f32 [n]")
-    if not density_only:
-        _check_input(rgb, "rgb")
-        _check(rgb.dtype == torch.float32 and rgb.numel() == 3 * n and rgb.device == dev, "rgb must be f32 [n, 3]")
-    with _on(dev):
-        _lib.check(_lib.load().tn_mlp_forward_gather_indexed(
-            m.handle, n, S, _ptr(live), _ptr(live_count), _ptr(vertex_indices), _ptr(barycentric_coordinates), _ptr(field_vm), _ptr(dirs),
-            _mode(mode), _ptr(sigma), None if density_only else _ptr(rgb),
-            _ptr(None if density_only else _ray_bias(ray_head_bias, n // S, dev)), _ptr(count), _stream(dev)))
-    return sigma if density_only else (sigma, rgb)
+    return _forward_gather(True, live, live_count, vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray, mode,
+                           ray_head_bias, count, sigma, rgb)
 
 
 class _RgbBackground(C.Structure):   # tn_rgb_background
@@ -1170,11 +1164,54 @@ class _MlpBackwardBuffers(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("x0", "h1", "h2", "h3", "h4", "masks", "d1", "d2", "d3", "d4", "dhead", "dx0")]
 
 
+def _backward_buffers(acts, masks, chain=None, dx0=None):
+    """tn_mlp_backward_buffers of a training call: acts f32 [576, n] = x0 [64, n] on top of h1..h4 [128, n] each, masks i64
+    [4, n, 2], chain f32 [516, n] = d1..d4 [128, n] on top of dhead [4, n], dx0 f32 [n, 64]; None (or without a column): null
+    pointers."""
+    def rows(t, firsts):
+        if t is None or not t.numel():
+            return (None,) * len(firsts)
+        base, step = t.data_ptr(), t.stride(0) * t.element_size()
+        return tuple(base + f * step for f in firsts)
+
+    return _MlpBackwardBuffers(*rows(acts, (0, 64, 192, 320, 448)), _ptr(masks), *rows(chain, (0, 128, 256, 384, 512)), _ptr(dx0))
+
+
 class MlpSaved:
     """What mlp_forward_gather_train leaves for mlp_backward: the layer inputs x0 [64,n], h1..h4 [128,n] (quad-major
     [F/4][n][4], opaque to the caller: the operands of the weight-gradient GEMMs) and the ReLU masks [4,n,2] (all the dX kernel needs).  (`sigma` / `rgb` are the
     forward's outputs as returned; an autograd node must hold them through save_for_backward, not through this object.)"""
     __slots__ = ("acts", "masks", "sigma", "rgb", "n", "S")
+
+
+def _forward_gather_train(listed, live, n_live, vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray,
+                          ray_head_bias, mode, sigma, rgb):
+    """mlp_forward_gather_train (listed=False: every sample has a column of the saves) and mlp_forward_gather_train_indexed
+    (listed=True: the columns are the n_live listed samples): checks, handle, field shadow, outputs, saves and the call."""
+    mode = _mode(mode, inference=False)
+    _check_input(dirs, "dirs")   # (no density-only form: the training forward is the full network)
+    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
+    dev = field.device
+    sv = MlpSavedIndexed() if listed else MlpSaved()
+    sv.n, sv.S = n, S
+    if listed:
+        sv.n, sv.n_samples, sv.live = int(n_live), n, live
+        _check_live_list(live, sv.n, dev)
+    m = fused_mlp(weights)
+    field_vm = field_vertex_major(field)
+    sv.sigma = _given_or_fresh(sigma, "sigma", (n,), dev, f"sigma must be f32 with {n} elements")
+    sv.rgb = _given_or_fresh(rgb, "rgb", (n, 3), dev, f"rgb must be f32 with {3 * n} elements")
+    sv.acts = _empty((64 + 4 * 128, sv.n), dtype=torch.float32, device=dev)
+    sv.masks = _empty((4, sv.n, 2), dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    with _on(dev):
+        args = (_ptr(vertex_indices), _ptr(barycentric_coordinates), _ptr(field_vm), _ptr(dirs.contiguous()), mode, _ptr(sv.sigma),
+                _ptr(sv.rgb), C.byref(_backward_buffers(sv.acts, sv.masks)), _ptr(_ray_bias(ray_head_bias, n // S, dev)), _stream(dev))
+        if listed:
+            _lib.check(lib.tn_mlp_forward_gather_train_indexed(m.handle, sv.n, n, S, _ptr(live), *args))
+        else:
+            _lib.check(lib.tn_mlp_forward_gather_train_ex(m.handle, n, S, *args))
+    return sv.sigma, sv.rgb, sv
 
 
 def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray, ray_head_bias=None,
@@ -1183,29 +1220,8 @@ def mlp_forward_gather_train(vertex_indices, barycentric_coordinates, field, dir
     mlp_backward, which then recomputes nothing.  mode: "fp32" (default) or "bf16x3" (tn_mlp_forward_gather_train_ex): sigma /
     rgb are then mlp_forward_gather(mode="bf16x3")'s bits and `saved` holds that forward's activations and ReLU masks in the
     same layouts; mlp_backward runs on them in either arithmetic of its own (adjoint_mode), chosen independently."""
-    mode = _mode(mode, inference=False)
-    _check_input(dirs, "dirs")   # (no density-only form: the training forward is the full network)
-    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
-    m = fused_mlp(weights)
-    dev = field.device
-    field_vm = field_vertex_major(field)
-    sv = MlpSaved()
-    sv.n, sv.S = n, S
-    sv.sigma = _empty((n,), dtype=torch.float32, device=dev)
-    sv.rgb = _empty((n, 3), dtype=torch.float32, device=dev)
-    sv.acts = _empty((64 + 4 * 128, n), dtype=torch.float32, device=dev)
-    sv.masks = _empty((4, n, 2), dtype=torch.int64, device=dev)
-    a = sv.acts
-    bs = _MlpBackwardBuffers(a[0:64].data_ptr(), a[64:192].data_ptr(), a[192:320].data_ptr(), a[320:448].data_ptr(),
-                             a[448:576].data_ptr(), sv.masks.data_ptr(), None, None, None, None, None, None)
-    head = (m.handle, n, S, _ptr(vertex_indices), _ptr(barycentric_coordinates), _ptr(field_vm), _ptr(dirs.contiguous()))
-    tail = (_ptr(sv.sigma), _ptr(sv.rgb), C.byref(bs), _ptr(_ray_bias(ray_head_bias, n // S, dev)), _stream(dev))
-    with _on(dev):
-        if mode == 0:       # the default goes through the entry it always went through
-            _lib.check(_lib.load().tn_mlp_forward_gather_train(*head, *tail))
-        else:
-            _lib.check(_lib.load().tn_mlp_forward_gather_train_ex(*head, mode, *tail))
-    return sv.sigma, sv.rgb, sv
+    return _forward_gather_train(False, None, None, vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray,
+                                 ray_head_bias, mode, None, None)
 
 
 class MlpSavedIndexed(MlpSaved):
@@ -1248,35 +1264,8 @@ def mlp_forward_gather_train_indexed(live, n_live, vertex_indices, barycentric_c
     The forward itself tolerates a list entry >= n (it stores no output for it); mlp_backward does NOT: it compacts rows by the
     list without a bound (tn_compact_rows), so only a list whose every entry is a sample -- what cull_samples writes -- may go on
     to the backward."""
-    mode = _mode(mode, inference=False)
-    _check_input(dirs, "dirs")
-    n, S = _check_gather_args(field, dirs, samples=(vertex_indices, barycentric_coordinates, samples_per_ray))
-    dev = field.device
-    n_live = int(n_live)
-    _check_live_list(live, n_live, dev)
-    m = fused_mlp(weights)
-    field_vm = field_vertex_major(field)
-    if sigma is None:
-        sigma = _empty((n,), dtype=torch.float32, device=dev)
-    if rgb is None:
-        rgb = _empty((n, 3), dtype=torch.float32, device=dev)
-    for x, name, k in ((sigma, "sigma", n), (rgb, "rgb", 3 * n)):
-        _check_input(x, name)
-        _check(x.dtype == torch.float32 and x.numel() == k and x.device == dev, f"{name} must be f32 with {k} elements")
-    sv = MlpSavedIndexed()
-    sv.n, sv.S, sv.n_samples, sv.live = n_live, S, n, live
-    sv.sigma, sv.rgb = sigma, rgb
-    sv.acts = _empty((64 + 4 * 128, n_live), dtype=torch.float32, device=dev)
-    sv.masks = _empty((4, n_live, 2), dtype=torch.int64, device=dev)
-    a = sv.acts
-    bs = _MlpBackwardBuffers(a[0:64].data_ptr(), a[64:192].data_ptr(), a[192:320].data_ptr(), a[320:448].data_ptr(),
-                             a[448:576].data_ptr(), sv.masks.data_ptr(), None, None, None, None, None, None)
-    with _on(dev):
-        _lib.check(_lib.load().tn_mlp_forward_gather_train_indexed(
-            m.handle, n_live, n, S, _ptr(live), _ptr(vertex_indices), _ptr(barycentric_coordinates), _ptr(field_vm),
-            _ptr(dirs.contiguous()), mode, _ptr(sigma), _ptr(rgb), C.byref(bs), _ptr(_ray_bias(ray_head_bias, n // S, dev)),
-            _stream(dev)))
-    return sigma, rgb, sv
+    return _forward_gather_train(True, live, n_live, vertex_indices, barycentric_coordinates, field, dirs, weights, samples_per_ray,
+                                 ray_head_bias, mode, sigma, rgb)
 
 
 class MlpChain:
@@ -1299,12 +1288,12 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
     want_bary_grad: dL/d barycentric_coordinates [n, 3], the gather's adjoint w.r.t. the barycentrics on the same d x0 rows
     (tn_interpolate_values_backward_bary_vm; tet membership is a constant of it); return_dx0: those rows, d x0 [n, 64];
     return_chain: an MlpChain with views of everything the dX chain wrote.
-    adjoint_mode: arithmetic of the dX chain, independent of the forward's.  "fp32" (default): tn_mlp_backward.  "bf16x3"
-    (tn_mlp_backward_ex, mode 1): its four matrix products on the bf16 matrix cores, three bf16 pieces per operand; softplus' /
+    adjoint_mode: arithmetic of the dX chain (tn_mlp_backward_ex), independent of the forward's.  "fp32" (default; mode 0 is
+    tn_mlp_backward).  "bf16x3" (mode 1): its four matrix products on the bf16 matrix cores, three bf16 pieces per operand; softplus' /
     sigmoid', the head layer's gradient d4, the density term and the masks stay fp32 (dhead and d4 are the default's bits), and
     so does the gather adjoint, which reads the same buffers.  "bf16" is not an adjoint arithmetic.
-    dw_mode: arithmetic of the four weight-gradient GEMMs, independent of the other two.  "fp32" (default): tn_mlp_param_grads.
-    "bf16x3" (tn_mlp_param_grads_ex, mode 1): both streamed operands split into three bf16 pieces as they are staged, six
+    dw_mode: arithmetic of the four weight-gradient GEMMs (tn_mlp_param_grads_ex), independent of the other two.  "fp32" (default;
+    mode 0 is tn_mlp_param_grads).  "bf16x3" (mode 1): both streamed operands split into three bf16 pieces as they are staged, six
     products per multiply on the bf16 matrix cores, fp32 accumulation; the bias gradients, d wd and the rgb head stay fp32;
     still without atomics, bit-reproducible.  grad_field does not depend on it.  "bf16" is not a training arithmetic.
     saved an MlpSavedIndexed (mlp_forward_gather_train_indexed; occupancy-culled training): every argument still covers all
@@ -1345,27 +1334,18 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
     grads = [flat[o:o + k].view(tuple(w.shape)) for o, k, w in zip(offs, sizes, keep)]
     gs = _MlpWeightsStruct(*[g.data_ptr() for g in grads])
     grad_vm = torch.zeros((V, 64), dtype=torch.float32, device=dev)
-    a = saved.acts
     buf = _empty((4 * 128 + 4, n), dtype=torch.float32, device=dev)
     rows = _empty((n, 64), dtype=torch.float32, device=dev)     # d x0, sample-major
-    bs = _MlpBackwardBuffers(a[0:64].data_ptr(), a[64:192].data_ptr(), a[192:320].data_ptr(), a[320:448].data_ptr(),
-                             a[448:576].data_ptr(), saved.masks.data_ptr(), buf[0:128].data_ptr(), buf[128:256].data_ptr(),
-                             buf[256:384].data_ptr(), buf[384:512].data_ptr(), buf[512:516].data_ptr(), rows.data_ptr())
+    bs = _backward_buffers(saved.acts, saved.masks, buf, rows)
     stream = _stream(dev)
     some = n > 0 or live is None      # (an empty list: nothing to launch, every sum is empty)
     with _on(dev):
-        head = (mh.handle, n, _ptr(sigma.contiguous()), _ptr(rgb.contiguous()), _ptr(d_sigma), _ptr(d_rgb), C.byref(bs))
-        if not some:
-            pass
-        elif amode == 0:    # the default goes through the entry it always went through
-            _lib.check(lib.tn_mlp_backward(*head, stream))
-        else:
-            _lib.check(lib.tn_mlp_backward_ex(*head, amode, stream))
+        if some:
+            _lib.check(lib.tn_mlp_backward_ex(mh.handle, n, _ptr(sigma.contiguous()), _ptr(rgb.contiguous()), _ptr(d_sigma), _ptr(d_rgb),
+                                              C.byref(bs), amode, stream))
         if live is not None:
             _lib.check(lib.tn_mlp_param_grads_indexed(mh.handle, n, nfull, S, _ptr(live), _ptr(dirs), C.byref(bs), C.byref(gs), wmode,
                                                       stream))
-        elif wmode == 0:    # the default goes through the entry it always went through
-            _lib.check(lib.tn_mlp_param_grads(mh.handle, n, S, _ptr(dirs), C.byref(bs), C.byref(gs), stream))
         else:
             _lib.check(lib.tn_mlp_param_grads_ex(mh.handle, n, S, _ptr(dirs), C.byref(bs), C.byref(gs), wmode, stream))
         d_ray_bias = None
