@@ -521,6 +521,29 @@ int tn_mlp_forward_gather_indexed(tn_mlp_t mlp, size_t n_max, uint32_t samples_p
                                   const float *field_vm, const float *dirs, int mode, float *sigma, float *rgb,
                                   const float *ray_head_bias, const uint32_t *count, void *stream);
 
+/* ---- occupancy-guided coarse sampler (addition; model.py:98-99,256-265 declares the occupancy field and leaves it unused) -----
+ * One wavefront per HITTING ray; the trace rows (num_visited u32 [R], visited u32 [R,M], hit_distances f32 [R,M,2]) are read in
+ * place through ray_index u32 [r]; count as for tn_sample_coarse (rows from *count on are left unwritten).
+ * A segment k of a ray is LIVE unless tn_cull_samples would cull its cell (visited < num_cells and occupancy[visited] <
+ * threshold; invalid ids and a NaN occupancy are live, threshold <= 0 makes every segment live); w_k = max(t_out_k - t_in_k, 0)
+ * for a live segment, else 0; cum = the prefix sums of w, L = their total.  A ray with L == 0 counts every segment live; a row
+ * without a segment has near = 0, L = 1.  The LIVE-LENGTH coordinate s in [near, near + L] closes culled space up.
+ * tn_sample_live (model.py:98-99,256-265): near_far_live f32 [r,2] = (first t_in, first t_in + L) and s_edges f32 [r, S+1] =
+ *   tn_sample_coarse's uniform edges over that span (linspace f32 [S+1], t_rand f32 [r, S+1] or NULL, as there).
+ * tn_live_to_distance (model.py:98-99,256-265): values f32 [r,n] in the live-length coordinate (bin centres, edges, a depth) ->
+ *   t f32 [r,n] distances and slot u32 [r,n] segment indices: s' = clamp(s - near, 0, L), k = the first segment with cum[k+1] >
+ *   s' (none: the last with w > 0), t = min(t_in_k + clamp((s' - cum[k]) / w_k, 0, 1) len_k, t_out_k): always inside a live
+ *   segment of positive length when the ray has one.  A row without a segment: t = s, slot = 0.
+ * Both need (max_ray_triangles + 1) * 16 B <= 64 KB of LDS per block and fail with a message beyond (as the biased sampler). */
+int tn_sample_live(size_t num_hit_rays, uint32_t num_samples, uint32_t max_ray_triangles, const uint32_t *ray_index,
+                   const uint32_t *num_visited, const uint32_t *visited, const float *hit_distances, const float *occupancy,
+                   uint32_t num_cells, float threshold, const float *linspace, const float *t_rand, float *s_edges,
+                   float *near_far_live, const uint32_t *count, void *stream);
+int tn_live_to_distance(size_t num_hit_rays, uint32_t num_values, uint32_t max_ray_triangles, const uint32_t *ray_index,
+                        const uint32_t *num_visited, const uint32_t *visited, const float *hit_distances, const float *occupancy,
+                        uint32_t num_cells, float threshold, const float *values, float *t, uint32_t *slot, const uint32_t *count,
+                        void *stream);
+
 /* background colour of nerfstudio's RGBRenderer as the reference model configures / overrides it (model.py:466,504-518;
  * `renderers.BACKGROUND_COLOR_OVERRIDE`): comp_rgb + background (1 - accumulation).  clamp != 0 = the renderer's
  * evaluation mode (RGBRenderer.forward when not training): nan_to_num of the sample colours, result clamped to [0, 1].

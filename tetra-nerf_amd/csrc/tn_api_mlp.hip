@@ -484,6 +484,33 @@ int tn_sample_pdf(size_t num_hit_rays, uint32_t num_samples, uint32_t num_fine, 
     });
 }
 
+int tn_sample_live(size_t num_hit_rays, uint32_t num_samples, uint32_t M, const uint32_t *ray_index, const uint32_t *num_visited,
+                   const uint32_t *visited, const float *hit_distances, const float *occupancy, uint32_t num_cells, float threshold,
+                   const float *linspace, const float *t_rand, float *s_edges, float *near_far_live, const uint32_t *count, void *stream_) {
+    return guarded([&] {
+        if (num_hit_rays == 0) return;
+        if (!ray_index || !num_visited || !visited || !hit_distances || !linspace || !s_edges || !near_far_live || (num_cells && !occupancy))
+            throw tn::Error("null pointer");
+        if (num_samples == 0) throw tn::Error("num_samples must be positive");
+        tn::launch_sample_live(num_hit_rays, num_samples, M, ray_index, num_visited, visited, hit_distances, occupancy, num_cells, threshold,
+                               linspace, t_rand, s_edges, near_far_live, (hipStream_t)stream_, count);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_live_to_distance(size_t num_hit_rays, uint32_t num_values, uint32_t M, const uint32_t *ray_index, const uint32_t *num_visited,
+                        const uint32_t *visited, const float *hit_distances, const float *occupancy, uint32_t num_cells, float threshold,
+                        const float *values, float *t, uint32_t *slot, const uint32_t *count, void *stream_) {
+    return guarded([&] {
+        if (num_hit_rays == 0 || num_values == 0) return;
+        if (!ray_index || !num_visited || !visited || !hit_distances || !values || !t || !slot || (num_cells && !occupancy))
+            throw tn::Error("null pointer");
+        tn::launch_live_to_distance(num_hit_rays, num_values, M, ray_index, num_visited, visited, hit_distances, occupancy, num_cells,
+                                    threshold, values, t, slot, (hipStream_t)stream_, count);
+        TN_HIP(hipGetLastError());
+    });
+}
+
 int tn_composite_backward(size_t num_rays, uint32_t num_samples, const float *sigma, const float *rgb, const float *edges,
                           const tn_rgb_background *background, const float *d_out_rgb, const float *d_out_acc, float *d_sigma,
                           float *d_rgb, void *stream_) {

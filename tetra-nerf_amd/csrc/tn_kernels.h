@@ -316,6 +316,14 @@ void launch_sample_coarse(size_t r, uint32_t S, uint32_t M, const uint32_t *ray_
 void launch_sample_pdf(size_t r, uint32_t S, uint32_t num_fine, const float *edges, const float *weights, const float *near_far,
                        const float *u_table, const float *u_rand, float histogram_padding, float eps, float *out, hipStream_t stream,
                        const uint32_t *count = nullptr);
+// occupancy-guided coarse sampler (tn_live_sampler.hip): s_edges [r, S+1] in the live-length coordinate + near_far_live [r, 2];
+// the map back: values [r, n] -> t [r, n], slot [r, n].  visited u32 [R, M], occupancy f32 [T] (nullable when T == 0)
+void launch_sample_live(size_t r, uint32_t S, uint32_t M, const uint32_t *ray_index, const uint32_t *num_visited, const uint32_t *visited,
+                        const float *hit_dist, const float *occupancy, uint32_t T, float threshold, const float *lin, const float *t_rand,
+                        float *edges, float *near_far, hipStream_t stream, const uint32_t *count = nullptr);
+void launch_live_to_distance(size_t r, uint32_t n, uint32_t M, const uint32_t *ray_index, const uint32_t *num_visited,
+                             const uint32_t *visited, const float *hit_dist, const float *occupancy, uint32_t T, float threshold,
+                             const float *values, float *t, uint32_t *slot, hipStream_t stream, const uint32_t *count = nullptr);
 // ray_index (nullable): out_rgb / out_acc / out_depth are arrays over ALL rays of the call and row q is written at ray_index[q]
 void launch_composite(size_t R, uint32_t S, const float *sigma, const float *rgb, const float *edges, Background background,
                       float *out_rgb, float *out_acc, float *out_depth, float *out_weights, hipStream_t stream,

@@ -156,6 +156,73 @@ __device__ __forceinline__ void ray_sample_coarse(uint32_t S, uint32_t M, size_t
     ray_sample_coarse_nf(S, M, ray, nb, near, far, hit_dist, lin, t_row, biased, edges, nullptr, cum, lane);
 }
 
+// Live lengths of one ray for the occupancy-guided sampler (render.live_lengths_statement; the reference declares the occupancy
+// field and never uses it, model.py:98-99,256-265): w_k = max(t_out_k - t_in_k, 0) for a LIVE segment -- one that
+// cull_mask_statement would not cull: cell_k >= T, or not occupancy[cell_k] < threshold -- else 0.  cum [nb + 1] (M + 1 floats
+// of LDS owned by the wave): cum[0] = 0, cum[k + 1] = the running MAXIMUM over the segments j <= k with w_j > 0 of the prefix
+// sum w_0 + .. + w_j -- the prefix sums themselves, made non-decreasing and exactly flat over every segment of weight 0
+// whatever the summation tree of the wave scan rounds to, so that "first k with cum[k + 1] > s" always names a segment with
+// w_k > 0.  A ray whose live length is 0 (everything culled) is redone with every segment live.  Returns near = the first t_in,
+// L = cum[nb], last = the last segment with w > 0 (0 without one); a row without a segment: (0, 1, 0), cum[0] = 0.
+struct LiveCum { float near, L; uint32_t last; };
+constexpr int LIVE_CH = 4;    // chunks of 64 segments (ray_live_cum) / of 64 values (ray_live_to_distance) in flight per wave
+
+__device__ __forceinline__ LiveCum ray_live_cum(uint32_t M, size_t ray, uint32_t nb, const uint32_t *__restrict__ visited,
+                                                const float *__restrict__ hit_dist, const float *__restrict__ occupancy, uint32_t T,
+                                                float threshold, float *cum, int lane) {
+    if (nb > M) nb = M;
+    const float2 *row = reinterpret_cast<const float2 *>(hit_dist + ray * (size_t)M * 2);
+    const uint32_t *vis = visited + ray * (size_t)M;
+    LiveCum res;
+    res.near = 0.f; res.L = 1.f; res.last = 0;
+    if (lane == 0) cum[0] = 0.f;
+    if (nb == 0) { lds_sync(); return res; }
+    res.near = row[0].x;
+    const bool culls = T > 0 && threshold > 0.f;
+    for (int pass = 0; pass < 2; ++pass) {
+        float carry = 0.f, top = 0.f;
+        uint32_t last = 0;
+        for (uint32_t base0 = 0; base0 < nb; base0 += 64 * LIVE_CH) {
+            float w[LIVE_CH], inc[LIVE_CH], mx[LIVE_CH];
+#pragma unroll
+            for (int c = 0; c < LIVE_CH; ++c) {
+                const uint32_t k = base0 + 64u * c + lane;
+                w[c] = 0.f;
+                if (k < nb) {
+                    const float2 s = row[k];
+                    bool live = true;
+                    if (culls && pass == 0) {
+                        const uint32_t cell = vis[k];
+                        if (cell < T) live = !(occupancy[cell] < threshold);
+                    }
+                    w[c] = live ? fmaxf(s.y - s.x, 0.f) : 0.f;
+                }
+                inc[c] = w[c];
+            }
+            wave_incl_scan_multi<LIVE_CH>(inc, lane);
+#pragma unroll
+            for (int c = 0; c < LIVE_CH; ++c) {
+                mx[c] = w[c] > 0.f ? carry + inc[c] : 0.f;
+                carry += __shfl(inc[c], 63);
+            }
+            wave_incl_max_multi<LIVE_CH>(mx, lane);
+#pragma unroll
+            for (int c = 0; c < LIVE_CH; ++c) {
+                const uint32_t k = base0 + 64u * c + lane;
+                const float m = fmaxf(mx[c], top);
+                if (k < nb) cum[k + 1] = m;
+                top = __shfl(m, 63);
+                const uint64_t pos = __ballot(w[c] > 0.f);
+                if (pos) last = base0 + 64u * c + (63u - (uint32_t)__clzll((long long)pos));
+            }
+        }
+        res.L = top; res.last = last;
+        if (top > 0.f || !culls) break;
+    }
+    lds_sync();
+    return res;
+}
+
 // The binary searches of searchsorted / the merge by rank, for the CH items a lane owns AT ONCE: the classic lo / hi / mid loop
 // with a fixed trip count (K >= the longest search; a finished item idles), so every item visits exactly the mids the plain
 // loop visits -- same result on any array, sorted or not -- while the LDS reads of the CH items overlap instead of forming one
@@ -184,6 +251,49 @@ __device__ __forceinline__ void multi_search(const float *arr, uint32_t N, const
     }
 #pragma unroll
     for (int c = 0; c < CH; ++c) res[c] = lo[c];
+}
+
+// render.live_to_distance_statement for n values of one ray, after ray_live_cum (cum, lc): s' = clamp(s - near, 0, L); k = the
+// first segment with cum[k + 1] > s' (multi_search: LIVE_CH values per lane, their reads issued together), or the last segment
+// with w > 0 when there is none; the segment's row is gathered after the search; t = min(t_in + frac len, t_out) with frac =
+// clamp((s' - cum[k]) / len, 0, 1) -- w_k = len_k at every segment the search can name -- so t lies inside segment k bit-wise.
+// A row without a segment: t = s, slot 0.  s [n]; out: t [n], slot [n] of THIS ray.
+__device__ __forceinline__ void ray_live_to_distance(uint32_t n, uint32_t M, size_t ray, uint32_t nb, const float *__restrict__ hit_dist,
+                                                     const float *__restrict__ s, const LiveCum &lc, const float *cum,
+                                                     float *__restrict__ t, uint32_t *__restrict__ slot, int lane) {
+    if (nb > M) nb = M;
+    const float2 *row = reinterpret_cast<const float2 *>(hit_dist + ray * (size_t)M * 2);
+    for (uint32_t base0 = 0; base0 < n; base0 += 64 * LIVE_CH) {
+        float v[LIVE_CH], sv[LIVE_CH];
+        bool on[LIVE_CH];
+        uint32_t k[LIVE_CH];
+#pragma unroll
+        for (int c = 0; c < LIVE_CH; ++c) {
+            const uint32_t j = base0 + 64u * c + lane;
+            on[c] = j < n;
+            sv[c] = on[c] ? s[j] : 0.f;
+            v[c] = fminf(fmaxf(sv[c] - lc.near, 0.f), lc.L);
+        }
+        multi_search<LIVE_CH, true>(cum + 1, nb, v, on, k);      // entries of cum[1 .. nb] that are <= s'
+        float2 seg[LIVE_CH];
+        float c0[LIVE_CH];
+#pragma unroll
+        for (int c = 0; c < LIVE_CH; ++c) {
+            if (k[c] >= nb) k[c] = lc.last;
+            seg[c] = make_float2(0.f, 0.f);
+            c0[c] = 0.f;
+            if (on[c] && nb) { seg[c] = row[k[c]]; c0[c] = cum[k[c]]; }
+        }
+#pragma unroll
+        for (int c = 0; c < LIVE_CH; ++c) {
+            const uint32_t j = base0 + 64u * c + lane;
+            if (!on[c]) continue;
+            const float len = fmaxf(seg[c].y - seg[c].x, 0.f);
+            const float frac = len > 0.f ? fminf(fmaxf((v[c] - c0[c]) / len, 0.f), 1.f) : 0.f;
+            t[j] = nb ? fminf(seg[c].x + frac * len, seg[c].y) : sv[c];
+            slot[j] = k[c];
+        }
+    }
 }
 
 // floats of LDS ray_sample_pdf needs per wave

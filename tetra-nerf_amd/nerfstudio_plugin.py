@@ -338,6 +338,11 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
             batch = rd._tn_train_batches = getattr(rd, "_tn_train_batches", 0) + 1
             if every < 1 or batch % every != 0:
                 kw["occupancy"], kw["occupancy_threshold"] = occupancy, float(train_threshold)
+                if getattr(model.config, "occupancy_sampler", False):
+                    # opt-in (an absent field: off): the culled batches place their samples in live tetrahedra only
+                    # (TetraRenderer.render_train: occupancy_sampler); the unculled refresh batches keep the ordinary sampler, which is
+                    # how a culled tetrahedron still gets seen
+                    kw["occupancy_sampler"] = True
         return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
                                ray_head_bias=hb, **kw)
     kw = {}
@@ -346,6 +351,8 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
     if occupancy is not None and threshold is not None:
         # opt-in as above: samples in tetrahedra whose occupancy is below the threshold skip the network (TetraRenderer.render)
         kw["occupancy"], kw["occupancy_threshold"] = occupancy, float(threshold)
+        if getattr(model.config, "occupancy_sampler", False):
+            kw["occupancy_sampler"] = True      # opt-in: the S samples go where something is (TetraRenderer.render)
     eval_mode = getattr(model.config, "eval_mlp_mode", None)
     if eval_mode is not None:
         # opt-in like train_mlp_mode (an absent field, as in the reference's config: the renderer's own fp32): "bf16" = the fast

@@ -329,6 +329,77 @@ def cull_mask_statement(cells: torch.Tensor, occupancy: torch.Tensor, threshold:
     return valid & (occupancy.detach()[c.clamp(0, T - 1)] < float(threshold))
 
 
+def live_lengths_statement(num_visited_cells: torch.Tensor, visited_cells: torch.Tensor, hit_distances: torch.Tensor,
+                           occupancy: torch.Tensor, threshold: float) -> Dict[str, torch.Tensor]:
+    """Statement of the LIVE LENGTHS of traced rays, the base of the occupancy-guided sampler (tn_sample_live / tn_live_to_distance
+    compute it per ray; dtype-generic: it runs in the dtype of `hit_distances`).  Rows [r,M] / [r,M,2] of r rays, nb =
+    num_visited_cells segments each:
+        len_k = max(t_out_k - t_in_k, 0);  segment k is LIVE unless cull_mask_statement would cull its cell (invalid ids and a NaN
+        occupancy are live, threshold <= 0 makes every segment live);  w_k = len_k for a live segment, else 0;
+        cum_0 = 0, cum_{k+1} = cum_k + w_k, L = cum_nb, near = t_in_0.
+    The prefix sums are made non-decreasing and exactly flat over every segment of weight 0 whatever the summation rounds to (a
+    running maximum over the sums at the segments with w > 0: the identity in exact arithmetic), so that "the first k with
+    cum_{k+1} > s" always names a segment with w_k > 0.  A ray with L == 0 (everything culled) counts every segment live: its
+    samples are culled later anyway.  A row without a segment has near = 0, L = 1.
+    Returns {"w" [r,M], "cum" [r,M+1], "near" [r,1], "length" [r,1] = L, "num_visited" [r,1] int64, "hit_distances"}."""
+    hd = hit_distances
+    nb = num_visited_cells.long()[:, None]
+    M = hd.shape[1]
+    inside = torch.arange(M, device=hd.device)[None] < nb
+    zero = torch.zeros((), dtype=hd.dtype, device=hd.device)
+    lengths = torch.where(inside, (hd[..., 1] - hd[..., 0]).clamp_min(0), zero)
+    live = inside & ~cull_mask_statement(visited_cells, occupancy, threshold)
+
+    def sums(w):
+        top = torch.cummax(torch.where(w > 0, torch.cumsum(w, 1), zero), 1).values
+        return torch.cat([torch.zeros_like(top[:, :1]), top], 1)
+
+    w = torch.where(live, lengths, zero)
+    cum = sums(w)
+    dead = cum[:, -1:] == 0
+    w, cum = torch.where(dead, lengths, w), torch.where(dead, sums(lengths), cum)
+    hit = nb > 0
+    return {"w": w, "cum": cum, "near": torch.where(hit, hd[:, 0, :1], zero), "length": torch.where(hit, cum[:, -1:], zero + 1),
+            "num_visited": nb, "hit_distances": hd}
+
+
+def live_to_distance_statement(s: torch.Tensor, live: Dict[str, torch.Tensor]):
+    """The inverse map of the live-length coordinate (tn_live_to_distance): s [r,n] in [near, near + L] -> (t [r,n] distances,
+    slot [r,n] int64 segment indices), `live` from live_lengths_statement:
+        s' = clamp(s - near, 0, L);  k = the first segment with cum_{k+1} > s', or the last segment with w_k > 0 when there is none;
+        frac = clamp((s' - cum_k) / w_k, 0, 1);  t = min(t_in_k + frac len_k, t_out_k);  slot = k.
+    A mapped value lies inside a live segment.  A row without a segment: t = s, slot = 0."""
+    w, cum, hd, nb = live["w"], live["cum"], live["hit_distances"], live["num_visited"]
+    M = w.shape[1]
+    sp = torch.minimum((s - live["near"]).clamp_min(0), live["length"])
+    k = torch.searchsorted(cum[:, 1:].contiguous(), sp.contiguous(), right=True)
+    last = ((w > 0) * torch.arange(M, device=w.device)[None]).max(1, keepdim=True).values
+    k = torch.where(k >= nb, last.expand_as(k), k).clamp(0, M - 1)
+    t_in, t_out = torch.gather(hd[..., 0], 1, k), torch.gather(hd[..., 1], 1, k)
+    wk = torch.gather(w, 1, k)
+    frac = torch.where(wk > 0, ((sp - torch.gather(cum, 1, k)) / wk).clamp(0, 1), torch.zeros_like(sp))
+    t = torch.minimum(t_in + frac * (t_out - t_in).clamp_min(0), t_out)
+    none = nb == 0
+    return torch.where(none, s, t), torch.where(none, torch.zeros_like(k), k)
+
+
+def live_sample_bins(live: Dict[str, torch.Tensor], num_samples: int, t_rand: Optional[torch.Tensor] = None):
+    """The occupancy-guided coarse sampler (tn_sample_live): (s_edges [r,S+1], near_far_live = (near [r,1], near + L [r,1])) --
+    the UniformSampler's bins (stratified with `t_rand` [r,S+1]) over the live-length span of every ray.  The edges are
+    live-length coordinates: a pass locates live_to_distance_statement(bin_centres(s_edges)) and composites with s_edges, whose
+    deltas are the live lengths inside the bins."""
+    near, far = live["near"], live["near"] + live["length"]
+    return uniform_sample_bins(near, far, num_samples, t_rand), (near, far)
+
+
+def hit_far(out, idx: torch.Tensor) -> torch.Tensor:
+    """[r,1] last exit distance of the rays `idx` of a trace result, read in place; 1 for a ray without a segment (the padded
+    entries of a batch that misses altogether: their rows may be unwritten)."""
+    nb = out["num_visited_cells"][idx].long()
+    far = out["hit_distances"][idx, (nb - 1).clamp_min(0), 1]
+    return torch.where(nb > 0, far, torch.ones_like(far))[:, None]
+
+
 def occupancy_from_field(cells: torch.Tensor, field: torch.Tensor, mlp, mode: str = "fp32") -> torch.Tensor:
     """A starting occupancy f32 [T] for a checkpoint that has none: the maximum density over five probes per tetrahedron -- the
     centroid and the four vertices -- through the density-only gather + MLP kernel (cpp.mlp_forward_gather(dirs=None)).
@@ -355,16 +426,22 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
                      directions: torch.Tensor, num_samples: int = 256, max_ray_triangles: int = 512,
                      far_plane: float = 1000.0, num_fine_samples: int = 0, biased: bool = False,
                      background=1.0, occupancy: Optional[torch.Tensor] = None,
-                     occupancy_threshold: Optional[float] = None) -> Dict[str, torch.Tensor]:
+                     occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False) -> Dict[str, torch.Tensor]:
     """Plain-PyTorch statement of the render path in EVALUATION mode (model.py:520-662 with `self.training == False`: the
     samplers do not jitter, the RGB renderer sanitises and clamps); `tracer` needs trace_rays / find_visited_cells
     returning tensors, `interpolate_values(vi, bc, field)` the gather.  Pinned by the reference's own `get_outputs`
     executed from its file (tests/test_reference_model.py).
     occupancy f32 [T] + occupancy_threshold (both or neither): the CULLED render -- sigma = 0 and rgb = 0 at the samples
     cull_mask_statement names, in both passes: the coarse weights, hence the PDF samples, see the masked densities, the final
-    composite the masked final samples."""
+    composite the masked final samples.
+    occupancy_sampler (with an occupancy): the occupancy-guided coarse sampler in the place of the uniform / biased one --
+    live_sample_bins places the S bins over the live length of every ray, both passes locate
+    live_to_distance_statement(bin_centres(s_edges)), the PDF sampler and the composite run on the live-length edges, and the
+    median depth is mapped back to a distance."""
     if (occupancy is None) != (occupancy_threshold is None):
         raise RuntimeError("occupancy and occupancy_threshold go together: pass both or neither")
+    if occupancy_sampler and occupancy is None:
+        raise RuntimeError("occupancy_sampler needs occupancy and occupancy_threshold: the field the samples follow")
     out = tracer.trace_rays(origins.contiguous(), directions.contiguous(), max_ray_triangles)
     nv = out["num_visited_cells"]
     nears = out["hit_distances"][:, 0, 0][:, None]
@@ -381,14 +458,23 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
 
         culled = None     # [r, S] of the current pass, with an occupancy
 
+        live = live_lengths_statement(lists[0], lists[1], lists[3], occupancy, occupancy_threshold) if occupancy_sampler else None
+
         def features(edges):
             nonlocal culled
-            traced = tracer.find_visited_cells(*lists, bin_centres(edges))
+            centres = bin_centres(edges)
+            if live is not None:
+                centres = live_to_distance_statement(centres, live)[0].contiguous()
+            traced = tracer.find_visited_cells(*lists, centres)
             if occupancy is not None:
                 culled = cull_mask_statement(traced["cell_indices"], occupancy, occupancy_threshold)
             return interpolate_values(traced["vertex_indices"], traced["barycentric_coordinates"], field)
 
-        edges, spacing = coarse_samples(near_r, far_r, num_samples, biased, lists[0], lists[3])
+        if live is None:
+            edges, spacing = coarse_samples(near_r, far_r, num_samples, biased, lists[0], lists[3])
+        else:
+            edges, (near_r, far_r) = live_sample_bins(live, num_samples)
+            spacing = (edges - near_r) / (far_r - near_r)
         feats = features(edges)
         if num_fine_samples > 0:
             sigma_c = coarse_sigma(mlp, feats)
@@ -403,6 +489,8 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
             sigma = torch.where(culled[..., None], torch.zeros_like(sigma), sigma)
             col = torch.where(culled[..., None], torch.zeros_like(col), col)
         rgb_r, acc_r, depth_r, w_r = composite(sigma, col, starts, ends, background=background, clamp=True)
+        if live is not None:
+            depth_r = live_to_distance_statement(depth_r, live)[0]
         rgb[ray_mask] = rgb_r
         acc[ray_mask] = acc_r
         depth[ray_mask] = depth_r
@@ -662,11 +750,40 @@ class TetraRenderer:
         return (self._background_rows(R, bg, dev), torch.zeros((R, 1), dtype=torch.float32, device=dev),
                 torch.full((R, 1), self.far_plane, dtype=torch.float32, device=dev))
 
-    def _locate(self, lists, edges, ray_index, count=None):
+    def _locate(self, lists, edges, ray_index, count=None, to_distance=None):
         """find_visited_cells of the bin centres of `edges` [r,S+1] on the trace rows in place: row i of the result belongs to
-        trace row ray_index[i]; count: device-side number of rows to match."""
+        trace row ray_index[i]; count: device-side number of rows to match.  to_distance (the occupancy-guided sampler): the
+        edges are live-length coordinates and the centres go through this map first."""
         kw = {} if count is None else {"count": count}
-        return self.tracer.find_visited_cells(*lists, bin_centres(edges), ray_index=ray_index, **kw)
+        centres = bin_centres(edges)
+        if to_distance is not None:
+            centres = to_distance(centres)
+        return self.tracer.find_visited_cells(*lists, centres, ray_index=ray_index, **kw)
+
+    def _live_sampler(self, lists, ray_index, occ, t_rand=None, count=None):
+        """The occupancy-guided coarse sampler of one call, occ = (occupancy, threshold): (s_edges [r,S+1] in the live-length
+        coordinate, near_far_live [r,2], to_distance) -- to_distance(values [r,n], out=None) maps live-length values (bin centres,
+        edges, a depth) to distances.  Device samplers: cpp.sample_live / cpp.live_to_distance on the trace rows in place
+        (count: device-side number of rows; `out`: a tensor to store into, so that rows beyond count keep what it holds);
+        otherwise the PyTorch statements on the rows of `ray_index`."""
+        cpp = self.cpp
+        if self.device_samplers:
+            rows = (lists[0], lists[1], lists[3], ray_index)
+            edges, near_far = cpp.sample_live(*rows, self.S, occ[0], occ[1], t_rand=t_rand, count=count)
+
+            def to_distance(values, out=None):
+                if out is not None:
+                    out = (out, cpp._empty(tuple(out.shape), dtype=torch.int32, device=out.device))
+                return cpp.live_to_distance(values.contiguous(), *rows, occ[0], occ[1], count=count, out=out)[0]
+        else:
+            idx = ray_index.long()
+            live = live_lengths_statement(lists[0][idx], lists[1][idx], lists[3][idx], *occ)
+            edges, (near, far) = live_sample_bins(live, self.S, t_rand)
+            edges, near_far = edges.contiguous(), torch.cat([near, far], 1).contiguous()
+
+            def to_distance(values, out=None):
+                return live_to_distance_statement(values, live)[0].contiguous()
+        return edges, near_far, to_distance
 
     def _culled_forward(self, traced, S, dirs, w, mode, hb, count, occ):
         """mlp_forward_gather of one pass with an occupancy (occ = (occupancy, threshold)): cull_samples on the pass's matched
@@ -681,12 +798,12 @@ class TetraRenderer:
                                        sigma=sigma, rgb=rgb)
         return sigma if dirs is None else (sigma, rgb)
 
-    def _chain_passes(self, lists, edges, ray_index, w, mode, pdf, count=None, coarse_weights=None, occ=None):
+    def _chain_passes(self, lists, edges, ray_index, w, mode, pdf, count=None, coarse_weights=None, occ=None, to_distance=None):
         """The sample placement of the kernel chain: locate -> [coarse weights -> pdf(edges, weights) -> locate] (the bracket
         with fine samples only).  Coarse weights: gather + mlp_base + density head in one kernel and get_weights in one more,
         unless `coarse_weights(traced, edges)` states them otherwise.  occ = (occupancy, threshold): the culled chain
-        (_culled_forward).  Returns (traced, final edges)."""
-        traced = self._locate(lists, edges, ray_index, count)
+        (_culled_forward).  to_distance: see _locate.  Returns (traced, final edges)."""
+        traced = self._locate(lists, edges, ray_index, count, to_distance)
         if self.S_fine > 0:
             if coarse_weights is None:
                 S = edges.shape[1] - 1
@@ -699,7 +816,7 @@ class TetraRenderer:
             else:
                 weights_c = coarse_weights(traced, edges)
             edges = pdf(edges, weights_c)
-            traced = self._locate(lists, edges, ray_index, count)
+            traced = self._locate(lists, edges, ray_index, count, to_distance)
         return traced, edges
 
     def _final_forward(self, vi, bc, edges, dirs, w, mode, hb, count=None, occ=None, traced=None):
@@ -739,7 +856,7 @@ class TetraRenderer:
     @torch.no_grad()
     def render(self, origins: torch.Tensor, directions: torch.Tensor, background=None, ray_head_bias=None,
                mlp_mode: Optional[str] = None, occupancy: Optional[torch.Tensor] = None,
-               occupancy_threshold: Optional[float] = None) -> Dict[str, torch.Tensor]:
+               occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False) -> Dict[str, torch.Tensor]:
         """Evaluation-mode render (model.py:520-662 with `self.training == False`: samplers without jitter, RGB renderer
         with nan_to_num + clamp).  background: per-call override of the renderer's colour (grey level or (r, g, b)).
         ray_head_bias f32 [R, 128] (fused path only): per-ray vector added to mlp_head's pre-activation -- the appearance
@@ -754,10 +871,17 @@ class TetraRenderer:
         occupancy f32 [num_cells] + occupancy_threshold (opt-in; both or neither, fused path, "fp32" / "bf16x3"): the per-tetrahedron
         occupancy field.  Samples whose tetrahedron lies below the threshold (cull_mask_statement) get sigma = rgb = 0 without
         running the network, in both passes; every other sample gets the bits it gets without an occupancy.  Such a call renders
-        through the kernel chain (the persistent launch does not cull)."""
+        through the kernel chain (the persistent launch does not cull).
+        occupancy_sampler (opt-in; needs occupancy and occupancy_threshold): the occupancy-GUIDED coarse sampler replaces the
+        uniform / biased one of this call.  The S bins are spread over the LIVE length of every ray (cpp.sample_live), both passes
+        locate cpp.live_to_distance of the bin centres with the unchanged matcher, the PDF sampler and the composite run on the
+        live-length edges -- a delta is the live length inside its bin -- and the median depth is mapped back to a distance.
+        Matcher, cull, indexed forward and composite are the kernels of a culled call."""
         cpp, S = self.cpp, self.S
         bg = self._bg(background)
         occ = self._occupancy_args(occupancy, occupancy_threshold, self.mlp_mode if mlp_mode is None else mlp_mode)
+        if occupancy_sampler and occ is None:
+            raise RuntimeError("occupancy_sampler needs occupancy and occupancy_threshold: the field the samples follow")
         if not self.fused:
             if ray_head_bias is not None:
                 raise RuntimeError("ray_head_bias is an input of the fused kernels; the PyTorch statement takes the model's own modules")
@@ -766,7 +890,8 @@ class TetraRenderer:
         mode = self.mlp_mode if mlp_mode is None else mlp_mode
         cpp._mode(mode)
         if not self.device_samplers:
-            return self._render_host_compaction(origins, directions, bg, ray_head_bias, mode, *(occ or ()))
+            return self._render_host_compaction(origins, directions, bg, ray_head_bias, mode, *(occ or (None, None)),
+                                                occupancy_sampler=bool(occupancy_sampler))
         out = self._trace(origins, directions)
         nv = out["num_visited_cells"]
         ray_mask = nv > 0
@@ -789,18 +914,26 @@ class TetraRenderer:
         order_l = order.long()
         dirs_o = d.index_select(0, order_l)
         hb = None if ray_head_bias is None else ray_head_bias.index_select(0, order_l).contiguous()
-        edges, near_far = cpp.sample_coarse(lists[0], lists[3], order, S, biased=self.biased, count=count)
-        traced, edges = self._chain_passes(lists, edges, order, w, mode, count=count, occ=occ,
+        to_distance = None
+        if occupancy_sampler:
+            edges, near_far, to_distance = self._live_sampler(lists, order, occ, count=count)
+        else:
+            edges, near_far = cpp.sample_coarse(lists[0], lists[3], order, S, biased=self.biased, count=count)
+        traced, edges = self._chain_passes(lists, edges, order, w, mode, count=count, occ=occ, to_distance=to_distance,
                                            pdf=lambda e, weights_c: cpp.sample_pdf(e, weights_c, near_far, self.S_fine, count=count))
         sigma, col = self._final_forward(traced["vertex_indices"], traced["barycentric_coordinates"], edges, dirs_o, w, mode, hb, count,
                                          occ=occ, traced=traced)
         cpp.composite(sigma, col, edges, background=bg, clamp=True, out=(rgb, acc, depth), ray_index=order,
                       count=count)
+        if to_distance is not None:
+            # the median depth is a live-length coordinate: mapped per hitting ray (the rows beyond count keep the far plane)
+            d_live = depth.index_select(0, order_l)
+            depth.index_copy_(0, order_l, to_distance(d_live, out=d_live.clone()))
         return res
 
     @torch.no_grad()
     def _render_host_compaction(self, origins, directions, bg, ray_head_bias=None, mode=None, occupancy=None,
-                                occupancy_threshold=None):
+                                occupancy_threshold=None, occupancy_sampler=False):
         """render() with the PyTorch SAMPLER statements (device_samplers=False: the parity definition of tn_sample_coarse /
         tn_sample_pdf, ~15 small operators per pass) between the HIP kernels.  Sizes its work on the host (torch.nonzero), as
         the reference does; not the production path."""
@@ -817,15 +950,21 @@ class TetraRenderer:
             w = mlp_weights(self.mlp)
             hb = None if ray_head_bias is None else ray_head_bias.index_select(0, idx).contiguous()
             near_r, far_r = hit_near_far(out, idx)
-            if self.biased:
+            to_distance = None
+            if occupancy_sampler:
+                edges, near_far, to_distance = self._live_sampler(lists, ridx, occ)
+                near_r, far_r = near_far[:, 0:1], near_far[:, 1:2]
+            elif self.biased:
                 edges = biased_sample_bins(near_r, far_r, S, lists[0][idx], lists[3][idx]).contiguous()
             else:
                 edges = uniform_sample_bins(near_r, far_r, S).contiguous()
-            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, occ=occ, pdf=lambda e, weights_c: pdf_sample_bins(
+            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, occ=occ, to_distance=to_distance, pdf=lambda e, weights_c: pdf_sample_bins(
                 (e - near_r) / (far_r - near_r), weights_c, self.S_fine, near_r, far_r).contiguous())
             sigma, col = self._final_forward(traced["vertex_indices"], traced["barycentric_coordinates"], edges,
                                              directions[idx].contiguous(), w, mode, hb, occ=occ, traced=traced)
             rgb_r, acc_r, depth_r = cpp.composite(sigma, col, edges, background=bg, clamp=True)
+            if to_distance is not None:
+                depth_r = to_distance(depth_r.reshape(-1, 1)).view_as(depth_r)
             rgb[idx] = rgb_r
             acc[idx] = acc_r
             depth[idx] = depth_r
@@ -890,7 +1029,7 @@ class TetraRenderer:
                      vertices: Optional[torch.Tensor] = None, mlp_mode: Optional[str] = None,
                      adjoint_mode: Optional[str] = None, dw_mode: Optional[str] = None,
                      occupancy: Optional[torch.Tensor] = None, occupancy_decay: Optional[float] = None,
-                     occupancy_threshold: Optional[float] = None) -> Dict[str, torch.Tensor]:
+                     occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
         (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches
         them), gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) --
@@ -940,7 +1079,12 @@ class TetraRenderer:
         (torch.where on the mask in both passes): the oracle of the fused path.  A culled tetrahedron contributes sigma = 0, so
         an update can only decay it: a caller that wants it to come back runs some batches unculled
         (nerfstudio_plugin: occupancy_refresh_every).
-        capture additionally receives cell_indices and, with a threshold, culled [r, S]."""
+        capture additionally receives cell_indices and, with a threshold, culled [r, S]; with gradient scaling, ray_dist [r, S, 1].
+        occupancy_sampler (opt-in; needs `occupancy` and a threshold, i.e. a culled batch): the occupancy-GUIDED coarse sampler
+        replaces the uniform / biased one of this call, as in render(): stratified bins over the live length of every ray, both passes
+        located through the live-to-distance map, PDF sampler and composite (node and statement alike) on the live-length edges, the
+        depth mapped back; GradientScaler takes its spacing from the mapped edges, (t(s_edges) - near) / (far - near) with the ray's
+        own far.  The sample placement stays a constant of the gradient; position_gradients=True is refused: the map has no adjoint."""
         cpp, S = self.cpp, self.S
         thr = occupancy_threshold
         if thr is None and occupancy is not None:
@@ -953,6 +1097,10 @@ class TetraRenderer:
         if occupancy_decay is not None and not fused:
             raise RuntimeError("the occupancy update is a kernel of the fused path (fused=True); its statement is occupancy_update_statement")
         occ = None if thr is None else (occupancy.detach(), float(thr))
+        if occupancy_sampler and occ is None:
+            raise RuntimeError("occupancy_sampler needs occupancy and an occupancy threshold: the field the samples follow")
+        if occupancy_sampler and position_gradients:
+            raise RuntimeError("occupancy_sampler cannot be combined with position_gradients: the live-to-distance map has no adjoint")
         # the arithmetic of the forward kernels, of the recorded node's dX chain and of its weight-gradient GEMMs
         modes = tuple(own if given is None else given for given, own in
                       ((mlp_mode, self.train_mlp_mode), (adjoint_mode, self.train_adjoint_mode), (dw_mode, self.train_dw_mode)))
@@ -1021,7 +1169,11 @@ class TetraRenderer:
             t_rand = rand.get("coarse")
             if t_rand is None:
                 t_rand = torch.rand((r, S + 1), device=dev, generator=generator)
-            if self.device_samplers:
+            to_distance = None
+            if occupancy_sampler:
+                edges, near_far, to_distance = self._live_sampler(lists, ridx, occ, t_rand=t_rand.contiguous())
+                near_r, far_r = near_far[:, 0:1], near_far[:, 1:2]
+            elif self.device_samplers:
                 edges, near_far = cpp.sample_coarse(lists[0], lists[3], ridx, S, biased=self.biased, t_rand=t_rand.contiguous())
                 near_r, far_r = near_far[:, 0:1], near_far[:, 1:2]
             else:
@@ -1052,7 +1204,7 @@ class TetraRenderer:
                 return ray_weights(sigma_c, e)
 
             traced, edges = self._chain_passes(lists, edges, ridx, w, mode, pdf, coarse_weights=None if fused else weights_torch,
-                                               occ=occ if fused else None)
+                                               occ=occ if fused else None, to_distance=to_distance)
             S = edges.shape[1] - 1
         dirs = directions[idx].contiguous()      # (a differentiable index: the view term of position_gradients)
         # per-ray bias of the head layer (appearance embedding; fused path only): differentiable w.r.t. the caller's tensor
@@ -1079,9 +1231,14 @@ class TetraRenderer:
             with torch.no_grad():
                 cpp.occupancy_update(occupancy, traced["cell_indices"], sigma.detach().contiguous(), occupancy_decay)
         if gradient_scaling and torch.is_grad_enabled():
+            if to_distance is not None:     # distances of the edges, over the ray's own [near, far]
+                with torch.no_grad():
+                    spacing = (to_distance(edges) - near_r) / (hit_far(out, idx) - near_r)
             if spacing is None:
                 spacing = (edges - near_r) / (far_r - near_r)
             ray_dist = (spacing[:, 1:] + spacing[:, :-1])[..., None]      # model.py:625-630
+            if capture is not None:
+                capture["ray_dist"] = ray_dist
             col, sg, _ = GradientScaler.apply(col, sigma[..., None], ray_dist)
             sigma = sg[..., 0]
         if record:
@@ -1091,6 +1248,8 @@ class TetraRenderer:
         else:
             rgb_r, acc_r, depth_r, _ = composite(sigma[..., None], col, edges[:, :-1, None], edges[:, 1:, None], background=bg)
         acc_r, depth_r = acc_r.reshape(-1, 1), depth_r.reshape(-1, 1).detach()
+        if to_distance is not None:
+            depth_r = to_distance(depth_r.contiguous())
         if sync_free:     # `order` is a permutation of the rays: every row is written once, padded entries get the miss values
             v = valid[:, None]
             idx, rgb_r, acc_r, depth_r = order, torch.where(v, rgb_r, rgb), torch.where(v, acc_r, acc), torch.where(v, depth_r, depth)

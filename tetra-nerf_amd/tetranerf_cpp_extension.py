@@ -1100,6 +1100,77 @@ def sample_coarse(num_visited_cells, hit_distances, ray_index, num_samples, bias
     return edges, near_far
 
 
+def _check_live_rows(num_visited_cells, visited_cells, hit_distances, ray_index, occupancy, what):
+    """the trace rows + occupancy of sample_live / live_to_distance, checked -> (r, M, device)"""
+    for x, name in ((num_visited_cells, "num_visited_cells"), (visited_cells, "visited_cells"), (hit_distances, "hit_distances"),
+                    (ray_index, "ray_index")):
+        _check_input(x, name)
+    _check(ray_index.dtype == torch.int32 and ray_index.dim() == 1, "ray_index must be i32 [r]")
+    _check(hit_distances.dtype == torch.float32 and hit_distances.dim() == 3 and hit_distances.size(2) == 2, "hit_distances must be f32 [R,M,2]")
+    R, M = hit_distances.size(0), hit_distances.size(1)
+    dev = hit_distances.device
+    _check(num_visited_cells.dtype == torch.int32 and num_visited_cells.dim() == 1 and num_visited_cells.numel() == R
+           and num_visited_cells.device == dev, "num_visited_cells must be i32 [R] on the rows' device")
+    _check(visited_cells.dtype == torch.int32 and tuple(visited_cells.shape) == (R, M) and visited_cells.device == dev,
+           "visited_cells must be i32 [R,M] on the rows' device")
+    _check(ray_index.device == dev, "ray_index must be on the rows' device")
+    _check(occupancy is not None, f"{what} needs the occupancy field its segments are compared with")
+    _check_occupancy(occupancy, dev)
+    return ray_index.numel(), M, dev
+
+
+def _check_ray_count(count):
+    _check(count is None or (count.dtype == torch.int32 and count.numel() >= 1 and count.is_cuda), "count must be an i32 device tensor")
+
+
+def sample_live(num_visited_cells, visited_cells, hit_distances, ray_index, num_samples, occupancy, threshold, t_rand=None, count=None):
+    """The occupancy-guided coarse sampler as ONE kernel on the trace rows in place (tn_sample_live; statements:
+    render.live_lengths_statement + live_sample_bins): returns (s_edges f32 [r, S+1], near_far_live f32 [r, 2]) for the hitting
+    rays ray_index i32 [r].  near_far_live = (near, near + L), L = the summed length of the ray's LIVE segments -- those whose
+    cell cull_samples would not cull under (occupancy f32 [T], threshold); s_edges = the uniform sampler's bin edges over that span
+    (t_rand [r, S+1]: training-mode stratified bins), in the live-length coordinate: map values of it with live_to_distance.  A ray
+    without a live segment counts all its segments live; count (i32 [1] on the device): rows from count[0] on are unwritten."""
+    r, M, dev = _check_live_rows(num_visited_cells, visited_cells, hit_distances, ray_index, occupancy, "sample_live")
+    S = int(num_samples)
+    _check(S >= 1, "num_samples must be positive")
+    _check_ray_count(count)
+    if t_rand is not None:
+        _check_input(t_rand, "t_rand")
+        _check(t_rand.dtype == torch.float32 and tuple(t_rand.shape) == (r, S + 1) and t_rand.device == dev, "t_rand must be f32 [r, S+1]")
+    edges = _empty((r, S + 1), dtype=torch.float32, device=dev)
+    near_far = _empty((r, 2), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.load().tn_sample_live(r, S, M, _ptr(ray_index), _ptr(num_visited_cells), _ptr(visited_cells), _ptr(hit_distances),
+                                              _ptr(occupancy), occupancy.numel(), float(threshold), _ptr(_linspace_table(S, dev)),
+                                              _ptr(t_rand), _ptr(edges), _ptr(near_far), _ptr(count), _stream(dev)))
+    return edges, near_far
+
+
+def live_to_distance(values, num_visited_cells, visited_cells, hit_distances, ray_index, occupancy, threshold, count=None, out=None):
+    """The inverse map of the live-length coordinate as ONE kernel (tn_live_to_distance; statement:
+    render.live_to_distance_statement): values f32 [r, n] (bin centres, edges, one depth per ray) of the rays ray_index i32 [r] ->
+    (t f32 [r, n] distances, slot i32 [r, n] = the segment of the trace row each value landed in).  Every t lies inside a live
+    segment of its ray: t_in[slot] <= t <= t_out[slot].  out = (t, slot) to store into; count (i32 [1] on the device): rows from
+    count[0] on are unwritten."""
+    r, M, dev = _check_live_rows(num_visited_cells, visited_cells, hit_distances, ray_index, occupancy, "live_to_distance")
+    _check_input(values, "values")
+    _check(values.dtype == torch.float32 and values.dim() == 2 and values.size(0) == r and values.device == dev, "values must be f32 [r, n]")
+    n = values.size(1)
+    _check_ray_count(count)
+    if out is None:
+        t, slot = _empty((r, n), dtype=torch.float32, device=dev), _empty((r, n), dtype=torch.int32, device=dev)
+    else:
+        t, slot = out
+        for x, name, dt in ((t, "out t", torch.float32), (slot, "out slot", torch.int32)):
+            _check_input(x, name)
+            _check(x.dtype == dt and tuple(x.shape) == (r, n) and x.device == dev, f"{name} must be [r, n] of the right type")
+    with _on(dev):
+        _lib.check(_lib.load().tn_live_to_distance(r, n, M, _ptr(ray_index), _ptr(num_visited_cells), _ptr(visited_cells),
+                                                   _ptr(hit_distances), _ptr(occupancy), occupancy.numel(), float(threshold), _ptr(values),
+                                                   _ptr(t), _ptr(slot), _ptr(count), _stream(dev)))
+    return t, slot
+
+
 def sample_pdf(edges, weights, near_far, num_fine, u_rand=None, histogram_padding=0.01, eps=1e-5, count=None):
     """nerfstudio's PDFSampler (include_original) as ONE kernel (tn_sample_pdf; model.py:582-586): edges f32 [r, S+1]
     euclidean coarse edges, weights f32 [r, S], near_far f32 [r, 2] -> f32 [r, S + num_fine + 2] merged, sorted euclidean
