@@ -721,6 +721,27 @@ int tn_composite_backward(size_t num_rays, uint32_t num_samples, const float *si
                           const tn_rgb_background *background, const float *d_out_rgb, const float *d_out_acc,
                           float *d_sigma, float *d_rgb, void *stream);
 
+/* Expected-depth moment and distortion loss of a ray (addition, same ABI version: nothing existing changes).  Replaces, on the
+ * training path, nerfstudio's DepthRenderer(method="expected") (model_components/renderers.py) and
+ * losses.lossfun_distortion (model_components/losses.py; mip-NeRF 360 eq. 15), which run in PyTorch on the materialised
+ * [R,S] weights, the distortion's pairwise term in O(S^2) per ray.  sigma f32 [R,S], edges f32 [R,S+1] non-decreasing per ray;
+ * with w = tn_composite's weights (the same bits), delta_i = e_{i+1} - e_i, u'_i = ((e_i - e_0) + (e_{i+1} - e_0)) / 2:
+ *   out_depth_moment f32 [R] = e_0 sum w_i + sum w_i u'_i                       (the caller divides by accumulation + eps)
+ *   out_distortion   f32 [R] = sum_ij w_i w_j |u'_i - u'_j| + 1/3 sum_i w_i^2 delta_i   (the caller divides by e_S - e_0)
+ *   out_weights      f32 [R,S]
+ * each nullable.  Linear time per ray (prefix sums of w and w u'). */
+int tn_composite_aux(size_t num_rays, uint32_t num_samples, const float *sigma, const float *edges, float *out_depth_moment,
+                     float *out_distortion, float *out_weights, void *stream);
+
+/* tn_composite_backward with the gradients of tn_composite_aux's two per-ray outputs, d_out_depth_moment f32 [R] and
+ * d_out_distortion f32 [R] (either nullable), as further terms of dL/dw: the adjoint of DepthRenderer(method="expected")'s
+ * numerator and of losses.lossfun_distortion, which PyTorch autograd forms through the materialised weights.  Edges are
+ * constants of the gradient.  Everything else as tn_composite_backward. */
+int tn_composite_backward_aux(size_t num_rays, uint32_t num_samples, const float *sigma, const float *rgb, const float *edges,
+                              const tn_rgb_background *background, const float *d_out_rgb, const float *d_out_acc,
+                              const float *d_out_depth_moment, const float *d_out_distortion, float *d_sigma, float *d_rgb,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

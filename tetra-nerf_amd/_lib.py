@@ -32,6 +32,7 @@ SYMBOLS = (
     "tn_mlp_forward_gather_train_indexed", "tn_mlp_param_grads_indexed", "tn_mlp_ray_head_grad_indexed", "tn_compact_rows",
     "tn_update_vertices", "tn_refit_table_bytes",
     "tn_sample_live", "tn_live_to_distance",       # the occupancy-guided sampler: the reference declares the field and never uses it
+    "tn_composite_aux", "tn_composite_backward_aux",   # expected-depth moment + distortion loss and their adjoint (nerfstudio renderers / losses)
     "tn_tet_quality", "tn_limit_vertex_step",      # the vertex step limiter: the reference has no counterpart (it never moves vertices)
 )
 
@@ -112,6 +113,8 @@ def load():
     lib.tn_mlp_param_grads.argtypes = [vp, sz, u32, vp, vp, vp, vp]
     lib.tn_mlp_param_grads_ex.argtypes = [vp, sz, u32, vp, vp, vp, i32, vp]
     lib.tn_composite_backward.argtypes = [sz, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.tn_composite_aux.argtypes = [sz, u32, vp, vp, vp, vp, vp, vp]
+    lib.tn_composite_backward_aux.argtypes = [sz, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_sample_coarse.argtypes = [sz, u32, u32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.tn_sample_pdf.argtypes = [sz, u32, u32, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]
     lib.tn_sample_live.argtypes = [sz, u32, u32, vp, vp, vp, vp, vp, u32, C.c_float, vp, vp, vp, vp, vp, vp]

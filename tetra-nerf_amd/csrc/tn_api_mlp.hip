@@ -531,4 +531,27 @@ int tn_composite(size_t num_rays, uint32_t num_samples, const float *sigma, cons
     });
 }
 
+int tn_composite_aux(size_t num_rays, uint32_t num_samples, const float *sigma, const float *edges, float *out_depth_moment,
+                     float *out_distortion, float *out_weights, void *stream_) {
+    return guarded([&] {
+        if (num_rays == 0 || num_samples == 0) return;
+        if (!sigma || !edges) throw tn::Error("null pointer");
+        tn::launch_composite_aux(num_rays, num_samples, sigma, edges, out_depth_moment, out_distortion, out_weights, (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_composite_backward_aux(size_t num_rays, uint32_t num_samples, const float *sigma, const float *rgb, const float *edges,
+                              const tn_rgb_background *background, const float *d_out_rgb, const float *d_out_acc,
+                              const float *d_out_depth_moment, const float *d_out_distortion, float *d_sigma, float *d_rgb,
+                              void *stream_) {
+    return guarded([&] {
+        if (num_rays == 0 || num_samples == 0) return;
+        if (!sigma || !rgb || !edges || !d_sigma || !d_rgb) throw tn::Error("null pointer");
+        tn::launch_composite_backward_aux(num_rays, num_samples, sigma, rgb, edges, background_of(background), d_out_rgb, d_out_acc,
+                                          d_out_depth_moment, d_out_distortion, d_sigma, d_rgb, (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
 }  // extern "C"

@@ -294,6 +294,14 @@ __host__ __device__ __forceinline__ float nan_to_num(float x) {
 // adjoint of launch_composite: d sigma [R,S], d rgb [R,S,3] from the gradients of the rendered rgb / accumulation
 void launch_composite_backward(size_t R, uint32_t S, const float *sigma, const float *rgb, const float *edges, Background background,
                                const float *d_out_rgb, const float *d_out_acc, float *d_sigma, float *d_rgb, hipStream_t stream);
+// two more per-ray sums over the composite's weights (tn_ray_aux.hip): depth_moment [R] = sum w (e_i + e_{i+1}) / 2, distortion_raw [R]
+// (mip-NeRF 360 eq. 15 on the edges as given), weights [R,S] = launch_composite's, bit for bit; every output nullable
+void launch_composite_aux(size_t R, uint32_t S, const float *sigma, const float *edges, float *out_moment, float *out_dist,
+                          float *out_weights, hipStream_t stream);
+// launch_composite_backward with the cotangents of those two sums (either nullable) as further terms of dL/dw
+void launch_composite_backward_aux(size_t R, uint32_t S, const float *sigma, const float *rgb, const float *edges, Background background,
+                                   const float *d_out_rgb, const float *d_out_acc, const float *d_out_moment, const float *d_out_dist,
+                                   float *d_sigma, float *d_rgb, hipStream_t stream);
 void launch_transpose(const float *in, float *out, uint32_t rows, uint32_t cols, hipStream_t stream);
 // everything between trace_rays and the frame as ONE persistent launch (tn_render_rays.hip): coarse sampler -> match -> gather +
 // MLP (density) -> weights -> PDF sampler -> match -> gather + MLP + heads -> composite, scattered into out_* (arrays over ALL rays)

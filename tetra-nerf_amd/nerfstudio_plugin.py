@@ -275,7 +275,8 @@ def _follow_vertices(tracer, model=None, fraction=None):
 def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
     """Drop-in body of TetrahedraNerf.get_outputs (model.py:520-662) on the fused kernels: training mode = stratified
     samples + autograd through the HIP adjoints (`render_train`), evaluation = `render`; same output dictionary
-    ("rgb", "accumulation", "depth", "ray_mask").  Unsupported configurations run the reference implementation."""
+    ("rgb", "accumulation", "depth", "ray_mask"; with config.aux_outputs or config.distortion_loss_mult also "expected_depth" and
+    "distortion").  Unsupported configurations run the reference implementation (and have no such outputs)."""
     ok, _why = fused_config_supported(model.config)
     ref = getattr(type(model), "_tn_reference_get_outputs", None)
     bg = resolve_background(model) if ok else None
@@ -343,9 +344,13 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
                     # (TetraRenderer.render_train: occupancy_sampler); the unculled refresh batches keep the ordinary sampler, which is
                     # how a culled tetrahedron still gets seen
                     kw["occupancy_sampler"] = True
+        if _wants_aux_outputs(model.config):
+            kw["aux_outputs"] = True
         return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
                                ray_head_bias=hb, **kw)
     kw = {}
+    if _wants_aux_outputs(model.config):
+        kw["aux_outputs"] = True
     occupancy = getattr(model, "tetrahedra_occupancy", None)
     threshold = getattr(model.config, "occupancy_threshold", None)
     if occupancy is not None and threshold is not None:
@@ -361,15 +366,40 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
     return rd.render(o, d, background=bg, ray_head_bias=hb, **kw)
 
 
+def _wants_aux_outputs(config) -> bool:
+    """opt-in (no such fields in the reference's config): `aux_outputs` truthy, or a `distortion_loss_mult`, adds "expected_depth"
+    and "distortion" to the outputs (TetraRenderer.render_train / render: aux_outputs)."""
+    return bool(getattr(config, "aux_outputs", None)) or getattr(config, "distortion_loss_mult", None) is not None
+
+
+def fused_get_loss_dict(model, outputs, batch, metrics_dict=None):
+    """The reference's get_loss_dict, its dictionary returned UNCHANGED unless config.distortion_loss_mult is set and the outputs
+    carry "distortion" (a configuration that fell back to the reference body has no such output): then "distortion_loss" =
+    mult * mean(distortion) is added -- what nerfstudio's models add from losses.distortion_loss; here the per-ray value comes out
+    of the fused composite node.  A depth-supervision loss is the caller's: "expected_depth" is in the outputs."""
+    ref = getattr(type(model), "_tn_reference_get_loss_dict", None)
+    if ref is None:
+        raise RuntimeError("no reference get_loss_dict to wrap: install() / make_fused_model_class() set it")
+    loss_dict = ref(model, outputs, batch, metrics_dict)
+    mult = getattr(model.config, "distortion_loss_mult", None)
+    if mult is not None and "distortion" in outputs:
+        loss_dict["distortion_loss"] = float(mult) * outputs["distortion"].mean()
+    return loss_dict
+
+
 def install(model_cls=None):
     """Monkey-patch `model_cls.get_outputs` (default: the reference's TetrahedraNerf, imported here -- needs nerfstudio)
-    with `fused_get_outputs`; the original stays reachable as `_tn_reference_get_outputs` (fallback rule).  Idempotent.
+    with `fused_get_outputs`; the original stays reachable as `_tn_reference_get_outputs` (fallback rule).  `get_loss_dict`, where
+    the class has one, is wrapped by `fused_get_loss_dict` the same way (`_tn_reference_get_loss_dict`).  Idempotent.
     Returns the class."""
     if model_cls is None:
         from tetranerf.nerfstudio.model import TetrahedraNerf as model_cls   # noqa: N813  (reference package)
     if getattr(model_cls, "_tn_reference_get_outputs", None) is None:
         model_cls._tn_reference_get_outputs = model_cls.get_outputs
         model_cls.get_outputs = fused_get_outputs
+    if getattr(model_cls, "_tn_reference_get_loss_dict", None) is None and getattr(model_cls, "get_loss_dict", None) is not None:
+        model_cls._tn_reference_get_loss_dict = model_cls.get_loss_dict
+        model_cls.get_loss_dict = fused_get_loss_dict
     return model_cls
 
 
@@ -378,6 +408,10 @@ def uninstall(model_cls):
     if ref is not None:
         model_cls.get_outputs = ref
         model_cls._tn_reference_get_outputs = None
+    ref = getattr(model_cls, "_tn_reference_get_loss_dict", None)
+    if ref is not None:
+        model_cls.get_loss_dict = ref
+        model_cls._tn_reference_get_loss_dict = None
     return model_cls
 
 
@@ -390,6 +424,12 @@ def make_fused_model_class(base_cls):
 
         def get_outputs(self, ray_bundle):
             return fused_get_outputs(self, ray_bundle)
+
+        if getattr(base_cls, "get_loss_dict", None) is not None:
+            _tn_reference_get_loss_dict = base_cls.get_loss_dict
+
+            def get_loss_dict(self, outputs, batch, metrics_dict=None):
+                return fused_get_loss_dict(self, outputs, batch, metrics_dict)
 
     FusedTetrahedraNerf.__name__ = "Fused" + base_cls.__name__
     return FusedTetrahedraNerf

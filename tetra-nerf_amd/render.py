@@ -256,6 +256,37 @@ def composite(sigma: torch.Tensor, rgb: torch.Tensor, starts: torch.Tensor, ends
     return out_rgb, acc, depth, weights
 
 
+def composite_aux_statement(sigma: torch.Tensor, edges: torch.Tensor):
+    """(depth_moment [R], distortion_raw [R]) of [R,S] densities on [R,S+1] non-decreasing edges, in the dtype of the inputs: the
+    first moment of the ray's weights (the numerator of nerfstudio's DepthRenderer(method="expected")) and the distortion loss of
+    mip-NeRF 360 (eq. 15; nerfstudio's losses.lossfun_distortion) on the edges as given, in the literal pairwise O(S^2) form --
+    the oracle of tn_composite_aux / tn_composite_backward_aux, which evaluate it in linear time.  The weights are ray_weights'
+    (= composite's).  The midpoints are taken RELATIVE TO THE FIRST EDGE, u'_i = ((e_i - e_0) + (e_{i+1} - e_0)) / 2, so that
+    fp32 keeps its digits on a ray that starts far from the camera:
+        depth_moment   = e_0 sum_i w_i + sum_i w_i u'_i                             (= sum_i w_i (e_i + e_{i+1}) / 2)
+        distortion_raw = sum_i sum_j w_i w_j |u'_i - u'_j| + (1/3) sum_i w_i^2 delta_i.
+    The edges are constants of the gradient wherever this is differentiated next to the kernels (pass them detached)."""
+    w = ray_weights(sigma, edges)
+    e0 = edges[:, :1]
+    u = ((edges[:, :-1] - e0) + (edges[:, 1:] - e0)) / 2
+    delta = edges[:, 1:] - edges[:, :-1]
+    depth_moment = e0[:, 0] * w.sum(-1) + (w * u).sum(-1)
+    pair = (w[:, :, None] * w[:, None, :] * (u[:, :, None] - u[:, None, :]).abs()).sum((-2, -1))
+    return depth_moment, pair + (w * w * delta).sum(-1) / 3
+
+
+def aux_outputs_of(depth_moment: torch.Tensor, distortion_raw: torch.Tensor, acc: torch.Tensor, edges: torch.Tensor):
+    """(expected_depth [r,1], distortion [r,1]) of a ray from the two sums: expected_depth = depth_moment / (accumulation + 1e-10)
+    (nerfstudio's "expected" depth without its global clip) and distortion = distortion_raw / (e_S - e_0), 0 where the span is 0
+    -- the loss is translation invariant and homogeneous of degree 1, so this is lossfun_distortion on the normalised bins
+    (e - e_0) / (e_S - e_0)."""
+    span = (edges[:, -1] - edges[:, 0]).detach()
+    expected = depth_moment.reshape(-1) / (acc.reshape(-1) + 1e-10)
+    dist = torch.where(span > 0, distortion_raw.reshape(-1) / torch.where(span > 0, span, torch.ones_like(span)),
+                       torch.zeros_like(span))
+    return expected[:, None], dist[:, None]
+
+
 TRACE_KEYS = ("num_visited_cells", "visited_cells", "barycentric_coordinates", "hit_distances", "vertex_indices")
 
 
@@ -426,7 +457,8 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
                      directions: torch.Tensor, num_samples: int = 256, max_ray_triangles: int = 512,
                      far_plane: float = 1000.0, num_fine_samples: int = 0, biased: bool = False,
                      background=1.0, occupancy: Optional[torch.Tensor] = None,
-                     occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False) -> Dict[str, torch.Tensor]:
+                     occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False,
+                     aux_outputs: bool = False) -> Dict[str, torch.Tensor]:
     """Plain-PyTorch statement of the render path in EVALUATION mode (model.py:520-662 with `self.training == False`: the
     samplers do not jitter, the RGB renderer sanitises and clamps); `tracer` needs trace_rays / find_visited_cells
     returning tensors, `interpolate_values(vi, bc, field)` the gather.  Pinned by the reference's own `get_outputs`
@@ -437,7 +469,11 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
     occupancy_sampler (with an occupancy): the occupancy-guided coarse sampler in the place of the uniform / biased one --
     live_sample_bins places the S bins over the live length of every ray, both passes locate
     live_to_distance_statement(bin_centres(s_edges)), the PDF sampler and the composite run on the live-length edges, and the
-    median depth is mapped back to a distance."""
+    median depth is mapped back to a distance.
+    aux_outputs: also "expected_depth" and "distortion" [R,1] of the final pass, from composite_aux_statement (far_plane and 0 on
+    rays that meet nothing); refused together with occupancy_sampler, as in TetraRenderer.render."""
+    if aux_outputs and occupancy_sampler:
+        raise RuntimeError(AUX_WITH_LIVE_SAMPLER)
     if (occupancy is None) != (occupancy_threshold is None):
         raise RuntimeError("occupancy and occupancy_threshold go together: pass both or neither")
     if occupancy_sampler and occupancy is None:
@@ -452,6 +488,7 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
     acc = torch.zeros((R, 1), dtype=torch.float32, device=origins.device)
     depth = torch.full((R, 1), far_plane, dtype=torch.float32, device=origins.device)
     margin = torch.full((R, 1), 0.5, dtype=torch.float32, device=origins.device)   # test aid: see median_margin
+    aux = {"expected_depth": depth.clone(), "distortion": torch.zeros_like(acc)} if aux_outputs else {}
     if bool(ray_mask.any()):
         lists = [x[ray_mask].contiguous() for x in trace_rows(out)]
         near_r, far_r = nears[ray_mask], fars[ray_mask]
@@ -495,7 +532,9 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
         acc[ray_mask] = acc_r
         depth[ray_mask] = depth_r
         margin[ray_mask] = median_margin(w_r)
-    return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask, "depth_margin": margin}
+        if aux_outputs:
+            aux["expected_depth"][ray_mask], aux["distortion"][ray_mask] = aux_outputs_of(*composite_aux_statement(sigma[..., 0], edges), acc_r, edges)
+    return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask, "depth_margin": margin, **aux}
 
 
 class GradientScaler(torch.autograd.Function):
@@ -629,6 +668,39 @@ class _FusedCompositeFunction(torch.autograd.Function):
         # (autograd hands over whatever layout the loss produced -- an expanded scalar after .sum() -- the op takes rows)
         d_sigma, d_col = cpp.composite_backward(sigma, rgb, edges, None if d_rgb is None else d_rgb.contiguous(),
                                                 None if d_acc is None else d_acc.reshape(-1).contiguous(), ctx.background)
+        return d_sigma, d_col, None, None
+
+
+AUX_WITH_LIVE_SAMPLER = ("aux_outputs cannot be combined with occupancy_sampler: the composite then runs on live-length edges, and an "
+                         "expected depth or a distortion measured in that coordinate is another quantity than the one in distances")
+
+
+class _FusedCompositeAuxFunction(torch.autograd.Function):
+    """_FusedCompositeFunction with two more per-ray outputs, depth_moment and distortion_raw (composite_aux_statement): forward =
+    tn_composite + tn_composite_aux, backward = ONE tn_composite_backward_aux call (the cotangents of the two sums are further
+    terms of dL/dw).  The edges are constants of the gradient."""
+
+    @staticmethod
+    def forward(ctx, sigma, rgb, edges, background):
+        from . import tetranerf_cpp_extension as cpp
+
+        ctx.save_for_backward(sigma, rgb, edges)
+        ctx.background = background
+        ctx.set_materialize_grads(False)      # an output the loss does not use hands None to backward, not a tensor of zeros
+        sg = sigma.detach()
+        out_rgb, acc, depth = cpp.composite(sg, rgb.detach(), edges, ctx.background)
+        depth_moment, distortion_raw = cpp.composite_aux(sg, edges)
+        ctx.mark_non_differentiable(depth)
+        return out_rgb, acc, depth, depth_moment, distortion_raw
+
+    @staticmethod
+    def backward(ctx, d_rgb, d_acc, _d_depth, d_moment, d_dist):
+        from . import tetranerf_cpp_extension as cpp
+
+        sigma, rgb, edges = ctx.saved_tensors
+        rows = [None if g is None else g.reshape(-1).contiguous() for g in (d_acc, d_moment, d_dist)]
+        d_sigma, d_col = cpp.composite_backward(sigma, rgb, edges, None if d_rgb is None else d_rgb.contiguous(), rows[0],
+                                                ctx.background, d_depth_moment=rows[1], d_distortion=rows[2])
         return d_sigma, d_col, None, None
 
 
@@ -856,7 +928,8 @@ class TetraRenderer:
     @torch.no_grad()
     def render(self, origins: torch.Tensor, directions: torch.Tensor, background=None, ray_head_bias=None,
                mlp_mode: Optional[str] = None, occupancy: Optional[torch.Tensor] = None,
-               occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False) -> Dict[str, torch.Tensor]:
+               occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False, aux_outputs: bool = False,
+               capture: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         """Evaluation-mode render (model.py:520-662 with `self.training == False`: samplers without jitter, RGB renderer
         with nan_to_num + clamp).  background: per-call override of the renderer's colour (grey level or (r, g, b)).
         ray_head_bias f32 [R, 128] (fused path only): per-ray vector added to mlp_head's pre-activation -- the appearance
@@ -876,7 +949,14 @@ class TetraRenderer:
         uniform / biased one of this call.  The S bins are spread over the LIVE length of every ray (cpp.sample_live), both passes
         locate cpp.live_to_distance of the bin centres with the unchanged matcher, the PDF sampler and the composite run on the
         live-length edges -- a delta is the live length inside its bin -- and the median depth is mapped back to a distance.
-        Matcher, cull, indexed forward and composite are the kernels of a culled call."""
+        Matcher, cull, indexed forward and composite are the kernels of a culled call.
+        aux_outputs (opt-in; off: nothing below changes, not a launch, not an allocation): the result also has
+        "expected_depth" and "distortion" [R,1] of the final pass (see render_train; rays that meet nothing: far_plane and 0), from
+        one more kernel (cpp.composite_aux) behind the composite; a renderer built with fused=False evaluates composite_aux_statement.  Such a call renders through the kernel chain, as one with an
+        occupancy does: the persistent launch is not touched.  capture (with aux_outputs): receives sigma [R,S], edges [R,S+1],
+        order and count of the final pass (rows from count on are not written)."""
+        if aux_outputs and occupancy_sampler:      # (in front of everything: an argument error, whatever else the call holds)
+            raise RuntimeError(AUX_WITH_LIVE_SAMPLER)
         cpp, S = self.cpp, self.S
         bg = self._bg(background)
         occ = self._occupancy_args(occupancy, occupancy_threshold, self.mlp_mode if mlp_mode is None else mlp_mode)
@@ -886,18 +966,20 @@ class TetraRenderer:
             if ray_head_bias is not None:
                 raise RuntimeError("ray_head_bias is an input of the fused kernels; the PyTorch statement takes the model's own modules")
             return render_reference(self.tracer, cpp.interpolate_values, self.field, self.mlp, origins, directions,
-                                    S, self.M, self.far_plane, self.S_fine, self.biased, background=bg)
+                                    S, self.M, self.far_plane, self.S_fine, self.biased, background=bg, aux_outputs=bool(aux_outputs))
         mode = self.mlp_mode if mlp_mode is None else mlp_mode
         cpp._mode(mode)
         if not self.device_samplers:
             return self._render_host_compaction(origins, directions, bg, ray_head_bias, mode, *(occ or (None, None)),
-                                                occupancy_sampler=bool(occupancy_sampler))
+                                                occupancy_sampler=bool(occupancy_sampler), aux_outputs=bool(aux_outputs))
         out = self._trace(origins, directions)
         nv = out["num_visited_cells"]
         ray_mask = nv > 0
         R, dev = origins.shape[0], origins.device
         rgb, acc, depth = self._miss_frame(R, bg, dev)
         res = {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask}
+        if aux_outputs:
+            res["expected_depth"], res["distortion"] = depth.clone(), torch.zeros_like(acc)
         if R == 0:
             return res
         # the 26 KB trace rows of the hitting rays are NOT compacted (model.py:546-567 copies them with boolean indexing):
@@ -906,7 +988,7 @@ class TetraRenderer:
         order, count = cpp.compact_hits(nv)          # hitting rays first, in ray order; their number stays on the device
         w = mlp_weights(self.mlp)
         d = directions.contiguous()
-        if self._one_launch_ok(mode, culled=occ is not None):
+        if not aux_outputs and self._one_launch_ok(mode, culled=occ is not None):
             cpp.render_rays(lists, order, count, self.field, d, w, S, self.S_fine, self.biased, out=(rgb, acc, depth), background=bg,
                             clamp=True, ray_head_bias=ray_head_bias, mode=mode)
             return res
@@ -925,6 +1007,15 @@ class TetraRenderer:
                                          occ=occ, traced=traced)
         cpp.composite(sigma, col, edges, background=bg, clamp=True, out=(rgb, acc, depth), ray_index=order,
                       count=count)
+        if aux_outputs:
+            # over all R rows (those from count on hold whatever their buffers held: masked below); `order` is a permutation
+            moment, dist_raw = cpp.composite_aux(sigma, edges)
+            exp_r, dist_r = aux_outputs_of(moment, dist_raw, acc.index_select(0, order_l), edges)
+            v = (torch.arange(R, device=dev) < count)[:, None]
+            res["expected_depth"].index_copy_(0, order_l, torch.where(v, exp_r, res["expected_depth"]))
+            res["distortion"].index_copy_(0, order_l, torch.where(v, dist_r, res["distortion"]))
+            if capture is not None:
+                capture.update(sigma=sigma, edges=edges, order=order, count=count)
         if to_distance is not None:
             # the median depth is a live-length coordinate: mapped per hitting ray (the rows beyond count keep the far plane)
             d_live = depth.index_select(0, order_l)
@@ -933,7 +1024,7 @@ class TetraRenderer:
 
     @torch.no_grad()
     def _render_host_compaction(self, origins, directions, bg, ray_head_bias=None, mode=None, occupancy=None,
-                                occupancy_threshold=None, occupancy_sampler=False):
+                                occupancy_threshold=None, occupancy_sampler=False, aux_outputs=False):
         """render() with the PyTorch SAMPLER statements (device_samplers=False: the parity definition of tn_sample_coarse /
         tn_sample_pdf, ~15 small operators per pass) between the HIP kernels.  Sizes its work on the host (torch.nonzero), as
         the reference does; not the production path."""
@@ -944,6 +1035,7 @@ class TetraRenderer:
         idx = torch.nonzero(ray_mask)[:, 0]
         mode = self.mlp_mode if mode is None else mode
         occ = self._occupancy_args(occupancy, occupancy_threshold, mode)
+        aux = {"expected_depth": depth.clone(), "distortion": torch.zeros_like(acc)} if aux_outputs else {}
         if idx.numel():
             lists = trace_rows(out)
             ridx = idx.to(torch.int32)
@@ -968,7 +1060,9 @@ class TetraRenderer:
             rgb[idx] = rgb_r
             acc[idx] = acc_r
             depth[idx] = depth_r
-        return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask}
+            if aux_outputs:
+                aux["expected_depth"][idx], aux["distortion"][idx] = aux_outputs_of(*cpp.composite_aux(sigma, edges), acc_r, edges)
+        return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask, **aux}
 
     def _train_final_pass(self, vi, bc, edges, dirs, w, modes, hb, occ, traced, record, fused):
         """The network on the final samples of a training call -> (sigma [r,S], col [r,S,3]).  record: as autograd nodes backed by
@@ -1029,7 +1123,8 @@ class TetraRenderer:
                      vertices: Optional[torch.Tensor] = None, mlp_mode: Optional[str] = None,
                      adjoint_mode: Optional[str] = None, dw_mode: Optional[str] = None,
                      occupancy: Optional[torch.Tensor] = None, occupancy_decay: Optional[float] = None,
-                     occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False) -> Dict[str, torch.Tensor]:
+                     occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False,
+                     aux_outputs: bool = False) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
         (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches
         them), gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) --
@@ -1084,7 +1179,24 @@ class TetraRenderer:
         replaces the uniform / biased one of this call, as in render(): stratified bins over the live length of every ray, both passes
         located through the live-to-distance map, PDF sampler and composite (node and statement alike) on the live-length edges, the
         depth mapped back; GradientScaler takes its spacing from the mapped edges, (t(s_edges) - near) / (far - near) with the ray's
-        own far.  The sample placement stays a constant of the gradient; position_gradients=True is refused: the map has no adjoint."""
+        own far.  The sample placement stays a constant of the gradient; position_gradients=True is refused: the map has no adjoint.
+        aux_outputs (opt-in; off: nothing above changes, not a launch, not an allocation): the result also has, each [R,1] and taken
+        from the FINAL pass only,
+            "expected_depth" = depth_moment / (accumulation + 1e-10), depth_moment = sum_i w_i (e_i + e_{i+1}) / 2: the first moment of
+                the weights, nerfstudio's DepthRenderer(method="expected") without its global clip -- the depth that carries a gradient
+                (the median depth does not), what a depth loss is written on;
+            "distortion" = distortion_raw / (e_S - e_0), 0 where the span is 0: mip-NeRF 360's distortion loss (eq. 15; nerfstudio's
+                losses.lossfun_distortion on the normalised bins (e - e_0) / (e_S - e_0)) of the ray, the regulariser against floaters;
+        rays that meet nothing get far_plane and 0, and the padded rows of the sync-free form are masked like the other outputs.
+        composite_aux_statement states both sums in the literal pairwise form; fused=False evaluates it (the oracle).  Fused, with a
+        graph: ONE node, _FusedCompositeAuxFunction, in the place of _FusedCompositeFunction -- the forward adds one kernel
+        (tn_composite_aux, linear in S), the backward is still one kernel (tn_composite_backward_aux); the two divisions run in PyTorch
+        on [r] tensors.  Without a graph the forward kernels alone run.  The edges stay constants of the gradient.  GradientScaler,
+        culled training, position gradients and the three arithmetic switches need no change: the composite node sits behind them and
+        sees full-size [r, S] tensors.  occupancy_sampler=True is refused with aux_outputs: the composite's edges are then live-length
+        coordinates, and a depth or a spread measured in them is another quantity."""
+        if aux_outputs and occupancy_sampler:      # (in front of everything: an argument error, whatever else the call holds)
+            raise RuntimeError(AUX_WITH_LIVE_SAMPLER)
         cpp, S = self.cpp, self.S
         thr = occupancy_threshold
         if thr is None and occupancy is not None:
@@ -1154,8 +1266,9 @@ class TetraRenderer:
                     self._hit_fraction, self._hits_host_id = idx.numel() / max(R, 1), self._batch_id
         bg = self._bg(background)
         rgb, acc, depth = self._miss_frame(R, bg, dev)
+        aux = {"expected_depth": depth.clone(), "distortion": torch.zeros_like(acc)} if aux_outputs else {}
         if idx.numel() == 0:
-            return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask}
+            return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask, **aux}
         lists = trace_rows(out)
         if ridx is None:
             ridx = idx.to(torch.int32)
@@ -1241,20 +1354,32 @@ class TetraRenderer:
                 capture["ray_dist"] = ray_dist
             col, sg, _ = GradientScaler.apply(col, sigma[..., None], ray_dist)
             sigma = sg[..., 0]
-        if record:
+        if record and aux_outputs:
+            rgb_r, acc_r, depth_r, moment_r, dist_raw_r = _FusedCompositeAuxFunction.apply(sigma, col, edges, bg)
+        elif record:
             rgb_r, acc_r, depth_r = _FusedCompositeFunction.apply(sigma, col, edges, bg)
         elif fused:
             rgb_r, acc_r, depth_r = cpp.composite(sigma.contiguous(), col.contiguous(), edges, background=bg)
+            if aux_outputs:
+                moment_r, dist_raw_r = cpp.composite_aux(sigma.contiguous(), edges)
         else:
             rgb_r, acc_r, depth_r, _ = composite(sigma[..., None], col, edges[:, :-1, None], edges[:, 1:, None], background=bg)
+            if aux_outputs:
+                moment_r, dist_raw_r = composite_aux_statement(sigma, edges)
         acc_r, depth_r = acc_r.reshape(-1, 1), depth_r.reshape(-1, 1).detach()
+        if aux_outputs:
+            exp_r, dist_r = aux_outputs_of(moment_r, dist_raw_r, acc_r, edges)
         if to_distance is not None:
             depth_r = to_distance(depth_r.contiguous())
         if sync_free:     # `order` is a permutation of the rays: every row is written once, padded entries get the miss values
             v = valid[:, None]
             idx, rgb_r, acc_r, depth_r = order, torch.where(v, rgb_r, rgb), torch.where(v, acc_r, acc), torch.where(v, depth_r, depth)
+            if aux_outputs:
+                exp_r, dist_r = torch.where(v, exp_r, aux["expected_depth"]), torch.where(v, dist_r, aux["distortion"])
+        if aux_outputs:
+            aux = {"expected_depth": aux["expected_depth"].index_copy(0, idx, exp_r), "distortion": aux["distortion"].index_copy(0, idx, dist_r)}
         return {"rgb": rgb.index_copy(0, idx, rgb_r), "accumulation": acc.index_copy(0, idx, acc_r),
-                "depth": depth.index_copy(0, idx, depth_r), "ray_mask": ray_mask}
+                "depth": depth.index_copy(0, idx, depth_r), "ray_mask": ray_mask, **aux}
 
 
 class TetraNerfModule(torch.nn.Module):

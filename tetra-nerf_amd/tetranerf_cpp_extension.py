@@ -1451,11 +1451,38 @@ def mlp_backward(saved, vertex_indices, barycentric_coordinates, field, dirs, we
     return res
 
 
-def composite_backward(sigma, rgb, edges, d_out_rgb, d_out_acc, background=1.0):
+def composite_aux(sigma, edges, want_weights=False):
+    """Two more per-ray sums over composite()'s weights, in one kernel (tn_composite_aux; linear time per ray) -- what nerfstudio's
+    DepthRenderer(method="expected") and losses.lossfun_distortion compute in PyTorch on the materialised weights:
+    depth_moment [R] = sum_i w_i (e_i + e_{i+1}) / 2 and distortion_raw [R] = sum_ij w_i w_j |u_i - u_j| + 1/3 sum_i w_i^2 delta_i
+    (render.composite_aux_statement).  sigma f32 [R,S], edges f32 [R,S+1], non-decreasing per ray.
+    Returns (depth_moment, distortion_raw), with want_weights also weights [R,S] (composite()'s, bit for bit)."""
+    for x, name in ((sigma, "sigma"), (edges, "edges")):
+        _check_input(x, name)
+        _check(x.dtype == torch.float32, f"{name} must have float32 type")
+    _check(sigma.dim() == 2, "sigma must be f32 [R,S]")
+    R, S = sigma.shape
+    _check(tuple(edges.shape) == (R, S + 1), "edges must be f32 [R,S+1]")
+    dev = sigma.device
+    _check(edges.device == dev, "all tensors must be on the same device")
+    if S == 0:        # (no sample: both sums are empty; the entry point returns before it writes)
+        return (torch.zeros(R, device=dev), torch.zeros(R, device=dev)) + ((sigma.clone(),) if want_weights else ())
+    moment = _empty((R,), dtype=torch.float32, device=dev)
+    dist = _empty((R,), dtype=torch.float32, device=dev)
+    weights = _empty((R, S), dtype=torch.float32, device=dev) if want_weights else None
+    with _on(dev):
+        _lib.check(_lib.load().tn_composite_aux(R, S, _ptr(sigma), _ptr(edges), _ptr(moment), _ptr(dist), _ptr(weights), _stream(dev)))
+    return (moment, dist, weights) if want_weights else (moment, dist)
+
+
+def composite_backward(sigma, rgb, edges, d_out_rgb, d_out_acc, background=1.0, d_depth_moment=None, d_distortion=None):
     """Adjoint of composite() w.r.t. sigma [R,S] and rgb [R,S,3] (the median depth has no gradient).  sigma f32 [R,S], rgb f32
-    [R,S,3], edges f32 [R,S+1]; d_out_rgb f32 [R,3] and d_out_acc f32 [R] (either may be None: that output has no gradient)."""
+    [R,S,3], edges f32 [R,S+1]; d_out_rgb f32 [R,3] and d_out_acc f32 [R] (either may be None: that output has no gradient).
+    d_depth_moment f32 [R], d_distortion f32 [R] (either may be None): the gradients of composite_aux()'s outputs, further terms of
+    dL/dw (tn_composite_backward_aux); with both None the call is tn_composite_backward, as before they existed."""
+    new = tuple((x, name) for x, name in ((d_depth_moment, "d_depth_moment"), (d_distortion, "d_distortion")) if x is not None)
     given = ((sigma, "sigma"), (rgb, "rgb"), (edges, "edges")) + tuple((x, name) for x, name in ((d_out_rgb, "d_out_rgb"), (d_out_acc, "d_out_acc"))
-                                                                      if x is not None)
+                                                                      if x is not None) + new
     for x, name in given:
         _check_input(x, name)
         _check(x.dtype == torch.float32, f"{name} must have float32 type")
@@ -1464,10 +1491,18 @@ def composite_backward(sigma, rgb, edges, d_out_rgb, d_out_acc, background=1.0):
     _check(tuple(rgb.shape) == (R, S, 3) and tuple(edges.shape) == (R, S + 1), "shape mismatch")
     _check(d_out_rgb is None or tuple(d_out_rgb.shape) == (R, 3), "d_out_rgb must be f32 [R,3]")
     _check(d_out_acc is None or tuple(d_out_acc.shape) == (R,), "d_out_acc must be f32 [R]")
+    for x, name in new:
+        _check(tuple(x.shape) == (R,), f"{name} must be f32 [R]")
     dev = sigma.device
     _check(all(x.device == dev for x, _ in given), "all tensors must be on the same device")
     d_sigma = _empty((R, S), dtype=torch.float32, device=dev)
     d_rgb = _empty((R, S, 3), dtype=torch.float32, device=dev)
+    if new:
+        with _on(dev):
+            _lib.check(_lib.load().tn_composite_backward_aux(R, S, _ptr(sigma), _ptr(rgb), _ptr(edges), _background(background),
+                                                             _ptr(d_out_rgb), _ptr(d_out_acc), _ptr(d_depth_moment), _ptr(d_distortion),
+                                                             _ptr(d_sigma), _ptr(d_rgb), _stream(dev)))
+        return d_sigma, d_rgb
     with _on(dev):
         _lib.check(_lib.load().tn_composite_backward(R, S, _ptr(sigma), _ptr(rgb), _ptr(edges), _background(background), _ptr(d_out_rgb),
                                                      _ptr(d_out_acc), _ptr(d_sigma), _ptr(d_rgb), _stream(dev)))
