@@ -287,6 +287,12 @@ def aux_outputs_of(depth_moment: torch.Tensor, distortion_raw: torch.Tensor, acc
     return expected[:, None], dist[:, None]
 
 
+def aux_start_values(depth: torch.Tensor, acc: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """{"expected_depth", "distortion"} [R,1] of rays that meet nothing, from the miss frame's depth and accumulation: the far
+    plane and 0."""
+    return {"expected_depth": depth.clone(), "distortion": torch.zeros_like(acc)}
+
+
 TRACE_KEYS = ("num_visited_cells", "visited_cells", "barycentric_coordinates", "hit_distances", "vertex_indices")
 
 
@@ -488,7 +494,7 @@ def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: Tetra
     acc = torch.zeros((R, 1), dtype=torch.float32, device=origins.device)
     depth = torch.full((R, 1), far_plane, dtype=torch.float32, device=origins.device)
     margin = torch.full((R, 1), 0.5, dtype=torch.float32, device=origins.device)   # test aid: see median_margin
-    aux = {"expected_depth": depth.clone(), "distortion": torch.zeros_like(acc)} if aux_outputs else {}
+    aux = aux_start_values(depth, acc) if aux_outputs else {}
     if bool(ray_mask.any()):
         lists = [x[ray_mask].contiguous() for x in trace_rows(out)]
         near_r, far_r = nears[ray_mask], fars[ray_mask]
@@ -714,6 +720,107 @@ def mlp_weights(mlp):
             mlp.density.bias, mlp.head.weight, mlp.head.bias, mlp.rgb.weight, mlp.rgb.bias]
 
 
+def _refuse_aux_with_live_sampler(aux_outputs, occupancy_sampler):
+    """The refusal common to every call path; raised in front of everything: an argument error, whatever else the call holds."""
+    if aux_outputs and occupancy_sampler:
+        raise RuntimeError(AUX_WITH_LIVE_SAMPLER)
+
+
+def _near_far_columns(near_far):
+    """(near [r,1], far [r,1]) of what a coarse sampler returned: the columns of a device sampler's [r,2] tensor, the pair of
+    a PyTorch statement as it is."""
+    return near_far if isinstance(near_far, tuple) else (near_far[:, 0:1], near_far[:, 1:2])
+
+
+def _uniform(rand, key, shape, device, generator):
+    """The uniform draws `key` of a training call: the caller's (render_train(rand=)), or drawn HERE from `generator` -- the
+    reference's order and shapes hold as long as "coarse" is asked for before "fine", and "fine" only when the PDF step runs."""
+    given = rand.get(key)
+    return torch.rand(shape, device=device, generator=generator) if given is None else given
+
+
+# The scatters of per-ray rows (a dict by output name) into a frame, in the frame's key order.  They stay apart: the first works
+# in place behind a composite that wrote its three outputs itself, the second is differentiable and never reads the count, the
+# third follows a compaction on the host (training: differentiable; evaluation: in place).
+
+def _scatter_counted_(frame, rows, order, count):
+    """render(): rows [R, .] in the order of `order` (a permutation of the rays), of which the first count[0] (on the device)
+    are real -- the others hold whatever their buffers held and are replaced by the frame's own values.  In place."""
+    valid = (torch.arange(order.numel(), device=order.device) < count)[:, None]
+    for key, row in rows.items():
+        frame[key].index_copy_(0, order, torch.where(valid, row, frame[key]))
+
+
+def _scatter_padded(frame, rows, order, valid):
+    """Sync-free training: rows [R, .] of the hitting rays first, then padded entries (valid [R,1] False) that get the frame's
+    miss values; `order` is a permutation of the rays, so every row is written once.  Differentiable: a frame of new tensors."""
+    return {**frame, **{key: frame[key].index_copy(0, order, torch.where(valid, row, frame[key])) for key, row in rows.items()}}
+
+
+def _scatter_compacted(frame, rows, idx):
+    """Training after a compaction on the host: rows [r, .] of the hitting rays `idx`.  Differentiable: a frame of new tensors."""
+    return {**frame, **{key: frame[key].index_copy(0, idx, row) for key, row in rows.items()}}
+
+
+def _scatter_compacted_(frame, rows, idx):
+    """Evaluation after a compaction on the host: an indexed store of the rows [r, .] of the hitting rays `idx`, in place."""
+    for key, row in rows.items():
+        frame[key][idx] = row
+
+
+def _median_to_distance(depth_rows, to_distance, keep=False):
+    """The median depth [r,1] of a call with the occupancy-guided sampler is a live-length coordinate: mapped to a distance
+    per ray.  keep: the `out=` form of the map -- rows beyond the device-side count keep what `depth_rows` holds."""
+    return to_distance(depth_rows.contiguous(), out=depth_rows.clone() if keep else None)
+
+
+def _scale_gradients(sigma, col, spacing, capture):
+    """GradientScaler on the final samples (model.py:625-630), ray_dist [r,S,1] from the spacing bins [r,S+1] of their edges
+    -> (sigma, col) with scaled gradients; capture receives ray_dist."""
+    ray_dist = (spacing[:, 1:] + spacing[:, :-1])[..., None]
+    if capture is not None:
+        capture["ray_dist"] = ray_dist
+    col, sg, _ = GradientScaler.apply(col, sigma[..., None], ray_dist)
+    return sg[..., 0], col
+
+
+class _SyncFreeDecision:
+    """Which form the next render_train batch takes, decided WITHOUT a host synchronisation.  The sync-free form pays for rays
+    that miss (padded entries are computed and discarded), so the hit count of a sync-free batch is read back asynchronously --
+    `pinned` (a one-element pinned int32 buffer) + `event`, never waited for -- and while the last known `fraction` of hitting
+    rays lies below the renderer's threshold the batches take the compacting form, which knows its count on the host anyway,
+    until the fraction recovers.  Rules: the decision is made on the last KNOWN fraction; there is no second copy while one is
+    pending (the buffer is busy); the count of an older batch never overrides one the host has seen since."""
+
+    def __init__(self):
+        self.pinned, self.event, self.fraction = None, None, 1.0
+        self.pending, self.host_id, self.batch_id = None, 0, 0     # (batch id, rays) of the copy in flight; last batch counted on the host
+
+    def begin_batch(self, min_hits: float) -> bool:
+        """A batch starts: take in a read-back that has landed -- whatever form this batch takes: a renderer that alternates
+        between the forms must not decide on a stale fraction -- and tell whether the last known fraction allows the sync-free form."""
+        self.batch_id += 1
+        if self.pending is not None and self.event.query():
+            (issued, rays), self.pending = self.pending, None
+            if issued > self.host_id:
+                self.fraction = float(self.pinned[0]) / max(float(rays), 1.0)   # of an EARLIER batch
+        return self.fraction >= min_hits
+
+    def start_copy(self, count, rays, stream):
+        """Sync-free batch: `count` (a one-element device tensor, as the compaction left it) of `rays` goes to the pinned buffer
+        as it is -- one copy on `stream` -- unless a copy is in flight."""
+        if self.pinned is None:
+            self.pinned, self.event = torch.zeros(1, dtype=torch.int32).pin_memory(), torch.cuda.Event()
+        if self.pending is None:
+            self.pinned.copy_(count, non_blocking=True)
+            self.event.record(stream)
+            self.pending = (self.batch_id, rays)
+
+    def host_counted(self, hits, rays):
+        """Compacting batch: the host knows the fraction."""
+        self.fraction, self.host_id = hits / max(rays, 1), self.batch_id
+
+
 class TetraRenderer:
     """GPU render path: HIP tracer/matcher/gather (+ optionally the fused fp32-MFMA MLP and the
     composite kernel).  With `fused=False` the MLP and the composite run in PyTorch on the GPU."""
@@ -735,11 +842,8 @@ class TetraRenderer:
 
         # render_train without a host synchronisation (see there); False: compact the hitting rays with torch.nonzero
         self.sync_free_train = bool(sync_free_train)
-        # the sync-free form pays for rays that miss (padded entries are computed and discarded): the hit fraction of a batch
-        # is read back ASYNCHRONOUSLY (pinned buffer + event, never waited for) and, when the last known fraction is below
-        # SYNC_FREE_MIN_HITS, the next batches take the compacting form until it recovers
-        self._hits_pinned, self._hits_event, self._hit_fraction = None, None, 1.0
-        self._hits_pending, self._hits_host_id, self._batch_id = None, 0, 0
+        # below this last known fraction of hitting rays the next batches take the compacting form (_SyncFreeDecision)
+        self._sync_free = _SyncFreeDecision()
         self.sync_free_min_hits = SYNC_FREE_MIN_HITS if sync_free_min_hits is None else float(sync_free_min_hits)
 
         self.cpp = cpp
@@ -757,13 +861,9 @@ class TetraRenderer:
         # cores (tn_mlp_backward_ex).  The four weight-gradient GEMMs have a third switch, train_dw_mode, independent of both
         # (all eight combinations are valid): "bf16x3" splits both streamed operands as they are staged and multiplies on the
         # bf16 matrix cores (tn_mlp_param_grads_ex); the bias sums, the rgb head and the gather adjoint are fp32 in all of them
-        self.mlp_mode = mlp_mode
-        self.train_mlp_mode = train_mlp_mode
-        self.train_adjoint_mode = train_adjoint_mode
-        cpp._mode(train_mlp_mode, inference=False)      # (an unknown mode fails here, not in the first training call)
-        cpp._mode(train_adjoint_mode, inference=False)
-        self.train_dw_mode = train_dw_mode
-        cpp._mode(train_dw_mode, inference=False)
+        self.mlp_mode, self.train_mlp_mode, self.train_adjoint_mode, self.train_dw_mode = mlp_mode, train_mlp_mode, train_adjoint_mode, train_dw_mode
+        for m in (train_mlp_mode, train_adjoint_mode, train_dw_mode):      # (an unknown mode fails here, not in the first training call)
+            cpp._mode(m, inference=False)
         self.train_node_samples = 1 << 22      # render_train: samples per autograd node of the fused MLP (see there)
         # RGBRenderer background: grey level (1.0 white = default config, 0.0 black) or an (r, g, b) triple; render() /
         # render_train() take a per-call override (nerfstudio's BACKGROUND_COLOR_OVERRIDE, model.py:504-518)
@@ -782,13 +882,16 @@ class TetraRenderer:
         # dense reference layout need not be written (non-materialising trace: 52 B per segment, not 52*M per ray)
         self.dense_tails = bool(dense_tails)
         # Everything after the trace as ONE persistent launch (tn_render_rays: samplers + match + gather + MLP + composite of both
-        # passes; round 5) whenever its preconditions hold (fp32 arithmetic, device samplers, the per-wave LDS regions fit:
-        # max_ray_triangles <= 2048).  True / "auto": use it; False: the chain of separate kernels (sampler, matcher, gather + MLP,
-        # composite per pass), which takes the same device-side ray count -- neither form synchronises with the host.  Round 2-4's
-        # per-pass fusion (tn_render_pass) interleaved match / composite with the MFMA layers and lost 4-6 % to the chain on
-        # 65,536-ray chunks; the persistent kernel separates the stages in time inside one launch and runs the chain's own device
-        # functions, so its frame is bit-identical to the chain's.
+        # passes) whenever its preconditions hold (_one_launch_ok).  True / "auto": use it; False: the chain of separate kernels
+        # (sampler, matcher, gather + MLP, composite per pass), which takes the same device-side ray count -- neither form
+        # synchronises with the host.  The persistent kernel separates the stages in time inside one launch and runs the chain's
+        # own device functions, so its frame is bit-identical to the chain's (DESIGN.md 4.5 has the history of the forms).
         self.fused_pass = fused_pass if fused_pass == "auto" else bool(fused_pass)
+
+    @property
+    def _hit_fraction(self):
+        """last known fraction of hitting rays of a render_train batch (_SyncFreeDecision)"""
+        return self._sync_free.fraction
 
     def _trace(self, origins, directions):
         """trace_rays; compact rows (a PER-CALL flag of the op: the tracer may be shared with other threads) unless this
@@ -822,6 +925,12 @@ class TetraRenderer:
         return (self._background_rows(R, bg, dev), torch.zeros((R, 1), dtype=torch.float32, device=dev),
                 torch.full((R, 1), self.far_plane, dtype=torch.float32, device=dev))
 
+    def _frame(self, R, bg, dev, ray_mask, aux_outputs):
+        """The result of a call whose rays all miss, in the key order of every result: the miss frame, ray_mask and, with
+        aux_outputs, their start values.  The scatters (_scatter_*) write the rows of the hitting rays into it."""
+        rgb, acc, depth = self._miss_frame(R, bg, dev)
+        return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask, **(aux_start_values(depth, acc) if aux_outputs else {})}
+
     def _locate(self, lists, edges, ray_index, count=None, to_distance=None):
         """find_visited_cells of the bin centres of `edges` [r,S+1] on the trace rows in place: row i of the result belongs to
         trace row ray_index[i]; count: device-side number of rows to match.  to_distance (the occupancy-guided sampler): the
@@ -834,10 +943,10 @@ class TetraRenderer:
 
     def _live_sampler(self, lists, ray_index, occ, t_rand=None, count=None):
         """The occupancy-guided coarse sampler of one call, occ = (occupancy, threshold): (s_edges [r,S+1] in the live-length
-        coordinate, near_far_live [r,2], to_distance) -- to_distance(values [r,n], out=None) maps live-length values (bin centres,
+        coordinate, near_far_live, to_distance) -- to_distance(values [r,n], out=None) maps live-length values (bin centres,
         edges, a depth) to distances.  Device samplers: cpp.sample_live / cpp.live_to_distance on the trace rows in place
-        (count: device-side number of rows; `out`: a tensor to store into, so that rows beyond count keep what it holds);
-        otherwise the PyTorch statements on the rows of `ray_index`."""
+        (near_far_live [r,2]; count: device-side number of rows; `out`: a tensor to store into, so that rows beyond count keep
+        what it holds); otherwise the PyTorch statements on the rows of `ray_index` (near_far_live: the pair (near, far))."""
         cpp = self.cpp
         if self.device_samplers:
             rows = (lists[0], lists[1], lists[3], ray_index)
@@ -850,12 +959,52 @@ class TetraRenderer:
         else:
             idx = ray_index.long()
             live = live_lengths_statement(lists[0][idx], lists[1][idx], lists[3][idx], *occ)
-            edges, (near, far) = live_sample_bins(live, self.S, t_rand)
-            edges, near_far = edges.contiguous(), torch.cat([near, far], 1).contiguous()
+            edges, near_far = live_sample_bins(live, self.S, t_rand)
+            edges = edges.contiguous()
 
             def to_distance(values, out=None):
                 return live_to_distance_statement(values, live)[0].contiguous()
         return edges, near_far, to_distance
+
+    def _coarse_samples(self, out, lists, ridx, idx, occ, occupancy_sampler, t_rand=None, count=None):
+        """The coarse sampler of a call on the trace `out` (lists = its rows), for the rays ridx i32 [r] (idx: the same as
+        int64, read by the PyTorch statement only) -> (edges [r,S+1], near_far, spacing or None, to_distance or None).
+        The choice: occupancy-guided (_live_sampler; to_distance: its map, the edges are live-length coordinates), the device
+        kernel (cpp.sample_coarse), or the PyTorch statement.  near_far: what _near_far_columns and the PDF step (_pdf_step)
+        take.  t_rand [r,S+1]: the stratified draws of a training call; count: device-side number of rows.  spacing: the
+        spacing bins of the edges, exact only where the statement of a training call drew them -- an evaluation call carries
+        none (its PDF step derives them from the edges)."""
+        if occupancy_sampler:
+            edges, near_far, to_distance = self._live_sampler(lists, ridx, occ, t_rand=t_rand, count=count)
+            return edges, near_far, None, to_distance
+        if self.device_samplers:
+            return (*self.cpp.sample_coarse(lists[0], lists[3], ridx, self.S, biased=self.biased, t_rand=t_rand, count=count), None, None)
+        near_far, spacing = hit_near_far(out, idx), None
+        if t_rand is not None:
+            edges, spacing = coarse_samples(*near_far, self.S, self.biased, lists[0][idx], lists[3][idx], t_rand)
+        elif self.biased:
+            edges = biased_sample_bins(*near_far, self.S, lists[0][idx], lists[3][idx])
+        else:
+            edges = uniform_sample_bins(*near_far, self.S)
+        return edges.contiguous(), near_far, spacing, None
+
+    def _pdf_step(self, edges, weights_c, near_far, carried, u_rand=None, count=None):
+        """The PDF step of _chain_passes: coarse edges and weights -> the S + S_fine + 2 merged edges.  Device samplers:
+        cpp.sample_pdf, over `count` rows (evaluation) or with the stratified draws u_rand [r,S_fine+1] (training).  Otherwise
+        the PyTorch statement on spacing bins: those `carried["spacing"]` holds, or (None or absent) derived from the edges.
+        The spacing bins of the returned edges are left in `carried` (a dict of the call), where a training call finds them:
+        None after the device sampler, which keeps none."""
+        if self.device_samplers:
+            kw = {"count": count} if u_rand is None else {"u_rand": u_rand.contiguous()}
+            edges, spacing = self.cpp.sample_pdf(edges, weights_c, near_far, self.S_fine, **kw), None
+        else:
+            near_r, far_r = _near_far_columns(near_far)
+            spacing = carried.get("spacing")
+            if spacing is None:
+                spacing = (edges - near_r) / (far_r - near_r)
+            edges, spacing = pdf_sample_bins(spacing, weights_c, self.S_fine, near_r, far_r, u_rand=u_rand, return_spacing=True)
+        carried["spacing"] = spacing
+        return edges.contiguous()
 
     def _culled_forward(self, traced, S, dirs, w, mode, hb, count, occ):
         """mlp_forward_gather of one pass with an occupancy (occ = (occupancy, threshold)): cull_samples on the pass's matched
@@ -901,23 +1050,84 @@ class TetraRenderer:
             sigma, col = self._culled_forward(traced, S, dirs, w, mode, hb, count, occ)
         return sigma.view(-1, S), col.view(-1, S, 3)
 
-    def _occupancy_args(self, occupancy, threshold, mode):
-        """(occupancy, threshold) of a culled render() call, checked; None without an occupancy"""
+    def _render_args(self, background, mlp_mode, occupancy, threshold, occupancy_sampler, aux_outputs):
+        """(bg, mode, occ) of a render() call, checked: the background of the call, the arithmetic of its MLP kernels, and
+        occ = (occupancy, threshold) of a culled call, None without an occupancy."""
+        _refuse_aux_with_live_sampler(aux_outputs, occupancy_sampler)
+        bg = self._bg(background)
+        mode = self.mlp_mode if mlp_mode is None else mlp_mode
         if (occupancy is None) != (threshold is None):
             raise RuntimeError("occupancy and occupancy_threshold go together: pass both or neither (there is no default "
                                "threshold: what counts as empty is the caller's decision)")
-        if occupancy is None:
-            return None
-        if not self.fused:
-            raise RuntimeError("an occupancy is an input of the fused kernel chain (fused=True); the PyTorch statement is "
-                               "render_reference(..., occupancy=, occupancy_threshold=)")
-        if self.cpp._mode(mode) == 2:
-            raise RuntimeError('mlp_mode="bf16" cannot be combined with an occupancy: the plain-bf16 kernel has no indexed form')
-        return occupancy.detach(), float(threshold)
+        occ = None
+        if occupancy is not None:
+            if not self.fused:
+                raise RuntimeError("an occupancy is an input of the fused kernel chain (fused=True); the PyTorch statement is "
+                                   "render_reference(..., occupancy=, occupancy_threshold=)")
+            if self.cpp._mode(mode) == 2:
+                raise RuntimeError('mlp_mode="bf16" cannot be combined with an occupancy: the plain-bf16 kernel has no indexed form')
+            occ = (occupancy.detach(), float(threshold))
+        if occupancy_sampler and occ is None:
+            raise RuntimeError("occupancy_sampler needs occupancy and occupancy_threshold: the field the samples follow")
+        return bg, mode, occ
+
+    def _train_args(self, fused, position_gradients, mlp_mode, adjoint_mode, dw_mode, occupancy, occupancy_decay, occupancy_threshold,
+                    occupancy_sampler, aux_outputs):
+        """(occ, modes) of a render_train() call, checked: occ = (occupancy, threshold) of a culled batch (the threshold of
+        the call, or the renderer's train_occupancy_threshold), None when training is not culled; modes = the arithmetic of
+        the forward kernels, of the recorded node's dX chain and of its weight-gradient GEMMs."""
+        _refuse_aux_with_live_sampler(aux_outputs, occupancy_sampler)
+        thr = self.train_occupancy_threshold if occupancy_threshold is None and occupancy is not None else occupancy_threshold
+        if thr is not None and occupancy is None:
+            raise RuntimeError("occupancy_threshold needs the occupancy field it is compared with: pass occupancy=")
+        if (occupancy is None) != (occupancy_decay is None) and thr is None:
+            raise RuntimeError("occupancy and occupancy_decay go together: pass both or neither (occupancy with an "
+                               "occupancy_threshold alone culls without updating)")
+        if occupancy_decay is not None and not fused:
+            raise RuntimeError("the occupancy update is a kernel of the fused path (fused=True); its statement is occupancy_update_statement")
+        occ = None if thr is None else (occupancy.detach(), float(thr))
+        if occupancy_sampler and occ is None:
+            raise RuntimeError("occupancy_sampler needs occupancy and an occupancy threshold: the field the samples follow")
+        if occupancy_sampler and position_gradients:
+            raise RuntimeError("occupancy_sampler cannot be combined with position_gradients: the live-to-distance map has no adjoint")
+        modes = tuple(own if given is None else given for given, own in
+                      ((mlp_mode, self.train_mlp_mode), (adjoint_mode, self.train_adjoint_mode), (dw_mode, self.train_dw_mode)))
+        for m in modes:
+            self.cpp._mode(m, inference=False)
+        return occ, modes
+
+    def _composite_rows(self, sigma, col, edges, bg, how, aux_outputs, clamp=False, into=None):
+        """Weights and renderers of the final samples -> the per-ray rows {"rgb" [r,3], "accumulation", "depth" [r,1]} and, with
+        aux_outputs, {"expected_depth", "distortion"} [r,1] (aux_outputs_of).  how: "node" -- recorded, ONE autograd node backed
+        by the forward / adjoint kernels (_FusedCompositeAuxFunction in the place of _FusedCompositeFunction with aux_outputs);
+        "kernels" -- the forward kernels alone (clamp: the RGB renderer's evaluation mode), cpp.composite_aux behind the
+        composite with aux_outputs only; "statement" -- composite / composite_aux_statement in PyTorch.
+        into = (frame, order i32 [R], order as int64, count): render()'s form of "kernels" -- the composite stores the first
+        count[0] (on the device) rows straight into the frame's three tensors at order[.] and only the aux rows, over all R, are
+        returned: those from count on hold whatever their buffers held (_scatter_counted_ masks them)."""
+        if how == "node":
+            rgb, acc, depth, *sums = (_FusedCompositeAuxFunction if aux_outputs else _FusedCompositeFunction).apply(sigma, col, edges, bg)
+        elif how == "kernels":
+            sigma = sigma.contiguous()
+            if into is None:
+                rgb, acc, depth = self.cpp.composite(sigma, col.contiguous(), edges, background=bg, clamp=clamp)
+            else:
+                frame, order, order_l, count = into
+                self.cpp.composite(sigma, col, edges, background=bg, clamp=clamp, out=(frame["rgb"], frame["accumulation"], frame["depth"]),
+                                   ray_index=order, count=count)
+                acc = frame["accumulation"].index_select(0, order_l) if aux_outputs else None
+            sums = self.cpp.composite_aux(sigma, edges) if aux_outputs else ()
+        else:
+            rgb, acc, depth, _ = composite(sigma[..., None], col, edges[:, :-1, None], edges[:, 1:, None], background=bg)
+            sums = composite_aux_statement(sigma, edges) if aux_outputs else ()
+        rows = {} if into is not None else {"rgb": rgb, "accumulation": acc, "depth": depth}
+        if aux_outputs:
+            rows["expected_depth"], rows["distortion"] = aux_outputs_of(*sums, acc, edges)
+        return rows
 
     def _one_launch_ok(self, mode, culled=False):
-        """tn_render_rays' preconditions: device samplers, the per-wave LDS regions of its ray phases fit (either arithmetic
-        since round 6: the bf16x3 mode runs x3::forward_group in the MLP phases).  `region` restates launch_render_rays'
+        """tn_render_rays' preconditions: device samplers, the per-wave LDS regions of its ray phases fit, "fp32" or "bf16x3"
+        arithmetic (the bf16x3 mode runs x3::forward_group in the MLP phases).  `region` restates launch_render_rays'
         per-wave LDS region (csrc/tn_render_rays.hip).  culled: a call with an occupancy -- the persistent launch does not cull."""
         if culled:
             return False
@@ -930,56 +1140,57 @@ class TetraRenderer:
                mlp_mode: Optional[str] = None, occupancy: Optional[torch.Tensor] = None,
                occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False, aux_outputs: bool = False,
                capture: Optional[dict] = None) -> Dict[str, torch.Tensor]:
-        """Evaluation-mode render (model.py:520-662 with `self.training == False`: samplers without jitter, RGB renderer
-        with nan_to_num + clamp).  background: per-call override of the renderer's colour (grey level or (r, g, b)).
-        ray_head_bias f32 [R, 128] (fused path only): per-ray vector added to mlp_head's pre-activation -- the appearance
+        """Evaluation-mode render (model.py:520-662 with `self.training == False`: samplers without jitter, RGB renderer with
+        nan_to_num + clamp) -> {"rgb" [R,3], "accumulation", "depth" [R,1], "ray_mask" [R]}.  NO HOST SYNCHRONISATION: the
+        reference compacts the hitting rays with boolean indexing (model.py:540-567), a device -> host round trip per chunk
+        during which the GPU idles; here they are compacted on the device (tn_compact_hits: their number stays there) and
+        every kernel after the trace takes the address of that count.  The stages -- trace, coarse samples, sample placement
+        of both passes, network, composite, scatter -- and the forms each call path takes of them: DESIGN.md 4.14.
+
+        origins, directions f32 [R,3]: the rays.
+
+        background: per-call override of the renderer's colour (grey level or (r, g, b)).
+
+        ray_head_bias f32 [R,128] (fused path only): per-ray vector added to mlp_head's pre-activation -- the appearance
         embedding's share of the head layer, Wh[:, 155:] emb (model.py:608-620), made by the caller.
-        mlp_mode (fused path; None: the renderer's mlp_mode): arithmetic of the MLP kernels of this call.  "bf16" -- both operands
-        of every product of the four wide layers rounded to bf16, fp32 accumulation (mlp_forward_bf16_statement) -- is the fast
-        one and the only one that does NOT hold the 1e-5 parity bar; it renders through the kernel chain.
-        NO HOST SYNCHRONISATION (round 5): the reference compacts the hitting rays with boolean indexing (model.py:540-567),
-        rounds 2-4 with torch.nonzero -- a device -> host round trip per chunk during which the GPU idles.  Here the hitting
-        rays are compacted on the device (tn_compact_hits: their number stays there) and every kernel after the trace takes the
-        address of that count.
-        occupancy f32 [num_cells] + occupancy_threshold (opt-in; both or neither, fused path, "fp32" / "bf16x3"): the per-tetrahedron
-        occupancy field.  Samples whose tetrahedron lies below the threshold (cull_mask_statement) get sigma = rgb = 0 without
-        running the network, in both passes; every other sample gets the bits it gets without an occupancy.  Such a call renders
-        through the kernel chain (the persistent launch does not cull).
+
+        mlp_mode (fused path; None: the renderer's mlp_mode): arithmetic of the MLP kernels of this call.  "bf16" -- both
+        operands of every product of the four wide layers rounded to bf16, fp32 accumulation (mlp_forward_bf16_statement) --
+        is the fast one and the only one that does NOT hold the 1e-5 parity bar; it renders through the kernel chain.
+
+        occupancy f32 [num_cells] + occupancy_threshold (opt-in; both or neither, fused path, "fp32" / "bf16x3"): the
+        per-tetrahedron occupancy field.  Samples whose tetrahedron lies below the threshold (cull_mask_statement) get
+        sigma = rgb = 0 without running the network, in both passes; every other sample gets the bits it gets without an
+        occupancy.  Such a call renders through the kernel chain (the persistent launch does not cull).
+
         occupancy_sampler (opt-in; needs occupancy and occupancy_threshold): the occupancy-GUIDED coarse sampler replaces the
-        uniform / biased one of this call.  The S bins are spread over the LIVE length of every ray (cpp.sample_live), both passes
-        locate cpp.live_to_distance of the bin centres with the unchanged matcher, the PDF sampler and the composite run on the
-        live-length edges -- a delta is the live length inside its bin -- and the median depth is mapped back to a distance.
-        Matcher, cull, indexed forward and composite are the kernels of a culled call.
-        aux_outputs (opt-in; off: nothing below changes, not a launch, not an allocation): the result also has
-        "expected_depth" and "distortion" [R,1] of the final pass (see render_train; rays that meet nothing: far_plane and 0), from
-        one more kernel (cpp.composite_aux) behind the composite; a renderer built with fused=False evaluates composite_aux_statement.  Such a call renders through the kernel chain, as one with an
-        occupancy does: the persistent launch is not touched.  capture (with aux_outputs): receives sigma [R,S], edges [R,S+1],
-        order and count of the final pass (rows from count on are not written)."""
-        if aux_outputs and occupancy_sampler:      # (in front of everything: an argument error, whatever else the call holds)
-            raise RuntimeError(AUX_WITH_LIVE_SAMPLER)
+        uniform / biased one of this call.  The S bins are spread over the LIVE length of every ray (cpp.sample_live), both
+        passes locate cpp.live_to_distance of the bin centres with the unchanged matcher, the PDF sampler and the composite
+        run on the live-length edges -- a delta is the live length inside its bin -- and the median depth is mapped back to a
+        distance.  Matcher, cull, indexed forward and composite are the kernels of a culled call.
+
+        aux_outputs (opt-in; off: nothing else changes, not a launch, not an allocation): the result also has
+        "expected_depth" and "distortion" [R,1] of the final pass (see render_train; rays that meet nothing: far_plane and
+        0), from one more kernel (cpp.composite_aux) behind the composite; a renderer built with fused=False evaluates
+        composite_aux_statement.  Such a call renders through the kernel chain, as one with an occupancy does: the
+        persistent launch is not touched.  Refused together with occupancy_sampler (AUX_WITH_LIVE_SAMPLER).
+
+        capture (with aux_outputs): receives sigma [R,S], edges [R,S+1], order and count of the final pass (rows from count
+        on are not written)."""
+        bg, mode, occ = self._render_args(background, mlp_mode, occupancy, occupancy_threshold, occupancy_sampler, aux_outputs)
         cpp, S = self.cpp, self.S
-        bg = self._bg(background)
-        occ = self._occupancy_args(occupancy, occupancy_threshold, self.mlp_mode if mlp_mode is None else mlp_mode)
-        if occupancy_sampler and occ is None:
-            raise RuntimeError("occupancy_sampler needs occupancy and occupancy_threshold: the field the samples follow")
         if not self.fused:
             if ray_head_bias is not None:
                 raise RuntimeError("ray_head_bias is an input of the fused kernels; the PyTorch statement takes the model's own modules")
             return render_reference(self.tracer, cpp.interpolate_values, self.field, self.mlp, origins, directions,
                                     S, self.M, self.far_plane, self.S_fine, self.biased, background=bg, aux_outputs=bool(aux_outputs))
-        mode = self.mlp_mode if mlp_mode is None else mlp_mode
         cpp._mode(mode)
         if not self.device_samplers:
-            return self._render_host_compaction(origins, directions, bg, ray_head_bias, mode, *(occ or (None, None)),
-                                                occupancy_sampler=bool(occupancy_sampler), aux_outputs=bool(aux_outputs))
+            return self._render_host_compaction(origins, directions, bg, ray_head_bias, mode, occ, bool(occupancy_sampler), bool(aux_outputs))
         out = self._trace(origins, directions)
         nv = out["num_visited_cells"]
-        ray_mask = nv > 0
-        R, dev = origins.shape[0], origins.device
-        rgb, acc, depth = self._miss_frame(R, bg, dev)
-        res = {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask}
-        if aux_outputs:
-            res["expected_depth"], res["distortion"] = depth.clone(), torch.zeros_like(acc)
+        R = origins.shape[0]
+        res = self._frame(R, bg, origins.device, nv > 0, aux_outputs)
         if R == 0:
             return res
         # the 26 KB trace rows of the hitting rays are NOT compacted (model.py:546-567 copies them with boolean indexing):
@@ -989,80 +1200,51 @@ class TetraRenderer:
         w = mlp_weights(self.mlp)
         d = directions.contiguous()
         if not aux_outputs and self._one_launch_ok(mode, culled=occ is not None):
-            cpp.render_rays(lists, order, count, self.field, d, w, S, self.S_fine, self.biased, out=(rgb, acc, depth), background=bg,
-                            clamp=True, ray_head_bias=ray_head_bias, mode=mode)
+            cpp.render_rays(lists, order, count, self.field, d, w, S, self.S_fine, self.biased, out=(res["rgb"], res["accumulation"], res["depth"]),
+                            background=bg, clamp=True, ray_head_bias=ray_head_bias, mode=mode)
             return res
         # the chain of separate kernels: each is launched over R rows and processes the first `count` of them
         order_l = order.long()
         dirs_o = d.index_select(0, order_l)
         hb = None if ray_head_bias is None else ray_head_bias.index_select(0, order_l).contiguous()
-        to_distance = None
-        if occupancy_sampler:
-            edges, near_far, to_distance = self._live_sampler(lists, order, occ, count=count)
-        else:
-            edges, near_far = cpp.sample_coarse(lists[0], lists[3], order, S, biased=self.biased, count=count)
+        edges, near_far, _, to_distance = self._coarse_samples(out, lists, order, None, occ, occupancy_sampler, count=count)
         traced, edges = self._chain_passes(lists, edges, order, w, mode, count=count, occ=occ, to_distance=to_distance,
-                                           pdf=lambda e, weights_c: cpp.sample_pdf(e, weights_c, near_far, self.S_fine, count=count))
+                                           pdf=lambda e, weights_c: self._pdf_step(e, weights_c, near_far, {}, count=count))
         sigma, col = self._final_forward(traced["vertex_indices"], traced["barycentric_coordinates"], edges, dirs_o, w, mode, hb, count,
                                          occ=occ, traced=traced)
-        cpp.composite(sigma, col, edges, background=bg, clamp=True, out=(rgb, acc, depth), ray_index=order,
-                      count=count)
+        rows = self._composite_rows(sigma, col, edges, bg, "kernels", aux_outputs, clamp=True, into=(res, order, order_l, count))
         if aux_outputs:
-            # over all R rows (those from count on hold whatever their buffers held: masked below); `order` is a permutation
-            moment, dist_raw = cpp.composite_aux(sigma, edges)
-            exp_r, dist_r = aux_outputs_of(moment, dist_raw, acc.index_select(0, order_l), edges)
-            v = (torch.arange(R, device=dev) < count)[:, None]
-            res["expected_depth"].index_copy_(0, order_l, torch.where(v, exp_r, res["expected_depth"]))
-            res["distortion"].index_copy_(0, order_l, torch.where(v, dist_r, res["distortion"]))
+            _scatter_counted_(res, rows, order_l, count)
             if capture is not None:
                 capture.update(sigma=sigma, edges=edges, order=order, count=count)
-        if to_distance is not None:
-            # the median depth is a live-length coordinate: mapped per hitting ray (the rows beyond count keep the far plane)
-            d_live = depth.index_select(0, order_l)
-            depth.index_copy_(0, order_l, to_distance(d_live, out=d_live.clone()))
+        if to_distance is not None:      # (the rows beyond count keep the far plane)
+            res["depth"].index_copy_(0, order_l, _median_to_distance(res["depth"].index_select(0, order_l), to_distance, keep=True))
         return res
 
     @torch.no_grad()
-    def _render_host_compaction(self, origins, directions, bg, ray_head_bias=None, mode=None, occupancy=None,
-                                occupancy_threshold=None, occupancy_sampler=False, aux_outputs=False):
+    def _render_host_compaction(self, origins, directions, bg, ray_head_bias, mode, occ, occupancy_sampler, aux_outputs):
         """render() with the PyTorch SAMPLER statements (device_samplers=False: the parity definition of tn_sample_coarse /
-        tn_sample_pdf, ~15 small operators per pass) between the HIP kernels.  Sizes its work on the host (torch.nonzero), as
-        the reference does; not the production path."""
-        cpp, S = self.cpp, self.S
+        tn_sample_pdf, ~15 small operators per pass) between the HIP kernels, on arguments render() has checked.  Sizes its
+        work on the host (torch.nonzero), as the reference does; not the production path."""
         out = self._trace(origins, directions)
         ray_mask = out["num_visited_cells"] > 0
-        rgb, acc, depth = self._miss_frame(origins.shape[0], bg, origins.device)
+        res = self._frame(origins.shape[0], bg, origins.device, ray_mask, aux_outputs)
         idx = torch.nonzero(ray_mask)[:, 0]
-        mode = self.mlp_mode if mode is None else mode
-        occ = self._occupancy_args(occupancy, occupancy_threshold, mode)
-        aux = {"expected_depth": depth.clone(), "distortion": torch.zeros_like(acc)} if aux_outputs else {}
         if idx.numel():
             lists = trace_rows(out)
             ridx = idx.to(torch.int32)
             w = mlp_weights(self.mlp)
             hb = None if ray_head_bias is None else ray_head_bias.index_select(0, idx).contiguous()
-            near_r, far_r = hit_near_far(out, idx)
-            to_distance = None
-            if occupancy_sampler:
-                edges, near_far, to_distance = self._live_sampler(lists, ridx, occ)
-                near_r, far_r = near_far[:, 0:1], near_far[:, 1:2]
-            elif self.biased:
-                edges = biased_sample_bins(near_r, far_r, S, lists[0][idx], lists[3][idx]).contiguous()
-            else:
-                edges = uniform_sample_bins(near_r, far_r, S).contiguous()
-            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, occ=occ, to_distance=to_distance, pdf=lambda e, weights_c: pdf_sample_bins(
-                (e - near_r) / (far_r - near_r), weights_c, self.S_fine, near_r, far_r).contiguous())
+            edges, near_far, _, to_distance = self._coarse_samples(out, lists, ridx, idx, occ, occupancy_sampler)
+            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, occ=occ, to_distance=to_distance,
+                                               pdf=lambda e, weights_c: self._pdf_step(e, weights_c, near_far, {}))
             sigma, col = self._final_forward(traced["vertex_indices"], traced["barycentric_coordinates"], edges,
                                              directions[idx].contiguous(), w, mode, hb, occ=occ, traced=traced)
-            rgb_r, acc_r, depth_r = cpp.composite(sigma, col, edges, background=bg, clamp=True)
+            rows = self._composite_rows(sigma, col, edges, bg, "kernels", aux_outputs, clamp=True)
             if to_distance is not None:
-                depth_r = to_distance(depth_r.reshape(-1, 1)).view_as(depth_r)
-            rgb[idx] = rgb_r
-            acc[idx] = acc_r
-            depth[idx] = depth_r
-            if aux_outputs:
-                aux["expected_depth"][idx], aux["distortion"][idx] = aux_outputs_of(*cpp.composite_aux(sigma, edges), acc_r, edges)
-        return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask, **aux}
+                rows["depth"] = _median_to_distance(rows["depth"], to_distance)
+            _scatter_compacted_(res, rows, idx)
+        return res
 
     def _train_final_pass(self, vi, bc, edges, dirs, w, modes, hb, occ, traced, record, fused):
         """The network on the final samples of a training call -> (sigma [r,S], col [r,S,3]).  record: as autograd nodes backed by
@@ -1126,201 +1308,165 @@ class TetraRenderer:
                      occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False,
                      aux_outputs: bool = False) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
-        (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches
-        them), gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) --
-        differentiable w.r.t. the field and the MLP parameters.  fused=True: the MLP and the composite are single autograd
-        nodes backed by the HIP forward / adjoint kernels (without a graph being recorded -- `torch.no_grad()` -- the
-        non-saving forward kernels run instead); fused=False: the plain PyTorch statement (autograd through nn.Linear
-        etc.; with device_samplers=False not one HIP kernel above the tracer's ops), which is what the parity tests compare
-        against and what tests/test_reference_model.py pins with the reference's own get_outputs.  `rand` may carry the
-        uniform draws ("coarse" [r,S+1], "fine" [r,S_fine+1] over the hitting rays) so that two calls see the same
-        samples; without it they are drawn from `generator` / torch's global generator in the reference's order and
-        shapes (coarse first, then fine), so the same seed gives the reference body and this path the same draws.
-        position_gradients (opt-in; off: nothing below changes): the gradient also reaches WHERE the samples sit -- the
-        `origins` and `directions` handed in (camera pose refinement) and `vertices` f32 [V, 3] (default: the tracer's vertex
-        table; it receives a gradient when it requires one).  The final pass's barycentrics go through
-        sample_positions_grad before the MLP node (fused) or the gather (fused=False), and the view directions of the head
-        layer are differentiable too.  Tet membership, the sample distances t, near / far and the sampler draws are
-        CONSTANTS of that gradient: the coarse pass and the samplers stay under no_grad, nothing flows through the
-        tracer's hit distances.  After the vertices moved the tracer must follow them: tracer.update_vertices(vertices) while
-        the cells stay (a tracer loaded with refittable=True), load_tetrahedra after a re-triangulation, with the host build, and
-        every so often over a long optimisation (records and BVH keep the order of the loaded positions).
+        (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches them),
+        gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) -- differentiable
+        w.r.t. the field and the MLP parameters.  Tet membership, the sample distances, near / far and the sampler draws are
+        CONSTANTS of the gradient: the coarse pass and the samplers run under no_grad, nothing flows through the tracer's hit
+        distances.  Returns render()'s dict.  The stages and the forms each call path takes of them: DESIGN.md 4.14.
+        SYNC-FREE form (the renderer's sync_free_train, default for the fused path with device samplers; not with capture= or
+        rand=): training batches are pixels of the object, nearly all of their rays hit, so the batch is processed at its
+        full size R -- the hitting rays first, in ray order, the tail padded with copies of the first entry, whose (finite)
+        results and gradients are masked out -- and nothing on the host ever waits for the ray count: no gap in the launch
+        stream between the trace and the samplers.  While the last known fraction of hitting rays lies below
+        sync_free_min_hits the batch is compacted with torch.nonzero instead, as the reference does (_SyncFreeDecision).
+
+        origins, directions f32 [R,3]: the rays.
+
+        gradient_scaling: GradientScaler of the `tetra-nerf` configuration on colours and densities (model.py:625-630).
+
+        generator: the stratified draws come from it (None: torch's global generator) in the reference's order and shapes
+        -- coarse [r,S+1] first, then fine [r,S_fine+1] when there is a fine pass -- so the same seed gives the reference
+        body and this path the same draws.  In the sync-free form that holds when every ray hits (the bench batch, the parity
+        tests); with misses the draws are the first `count` rows of an [R,S+1] draw instead of an [r,S+1] draw: the same
+        distribution, another stream.
+
+        rand: may carry the uniform draws ("coarse" [r,S+1], "fine" [r,S_fine+1] over the hitting rays) so that two calls see
+        the same samples.
+
+        fused=True: the MLP and the composite are single autograd nodes backed by the HIP forward / adjoint kernels (without a
+        graph being recorded -- `torch.no_grad()` -- the non-saving forward kernels run instead); fused=False: the plain
+        PyTorch statement (autograd through nn.Linear etc.; with device_samplers=False not one HIP kernel above the tracer's
+        ops), which is what the parity tests compare against and what tests/test_reference_model.py pins with the
+        reference's own get_outputs.
+
+        capture: receives the (non-differentiable) sample placement -- idx, vertex_indices, barycentric_coordinates (the
+        matcher's), edges, dirs, near, far, samples_per_ray, cell_indices -- and, with a threshold, culled [r,S]; with
+        gradient scaling, ray_dist [r,S,1]; with position gradients, barycentric_positions.
+
+        background: per-call override of the renderer's colour, as in render().
+
+        ray_head_bias f32 [R,128] (fused path only): as in render(); differentiable w.r.t. the caller's tensor.
+
+        position_gradients (opt-in; off: nothing else changes): the gradient also reaches WHERE the samples sit -- the
+        `origins` and `directions` handed in (camera pose refinement) and `vertices`.  The final pass's barycentrics go
+        through sample_positions_grad before the MLP node (fused) or the gather (fused=False), and the view directions of the
+        head layer are differentiable too; everything the opening paragraph calls a constant stays one.  After the vertices
+        moved the tracer must follow them: tracer.update_vertices(vertices) while the cells stay (a tracer loaded with
+        refittable=True), load_tetrahedra after a re-triangulation, with the host build, and every so often over a long
+        optimisation (records and BVH keep the order of the loaded positions).
+
+        vertices f32 [V,3] (with position_gradients; default: the tracer's vertex table): receives a gradient when it
+        requires one.
+
         mlp_mode (fused path; None: the renderer's train_mlp_mode, "fp32" unless chosen otherwise): "bf16x3" runs the forward
         kernels of this call -- the coarse density pass, the recorded fine node and the no-graph fine forward -- in the
         split-operand bf16 arithmetic (same 1e-5 bar against fp32 as in render()); the adjoints take that forward's
         activations and ReLU decisions.
+
         adjoint_mode (fused path; None: the renderer's train_adjoint_mode, "fp32" unless chosen otherwise; independent of
-        mlp_mode): "bf16x3" runs the four matrix products of the recorded node's dX chain in the split-operand bf16 arithmetic
-        (tn_mlp_backward_ex); the outputs of the call do not depend on it.
-        dw_mode (fused path; None: the renderer's train_dw_mode, "fp32" unless chosen otherwise; independent of the other two):
-        "bf16x3" runs the four weight-gradient GEMMs of the recorded node in the split-operand bf16 arithmetic
+        mlp_mode): "bf16x3" runs the four matrix products of the recorded node's dX chain in the split-operand bf16
+        arithmetic (tn_mlp_backward_ex); the outputs of the call do not depend on it.
+
+        dw_mode (fused path; None: the renderer's train_dw_mode, "fp32" unless chosen otherwise; independent of the other
+        two): "bf16x3" runs the four weight-gradient GEMMs of the recorded node in the split-operand bf16 arithmetic
         (tn_mlp_param_grads_ex); neither the outputs nor the field gradient depend on it.
-        occupancy f32 [num_cells] + occupancy_decay (opt-in; both or neither, fused path): the per-tetrahedron occupancy field is
-        UPDATED in place once per batch, after the forward, from the final pass's matched cells and the detached final densities
-        (cpp.occupancy_update: occupancy[t] = max(decay occupancy[t], max sigma in t)).  Without a threshold training itself is not
-        culled: the outputs and the gradients of the batch do not depend on the field.  (The padded duplicate rays of the sync-free
-        form repeat samples of a real ray: harmless to a maximum.)
-        occupancy + occupancy_threshold (opt-in; None: the renderer's train_occupancy_threshold; needs `occupancy`, and makes
-        occupancy_decay optional -- cull without update): CULLED training.  ONE definition: the unculled training forward with
-        sigma = 0 and rgb = 0 as CONSTANTS at every culled sample of both passes, the culled samples being those
-        cull_mask_statement(cells, occupancy, threshold) names -- render()'s rule.  No gradient reaches or leaves a culled sample;
-        the samplers, GradientScaler, the composite node, the sync-free padding, position gradients and the three arithmetic
-        switches are unchanged and see full-size [r, S] tensors.  Every live sample gets, bit for bit, the outputs and per-sample
-        gradients of the unculled kernels; only sums over samples (field gradient, weight gradients, per-ray head-bias sums) run
-        over a shorter list of terms.  Fused path: the coarse pass culls as render() does; the final pass runs cpp.cull_samples,
-        READS THE LIVE COUNT BACK TO THE HOST -- one host synchronisation per culled batch, which sizes the saves (2.3 KB per live
-        sample instead of per sample) and every adjoint launch -- and records a _FusedMlpCulledFunction; the update, when asked for,
-        runs after the forward as without a threshold.  fused=False with a threshold and no decay is the PyTorch statement
-        (torch.where on the mask in both passes): the oracle of the fused path.  A culled tetrahedron contributes sigma = 0, so
-        an update can only decay it: a caller that wants it to come back runs some batches unculled
-        (nerfstudio_plugin: occupancy_refresh_every).
-        capture additionally receives cell_indices and, with a threshold, culled [r, S]; with gradient scaling, ray_dist [r, S, 1].
-        occupancy_sampler (opt-in; needs `occupancy` and a threshold, i.e. a culled batch): the occupancy-GUIDED coarse sampler
-        replaces the uniform / biased one of this call, as in render(): stratified bins over the live length of every ray, both passes
-        located through the live-to-distance map, PDF sampler and composite (node and statement alike) on the live-length edges, the
-        depth mapped back; GradientScaler takes its spacing from the mapped edges, (t(s_edges) - near) / (far - near) with the ray's
-        own far.  The sample placement stays a constant of the gradient; position_gradients=True is refused: the map has no adjoint.
-        aux_outputs (opt-in; off: nothing above changes, not a launch, not an allocation): the result also has, each [R,1] and taken
-        from the FINAL pass only,
-            "expected_depth" = depth_moment / (accumulation + 1e-10), depth_moment = sum_i w_i (e_i + e_{i+1}) / 2: the first moment of
-                the weights, nerfstudio's DepthRenderer(method="expected") without its global clip -- the depth that carries a gradient
-                (the median depth does not), what a depth loss is written on;
-            "distortion" = distortion_raw / (e_S - e_0), 0 where the span is 0: mip-NeRF 360's distortion loss (eq. 15; nerfstudio's
-                losses.lossfun_distortion on the normalised bins (e - e_0) / (e_S - e_0)) of the ray, the regulariser against floaters;
-        rays that meet nothing get far_plane and 0, and the padded rows of the sync-free form are masked like the other outputs.
-        composite_aux_statement states both sums in the literal pairwise form; fused=False evaluates it (the oracle).  Fused, with a
-        graph: ONE node, _FusedCompositeAuxFunction, in the place of _FusedCompositeFunction -- the forward adds one kernel
-        (tn_composite_aux, linear in S), the backward is still one kernel (tn_composite_backward_aux); the two divisions run in PyTorch
-        on [r] tensors.  Without a graph the forward kernels alone run.  The edges stay constants of the gradient.  GradientScaler,
-        culled training, position gradients and the three arithmetic switches need no change: the composite node sits behind them and
-        sees full-size [r, S] tensors.  occupancy_sampler=True is refused with aux_outputs: the composite's edges are then live-length
-        coordinates, and a depth or a spread measured in them is another quantity."""
-        if aux_outputs and occupancy_sampler:      # (in front of everything: an argument error, whatever else the call holds)
-            raise RuntimeError(AUX_WITH_LIVE_SAMPLER)
+
+        occupancy f32 [num_cells] (opt-in, fused path; with occupancy_decay, occupancy_threshold or both): the
+        per-tetrahedron occupancy field.
+
+        occupancy_decay (opt-in; needs `occupancy`): the field is UPDATED in place once per batch, after the forward, from the
+        final pass's matched cells and the detached final densities (cpp.occupancy_update: occupancy[t] = max(decay
+        occupancy[t], max sigma in t)); refused with fused=False (the update is a kernel; its statement is
+        occupancy_update_statement).  Without a threshold training itself is not culled: the outputs and the gradients of the
+        batch do not depend on the field.  (The padded duplicate rays of the sync-free form repeat samples of a real ray:
+        harmless to a maximum.)
+
+        occupancy_threshold (opt-in; None: the renderer's train_occupancy_threshold; needs `occupancy`, and makes
+        occupancy_decay optional -- cull without update): CULLED training.  ONE definition: the unculled training forward
+        with sigma = 0 and rgb = 0 as CONSTANTS at every culled sample of both passes, the culled samples being those
+        cull_mask_statement(cells, occupancy, threshold) names -- render()'s rule.  No gradient reaches or leaves a culled
+        sample; the samplers, GradientScaler, the composite node, the sync-free padding, position gradients and the three
+        arithmetic switches are unchanged and see full-size [r,S] tensors.  Every live sample gets, bit for bit, the outputs
+        and per-sample gradients of the unculled kernels; only sums over samples (field gradient, weight gradients, per-ray
+        head-bias sums) run over a shorter list of terms.  Fused path: the coarse pass culls as render() does; the final pass
+        runs cpp.cull_samples, READS THE LIVE COUNT BACK TO THE HOST -- one host synchronisation per culled batch, which
+        sizes the saves (2.3 KB per live sample instead of per sample) and every adjoint launch -- and records a
+        _FusedMlpCulledFunction; the update, when asked for, runs after the forward as without a threshold.  fused=False with
+        a threshold and no decay is the PyTorch statement (torch.where on the mask in both passes): the oracle of the fused
+        path.  A culled tetrahedron contributes sigma = 0, so an update can only decay it: a caller that wants it to come
+        back runs some batches unculled (nerfstudio_plugin: occupancy_refresh_every).
+
+        occupancy_sampler (opt-in; needs `occupancy` and a threshold, i.e. a culled batch): the occupancy-GUIDED coarse
+        sampler replaces the uniform / biased one of this call, as in render(): stratified bins over the live length of every
+        ray, both passes located through the live-to-distance map, PDF sampler and composite (node and statement alike) on
+        the live-length edges, the depth mapped back; GradientScaler takes its spacing from the mapped edges,
+        (t(s_edges) - near) / (far - near) with the ray's own far.  The sample placement stays a constant of the gradient;
+        position_gradients=True is refused: the map has no adjoint.
+
+        aux_outputs (opt-in; off: nothing else changes, not a launch, not an allocation): the result also has, each [R,1] and
+        taken from the FINAL pass only,
+            "expected_depth" = depth_moment / (accumulation + 1e-10), depth_moment = sum_i w_i (e_i + e_{i+1}) / 2: the first
+                moment of the weights, nerfstudio's DepthRenderer(method="expected") without its global clip -- the depth that
+                carries a gradient (the median depth does not), what a depth loss is written on;
+            "distortion" = distortion_raw / (e_S - e_0), 0 where the span is 0: mip-NeRF 360's distortion loss (eq. 15;
+                nerfstudio's losses.lossfun_distortion on the normalised bins (e - e_0) / (e_S - e_0)) of the ray, the
+                regulariser against floaters;
+        rays that meet nothing get far_plane and 0, and the padded rows of the sync-free form are masked like the other
+        outputs.  composite_aux_statement states both sums in the literal pairwise form; fused=False evaluates it (the
+        oracle).  Fused, with a graph: ONE node, _FusedCompositeAuxFunction, in the place of _FusedCompositeFunction -- the
+        forward adds one kernel (tn_composite_aux, linear in S), the backward is still one kernel
+        (tn_composite_backward_aux); the two divisions run in PyTorch on [r] tensors.  Without a graph the forward kernels
+        alone run.  The edges stay constants of the gradient.  GradientScaler, culled training, position gradients and the
+        three arithmetic switches need no change: the composite node sits behind them and sees full-size [r,S] tensors.
+        occupancy_sampler=True is refused with aux_outputs: the composite's edges are then live-length coordinates, and a
+        depth or a spread measured in them is another quantity."""
+        occ, modes = self._train_args(fused, position_gradients, mlp_mode, adjoint_mode, dw_mode, occupancy, occupancy_decay,
+                                      occupancy_threshold, occupancy_sampler, aux_outputs)
         cpp, S = self.cpp, self.S
-        thr = occupancy_threshold
-        if thr is None and occupancy is not None:
-            thr = self.train_occupancy_threshold
-        if thr is not None and occupancy is None:
-            raise RuntimeError("occupancy_threshold needs the occupancy field it is compared with: pass occupancy=")
-        if (occupancy is None) != (occupancy_decay is None) and thr is None:
-            raise RuntimeError("occupancy and occupancy_decay go together: pass both or neither (occupancy with an "
-                               "occupancy_threshold alone culls without updating)")
-        if occupancy_decay is not None and not fused:
-            raise RuntimeError("the occupancy update is a kernel of the fused path (fused=True); its statement is occupancy_update_statement")
-        occ = None if thr is None else (occupancy.detach(), float(thr))
-        if occupancy_sampler and occ is None:
-            raise RuntimeError("occupancy_sampler needs occupancy and an occupancy threshold: the field the samples follow")
-        if occupancy_sampler and position_gradients:
-            raise RuntimeError("occupancy_sampler cannot be combined with position_gradients: the live-to-distance map has no adjoint")
-        # the arithmetic of the forward kernels, of the recorded node's dX chain and of its weight-gradient GEMMs
-        modes = tuple(own if given is None else given for given, own in
-                      ((mlp_mode, self.train_mlp_mode), (adjoint_mode, self.train_adjoint_mode), (dw_mode, self.train_dw_mode)))
-        for m in modes:
-            cpp._mode(m, inference=False)
-        mode = modes[0]
         R, dev = origins.shape[0], origins.device
         rand = rand or {}
-        # SYNC-FREE form (default for the fused path): the reference compacts the hitting rays with boolean indexing
-        # (model.py:540-567: a device -> host synchronisation per call, like torch.nonzero here).  Training batches are
-        # pixels of the object: nearly all of their rays hit, so the batch is processed at its full size R instead -- the
-        # hitting rays first, in ray order (stable argsort of the miss flag), the tail padded with copies of the first entry,
-        # whose (finite) results and gradients are masked out -- and nothing on the host ever waits for the ray count:
-        # no gap in the launch stream between the trace and the samplers.  When every ray hits (the bench batch, the
-        # parity tests) the stratified draws are the reference's, element for element; with misses they are the first
-        # `count` rows of an [R, S+1] draw instead of an [r, S+1] draw -- the same distribution, another stream.
-        sync_free = self.sync_free_train and fused and self.device_samplers and capture is None and not rand and R > 0
-        self._batch_id += 1
-        if self._hits_pending is not None and self._hits_event.query():
-            # (whenever the copy has landed, whatever form THIS call takes: a renderer that alternates between forms must not
-            #  decide on a stale fraction -- nor let the count of an older batch override one the host has seen since)
-            issued, rays = self._hits_pending
-            self._hits_pending = None
-            if issued > self._hits_host_id:
-                self._hit_fraction = float(self._hits_pinned[0]) / max(float(rays), 1.0)   # of an EARLIER batch
-        sync_free = sync_free and self._hit_fraction >= self.sync_free_min_hits
-        ridx = None
+        # trace and ray set: the sync-free form (see sync_free_train) while the last known hit fraction allows it, else compaction
+        allowed = self._sync_free.begin_batch(self.sync_free_min_hits)
+        sync_free = self.sync_free_train and fused and self.device_samplers and capture is None and not rand and R > 0 and allowed
         with torch.no_grad():
             out = self._trace(origins, directions)
             nv = out["num_visited_cells"]
             ray_mask = nv > 0
             if sync_free:
-                # ONE small kernel pair (tn_compact_hits) instead of a stable argsort of the miss flag (13 rocprim launches) +
-                # where: order = the hitting rays in ray order, then the others; padded = order with the tail naming order[0]
-                order32, count, padded = self.cpp.compact_hits(nv, want_padded=True)
+                # order = the hitting rays in ray order, then the others; padded = order with the tail naming order[0]
+                order32, count, padded = cpp.compact_hits(nv, want_padded=True)
                 order = order32.long()
                 valid = torch.arange(R, device=dev) < count     # (count is a one-element device tensor: no read-back)
-                idx, ridx = padded.long(), padded
-                # asynchronous read-back of this batch's hit count for the decision of a later one: the count the compaction
-                # left on the device goes to pinned memory as it is (one copy; rounds 4's form built it from five small kernels)
-                if self._hits_pinned is None:
-                    self._hits_pinned = torch.zeros(1, dtype=torch.int32).pin_memory()
-                    self._hits_event = torch.cuda.Event()
-                if self._hits_pending is None:     # (no copy in flight: the buffer is free)
-                    self._hits_pinned.copy_(count, non_blocking=True)
-                    self._hits_event.record(torch.cuda.current_stream(dev))
-                    self._hits_pending = (self._batch_id, R)
+                idx = padded.long()
+                self._sync_free.start_copy(count, R, torch.cuda.current_stream(dev))
             else:
                 idx = torch.nonzero(ray_mask)[:, 0]
                 if self.sync_free_train:           # this form knows its count on the host anyway
-                    self._hit_fraction, self._hits_host_id = idx.numel() / max(R, 1), self._batch_id
+                    self._sync_free.host_counted(idx.numel(), R)
         bg = self._bg(background)
-        rgb, acc, depth = self._miss_frame(R, bg, dev)
-        aux = {"expected_depth": depth.clone(), "distortion": torch.zeros_like(acc)} if aux_outputs else {}
+        frame = self._frame(R, bg, dev, ray_mask, aux_outputs)
         if idx.numel() == 0:
-            return {"rgb": rgb, "accumulation": acc, "depth": depth, "ray_mask": ray_mask, **aux}
+            return frame
         lists = trace_rows(out)
-        if ridx is None:
-            ridx = idx.to(torch.int32)
+        ridx = padded if sync_free else idx.to(torch.int32)
         r = idx.numel()
         record = fused and torch.is_grad_enabled()
-        spacing = None            # spacing bins of the final samples (exact only on the PyTorch sampler path)
         # (outside the no_grad block below: an adapter may hand over differentiable VIEWS of its parameters -- the first
         # 155 columns of an mlp_head widened by an appearance embedding, nerfstudio_plugin.ModelMLP.fused_weights)
         w = mlp_weights(self.mlp)
+        # coarse samples and the sample placement of both passes: constants of the gradient
         with torch.no_grad():
-            t_rand = rand.get("coarse")
-            if t_rand is None:
-                t_rand = torch.rand((r, S + 1), device=dev, generator=generator)
-            to_distance = None
-            if occupancy_sampler:
-                edges, near_far, to_distance = self._live_sampler(lists, ridx, occ, t_rand=t_rand.contiguous())
-                near_r, far_r = near_far[:, 0:1], near_far[:, 1:2]
-            elif self.device_samplers:
-                edges, near_far = cpp.sample_coarse(lists[0], lists[3], ridx, S, biased=self.biased, t_rand=t_rand.contiguous())
-                near_r, far_r = near_far[:, 0:1], near_far[:, 1:2]
-            else:
-                near_r, far_r = hit_near_far(out, idx)
-                near_far = torch.cat([near_r, far_r], 1).contiguous()
-                edges, spacing = coarse_samples(near_r, far_r, S, self.biased, lists[0][idx], lists[3][idx], t_rand)
-                edges = edges.contiguous()
-
-            def pdf(e, weights_c):
-                nonlocal spacing
-                u_rand = rand.get("fine")
-                if u_rand is None:
-                    u_rand = torch.rand((r, self.S_fine + 1), device=dev, generator=generator)
-                if self.device_samplers:
-                    spacing = None
-                    return cpp.sample_pdf(e, weights_c, near_far, self.S_fine, u_rand=u_rand.contiguous())
-                if spacing is None:
-                    spacing = (e - near_r) / (far_r - near_r)
-                e, spacing = pdf_sample_bins(spacing, weights_c, self.S_fine, near_r, far_r, u_rand=u_rand, return_spacing=True)
-                return e.contiguous()
-
-            def weights_torch(traced, e):       # model.py:577-582 in PyTorch
-                gather = self._interpolate_values or cpp.interpolate_values
-                feats_c = gather(traced["vertex_indices"], traced["barycentric_coordinates"], self.field)
-                sigma_c = coarse_sigma(self.mlp, feats_c)
-                if occ is not None:
-                    sigma_c = torch.where(cull_mask_statement(traced["cell_indices"], *occ), torch.zeros_like(sigma_c), sigma_c)
-                return ray_weights(sigma_c, e)
-
-            traced, edges = self._chain_passes(lists, edges, ridx, w, mode, pdf, coarse_weights=None if fused else weights_torch,
-                                               occ=occ if fused else None, to_distance=to_distance)
-            S = edges.shape[1] - 1
+            t_rand = _uniform(rand, "coarse", (r, S + 1), dev, generator)
+            edges, near_far, spacing, to_distance = self._coarse_samples(out, lists, ridx, idx, occ, occupancy_sampler, t_rand=t_rand.contiguous())
+            near_r, far_r = _near_far_columns(near_far)
+            carried = {"spacing": spacing}     # spacing bins of the current edges (exact only on the PyTorch sampler path)
+            traced, edges = self._chain_passes(
+                lists, edges, ridx, w, modes[0], occ=occ if fused else None, to_distance=to_distance,
+                coarse_weights=None if fused else (lambda traced_c, e: self._coarse_weights_statement(traced_c, e, occ)),
+                pdf=lambda e, weights_c: self._pdf_step(e, weights_c, near_far, carried, u_rand=_uniform(rand, "fine", (r, self.S_fine + 1), dev, generator)))
+            spacing, S = carried["spacing"], edges.shape[1] - 1
+        # directions, per-ray bias of the head layer (appearance embedding; fused path only) and position gradients
         dirs = directions[idx].contiguous()      # (a differentiable index: the view term of position_gradients)
-        # per-ray bias of the head layer (appearance embedding; fused path only): differentiable w.r.t. the caller's tensor
         hb = None if ray_head_bias is None else ray_head_bias.index_select(0, idx).contiguous()
         if hb is not None and not fused:
             raise RuntimeError("ray_head_bias is an input of the fused kernels; the PyTorch statement takes the model's own modules")
@@ -1328,8 +1474,7 @@ class TetraRenderer:
         if position_gradients and torch.is_grad_enabled():
             from . import sample_positions_grad
 
-            if vertices is None:
-                vertices = self.tracer.tetrahedra_vertices
+            vertices = self.tracer.tetrahedra_vertices if vertices is None else vertices
             # (the distances `_locate` matched: held constant)
             bc = sample_positions_grad(bc, vi, vertices.reshape(-1, 3), origins[idx], dirs, bin_centres(edges))
             if capture is not None:
@@ -1347,39 +1492,20 @@ class TetraRenderer:
             if to_distance is not None:     # distances of the edges, over the ray's own [near, far]
                 with torch.no_grad():
                     spacing = (to_distance(edges) - near_r) / (hit_far(out, idx) - near_r)
-            if spacing is None:
-                spacing = (edges - near_r) / (far_r - near_r)
-            ray_dist = (spacing[:, 1:] + spacing[:, :-1])[..., None]      # model.py:625-630
-            if capture is not None:
-                capture["ray_dist"] = ray_dist
-            col, sg, _ = GradientScaler.apply(col, sigma[..., None], ray_dist)
-            sigma = sg[..., 0]
-        if record and aux_outputs:
-            rgb_r, acc_r, depth_r, moment_r, dist_raw_r = _FusedCompositeAuxFunction.apply(sigma, col, edges, bg)
-        elif record:
-            rgb_r, acc_r, depth_r = _FusedCompositeFunction.apply(sigma, col, edges, bg)
-        elif fused:
-            rgb_r, acc_r, depth_r = cpp.composite(sigma.contiguous(), col.contiguous(), edges, background=bg)
-            if aux_outputs:
-                moment_r, dist_raw_r = cpp.composite_aux(sigma.contiguous(), edges)
-        else:
-            rgb_r, acc_r, depth_r, _ = composite(sigma[..., None], col, edges[:, :-1, None], edges[:, 1:, None], background=bg)
-            if aux_outputs:
-                moment_r, dist_raw_r = composite_aux_statement(sigma, edges)
-        acc_r, depth_r = acc_r.reshape(-1, 1), depth_r.reshape(-1, 1).detach()
-        if aux_outputs:
-            exp_r, dist_r = aux_outputs_of(moment_r, dist_raw_r, acc_r, edges)
+            sigma, col = _scale_gradients(sigma, col, (edges - near_r) / (far_r - near_r) if spacing is None else spacing, capture)
+        rows = self._composite_rows(sigma, col, edges, bg, "node" if record else "kernels" if fused else "statement", aux_outputs)
         if to_distance is not None:
-            depth_r = to_distance(depth_r.contiguous())
-        if sync_free:     # `order` is a permutation of the rays: every row is written once, padded entries get the miss values
-            v = valid[:, None]
-            idx, rgb_r, acc_r, depth_r = order, torch.where(v, rgb_r, rgb), torch.where(v, acc_r, acc), torch.where(v, depth_r, depth)
-            if aux_outputs:
-                exp_r, dist_r = torch.where(v, exp_r, aux["expected_depth"]), torch.where(v, dist_r, aux["distortion"])
-        if aux_outputs:
-            aux = {"expected_depth": aux["expected_depth"].index_copy(0, idx, exp_r), "distortion": aux["distortion"].index_copy(0, idx, dist_r)}
-        return {"rgb": rgb.index_copy(0, idx, rgb_r), "accumulation": acc.index_copy(0, idx, acc_r),
-                "depth": depth.index_copy(0, idx, depth_r), "ray_mask": ray_mask, **aux}
+            rows["depth"] = _median_to_distance(rows["depth"], to_distance)
+        return _scatter_padded(frame, rows, order, valid[:, None]) if sync_free else _scatter_compacted(frame, rows, idx)
+
+    def _coarse_weights_statement(self, traced, edges, occ):
+        """The coarse weights of a pass in PyTorch (model.py:577-582): gather, mlp_base + density head, get_weights; occ =
+        (occupancy, threshold): zero density at the culled samples."""
+        feats_c = (self._interpolate_values or self.cpp.interpolate_values)(traced["vertex_indices"], traced["barycentric_coordinates"], self.field)
+        sigma_c = coarse_sigma(self.mlp, feats_c)
+        if occ is not None:
+            sigma_c = torch.where(cull_mask_statement(traced["cell_indices"], *occ), torch.zeros_like(sigma_c), sigma_c)
+        return ray_weights(sigma_c, edges)
 
 
 class TetraNerfModule(torch.nn.Module):
