@@ -62,7 +62,9 @@ int tn_tracer_destroy(tn_tracer_t tracer);
  * The structures are built ON THE DEVICE from these buffers (csrc/tn_build.hip; option "gpu_build" = 0 selects the
  * single-threaded host build of csrc/tn_mesh.cpp, which produces identical face tables, walk records and hull tree).
  * Blocking, like the reference's.
- * Errors: "A triangle is shared by more than two tetrahedra!", "cells contains a vertex index that is out of bounds" */
+ * Errors: "A triangle is shared by more than two tetrahedra!", "cells contains a vertex index that is out of bounds",
+ * "load_tetrahedra needs at least one tetrahedron" (num_cells = 0, either build; refused before anything is touched: a mesh
+ * loaded earlier stays loaded) */
 int tn_load_tetrahedra(tn_tracer_t tracer, size_t num_vertices, size_t num_cells,
                        const float *xyz, const uint32_t *cells, void *stream);
 

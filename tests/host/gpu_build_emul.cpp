@@ -177,23 +177,25 @@ int main(int argc, char **argv) {
         CHECK(covered == F);
     }
     // collapse: every binary leaf reachable exactly once, children numbered after their parent
-    size_t n_wide = 0, leaf_refs = 0;
+    size_t n_wide = 0, leaf_refs = 0, wide_levels = 0;
     {
         const core::BinTreeView tree{bn.data(), node_lo.data(), node_hi.data()};
         std::vector<int> wide_sub{0};
+        std::vector<size_t> depth{1};   // of every wide node, the root at 1 (the levels k_collapse is launched for)
         for (size_t w = 0; w < wide_sub.size(); ++w) {
             int kids[WIDE];
             const int nk = F ? core::collapse_node(wide_sub[w], tree, kids) : 0;
             CHECK(nk >= (F ? 1 : 0) && nk <= WIDE);
+            wide_levels = std::max(wide_levels, depth[w]);
             for (int i = 0; i < nk; ++i) {
                 if (bn[kids[i]].left < 0) ++leaf_refs;
-                else wide_sub.push_back(kids[i]);
+                else { wide_sub.push_back(kids[i]); depth.push_back(depth[w] + 1); }
             }
         }
         n_wide = wide_sub.size();
         CHECK(leaf_refs == leaf_nodes.size());
     }
-    std::printf("OK faces %zu variants %zu hull %zu bin_nodes %zu leaves %zu wide_nodes %zu\n", F, 4 * (size_t)T, hull_ids.size(), nn,
-                leaf_nodes.size(), n_wide);
+    std::printf("OK faces %zu variants %zu hull %zu bin_nodes %zu leaves %zu wide_nodes %zu wide_levels %zu\n", F, 4 * (size_t)T,
+                hull_ids.size(), nn, leaf_nodes.size(), n_wide, wide_levels);
     return 0;
 }

@@ -506,11 +506,14 @@ int tn_load_tetrahedra(tn_tracer_t tracer, size_t V, size_t T, const float *xyz,
         hipStream_t stream = (hipStream_t)stream_;
         if ((V && !xyz) || (T && !cells)) throw tn::Error("xyz / cells must not be null");
         if (V >= 0xFFFFFFFFull || T >= 0x0FFFFFFFull) throw tn::Error("mesh too large (uint32 ids)");
+        // either build: refused here, ahead of the first allocation and launch (a mesh without cells has no face, no record
+        // and no tree for the trace kernels to read)
+        if (T == 0) throw tn::Error("load_tetrahedra needs at least one tetrahedron");
         tn_tracer::Mesh &b = t->mesh;
         b.loaded = false;
         b.host.faces.clear(); b.host.face_tets.clear();
         b.refit.release();
-        b.device_built = t->opt.gpu_build && T > 0;
+        b.device_built = t->opt.gpu_build;
         BuildCounts n;
         if (b.device_built) {
             // everything is built on the device from the caller's buffers (tn_build.hip)
