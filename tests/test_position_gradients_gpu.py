@@ -12,6 +12,8 @@ Every bound below is a priori; u = 2^-24 is the fp32 unit round-off:
        by n_terms >= 1).  The weights w are the forward's own: w_0 = 1 - ((b0 + b1) + b2) evaluated in fp32, the bits that
        tn_interp.hip's kernels, the deterministic adjoint and k_sample_positions_bwd all form from the same barycentrics, so
        the float64 reference sums w32_k m64 (geometry.sample_positions_backward(weights=gather_weights(b32))).
+The reference and the bounds of (B) are position_grad_cases.m64_and_cond / sample_bound / sums_and_bounds, shared with
+tests/test_position_grad_edges_gpu.py, which holds (B) to them at the edges of its launch and on dead samples.
 """
 import importlib
 
@@ -19,9 +21,11 @@ import numpy as np
 import pytest
 import torch
 
+import position_grad_cases as pgc
+
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
+U = pgc.U
 BIG = (45000, 2, 4096, 256)      # the C4 mesh and training batch: points, seed, rays, samples per ray
 SMALL = (1500, 1, 37, 19)        # one small odd size
 
@@ -65,28 +69,6 @@ def _batch(tn, scenes, device, spec):
     assert int(b["mask"].sum()) > 0.5 * R * S
     _CACHE[spec] = b
     return b
-
-
-def _m64_and_cond(batch, grad_bary):
-    """float64 solve T m = g on the fp32 inputs and cond2(T), on the CPU, for the samples whose four ids are present;
-    -> (m64 [n,3] (zeros elsewhere), cond [n] (1 elsewhere), present [n]) on the batch's device."""
-    dev = grad_bary.device
-    vi = batch["vi"].reshape(-1, 4).cpu().long()
-    present = (vi >= 0).all(-1)
-    x = batch["verts"].cpu().double()[vi[present]]
-    T = x[:, 1:] - x[:, :1]
-    g = grad_bary.reshape(-1, 3).cpu().double()[present]
-    m = torch.linalg.solve(T, g.unsqueeze(-1)).squeeze(-1)
-    uniq, inv = torch.unique(vi[present], dim=0, return_inverse=True)
-    xu = batch["verts"].cpu().double()[uniq]
-    sv = torch.linalg.svdvals(xu[:, 1:] - xu[:, :1])
-    cond_u = sv[:, 0] / sv[:, -1]
-    n = vi.shape[0]
-    m64 = torch.zeros(n, 3, dtype=torch.float64)
-    cond = torch.ones(n, dtype=torch.float64)
-    m64[present] = m
-    cond[present] = cond_u[inv]
-    return m64.to(dev), cond.to(dev), present.to(dev)
 
 
 def _check_bary_adjoint(geometry, got, vi, field_vm, rows, what):
@@ -179,12 +161,12 @@ def test_sample_positions_backward(tn, device, scenes, geometry, spec):
     pts, go, gd, gv = cpp.sample_positions_backward(b["vi"], b["bc"], gb, b["verts"], b["dist"], want_points=True,
                                                     want_origins=True, want_directions=True, want_vertices=True)
     # -- grad_points
-    m64, cond, present = _m64_and_cond(b, gb)
+    m64, cond, present = pgc.m64_and_cond(b["vi"], b["verts"], gb)
     assert torch.equal(present, b["mask"].reshape(-1))
     m32 = pts.reshape(-1, 3)
     assert bool(torch.isfinite(m32).all())
     assert bool((m32[~present] == 0).all())
-    bound_s = 8 * U * cond * m64.norm(dim=-1)                       # [n]
+    bound_s = pgc.sample_bound(cond, m64)                           # [n]
     err_s = (m32.double() - m64).norm(dim=-1)
     ratio = float((err_s[present] / bound_s[present]).max())
     print(f"(B) {spec}: cond max {float(cond.max()):.3g}, worst ||m32 - m64|| / (8 u cond ||m64||) = {ratio:.3f}")
@@ -193,23 +175,9 @@ def test_sample_positions_backward(tn, device, scenes, geometry, spec):
     p2, o2, d2, v2 = cpp.sample_positions_backward(b["vi"], b["bc"], gb, b["verts"], None, want_origins=True)
     assert p2 is None and d2 is None and v2 is None and torch.equal(o2, go)
 
-    # -- sums: float64 over w32_k m64, m64 and t m64
-    n = R * S
-    live = present.double()
-    w = geometry.gather_weights(b["bc"].reshape(-1, 3)).double() * live[:, None]           # the forward's own weights
-    ids = b["vi"].reshape(-1, 4).long().clamp_min(0)
-    terms = -(w[:, :, None] * m64[:, None, :])                                           # [n, 4, 3]
-    want_v = torch.zeros(V, 3, dtype=torch.float64, device=device).index_add_(0, ids.reshape(-1), terms.reshape(-1, 3))
-    abs_v = torch.zeros_like(want_v).index_add_(0, ids.reshape(-1), terms.abs().reshape(-1, 3))
-    cnt_v = torch.zeros(V, dtype=torch.float64, device=device).index_add_(0, ids.reshape(-1), live[:, None].expand(-1, 4).reshape(-1))
-    bsum_v = torch.zeros(V, dtype=torch.float64, device=device).index_add_(0, ids.reshape(-1), (w.abs() * bound_s[:, None]).reshape(-1))
-    bound_v = bsum_v[:, None] + cnt_v[:, None] * U * abs_v
-    t = b["dist"].reshape(-1).double()
-    want_o = m64.reshape(R, S, 3).sum(1)
-    want_d = (t[:, None] * m64).reshape(R, S, 3).sum(1)
-    n_live = live.reshape(R, S).sum(1)[:, None]
-    bound_o = bound_s.reshape(R, S).sum(1)[:, None] + n_live * U * m64.abs().reshape(R, S, 3).sum(1)
-    bound_d = (t.abs() * bound_s).reshape(R, S).sum(1)[:, None] + n_live * U * (t[:, None] * m64).abs().reshape(R, S, 3).sum(1)
+    # -- sums: float64 over w32_k m64, m64 and t m64 (the forward's own weights)
+    sums = pgc.sums_and_bounds(b["vi"], geometry.gather_weights(b["bc"].reshape(-1, 3)), m64, bound_s, present, b["dist"], R, S, V)
+    want_v, bound_v, want_o, bound_o, want_d, bound_d = (sums[k] for k in ("want_v", "bound_v", "want_o", "bound_o", "want_d", "bound_d"))
 
     def check(name, got, want, bound):
         err = (got.double() - want).abs()
@@ -240,7 +208,7 @@ def test_matcher_barycentrics_follow_the_stated_convention(tn, device, scenes, g
     fp32 estimate at this conditioning is below 1e-3).  At most 10 % of the matched samples may fall to the cond cut."""
     b = _batch(tn, scenes, device, spec)
     R, S = b["R"], b["S"]
-    _, cond, present = _m64_and_cond(b, torch.zeros(R, S, 3, device=device))
+    _, cond, present = pgc.m64_and_cond(b["vi"], b["verts"], torch.zeros(R, S, 3, device=device))
     keep = present & (cond <= 200)
     assert int(keep.sum()) >= 0.9 * int(present.sum()), (int(keep.sum()), int(present.sum()))
     p = (b["o"].double()[:, None, :] + b["dist"].double()[..., None] * b["d"].double()[:, None, :]).reshape(-1, 3)[keep]
@@ -303,8 +271,7 @@ def test_render_train_position_gradients_wiring(tn, device, scenes, geometry, re
     dist = ((cap["edges"][:, 1:] + cap["edges"][:, :-1]) / 2)
     gb = seen[0].reshape(-1, 3)
     assert float(gb.abs().max()) > 0
-    batch = dict(vi=vi, verts=table)
-    m64, cond, present = _m64_and_cond(batch, gb)
+    m64, cond, present = pgc.m64_and_cond(vi, table, gb)
     want = geometry.sample_positions_backward(vi.reshape(-1, 4), bc.reshape(-1, 3).double(), gb.double(), table.double(),
                                               dist.reshape(-1).double(), S2, weights=geometry.gather_weights(bc.reshape(-1, 3)).double())
     # bounds of the sums (see the module docstring)

@@ -15,7 +15,8 @@ barycentrics b = (b0, b1, b2) [n, 3].  The forward statement is
 (B) `sample_positions_backward`: dL/dp = m with T m = g, in closed form
         m = (g0 (e2 x e3) + g1 (e3 x e1) + g2 (e1 x e2)) / (e1 . (e2 x e3)),   e_k = x_k - x_0;
     vertex v_k receives -w_k m with w = (1 - (b0+b1+b2), b0, b1, b2); a ray receives dL/do = sum_s m, dL/dd = sum_s t_s m.
-    A sample with an EMPTY id, a zero determinant or a non-finite m contributes exact zeros everywhere.
+    A sample with an EMPTY (or out-of-range) id, a zero determinant or a non-finite m contributes exact zeros everywhere; an
+    id-dead sample does so whatever its barycentrics, distance and gradient hold.
 
 Tet membership (the vertex ids), t, near / far and the sampler draws are CONSTANTS of these gradients.
 """
@@ -71,17 +72,21 @@ def sample_positions_backward(vertex_indices: torch.Tensor, barycentrics: torch.
     samples_per_ray S (n = R S; None: no per-ray sums).  weights [n, 4]: the gather's weights if they are not to be formed
     from `barycentrics` in this dtype (a float64 check of the float32 kernels passes gather_weights(b_float32)).
     Returns a dict: points [n, 3] = m; vertices [V, 3]; origins [R, 3] = sum_s m; directions [R, 3] = sum_s t_s m
-    (the last two only with samples_per_ray, the last only with distances)."""
+    (the last two only with samples_per_ray, the last only with distances).
+    A sample that is not `live` contributes exact zeros whatever its barycentrics, distance and gradient hold (a row the
+    matcher never wrote may hold NaN): its terms are SELECTED away, not multiplied by zero."""
     m, live = sample_point_gradient(vertex_indices, grad_bary, vertices)
     w = gather_weights(barycentrics) if weights is None else weights
     ids, _ = _ids(vertex_indices, vertices.shape[0])
-    terms = -(w[:, :, None] * m[:, None, :]) * live[:, None, None].to(m.dtype)          # [n, 4, 3]
+    terms = -(w[:, :, None] * m[:, None, :])                                            # [n, 4, 3]
+    terms = torch.where(live[:, None, None], terms, torch.zeros_like(terms))
     out = {"points": m, "live": live,
            "vertices": torch.zeros_like(vertices).index_add_(0, ids.reshape(-1), terms.reshape(-1, 3))}
     if samples_per_ray is not None:
         out["origins"] = m.reshape(-1, int(samples_per_ray), 3).sum(1)
         if distances is not None:
-            out["directions"] = (distances.reshape(-1, 1) * m).reshape(-1, int(samples_per_ray), 3).sum(1)
+            tm = distances.reshape(-1, 1) * m
+            out["directions"] = torch.where(live[:, None], tm, torch.zeros_like(tm)).reshape(-1, int(samples_per_ray), 3).sum(1)
     return out
 
 

@@ -640,8 +640,9 @@ def sample_positions_backward(vertex_indices, barycentric_coordinates, grad_bary
         vertices [V,3]: vertex v_k receives -w_k m, w = (1 - (b0+b1+b2), b0, b1, b2)
     -- summed with float atomics, or, under deterministic_gradients(), by one writer per element in a fixed order (-m
     through tn_interpolate_values_backward_vm_det with field_dim = 3).  Samples with an EMPTY id, a zero determinant or a
-    non-finite m contribute exact zeros.  Tet membership, t, near / far and the sampler draws are constants of the
-    gradient.  Returns (points, origins, directions, vertices), None where not asked for."""
+    non-finite m contribute exact zeros; an id-dead sample (an id that is EMPTY or >= V) does so whatever its barycentrics,
+    distance and gradient hold, on the atomic and on the deterministic path.  Tet membership, t, near / far and the sampler
+    draws are constants of the gradient.  Returns (points, origins, directions, vertices), None where not asked for."""
     for x, name in ((vertex_indices, "vertex_indices"), (barycentric_coordinates, "barycentric_coordinates"),
                     (grad_bary, "grad_bary"), (vertices, "vertices")) + (() if distances is None else ((distances, "distances"),)):
         _check_input(x, name)
@@ -666,7 +667,11 @@ def sample_positions_backward(vertex_indices, barycentric_coordinates, grad_bary
                                                     _ptr(distances), _ptr(vertices), _ptr(points), _ptr(origins), _ptr(directions),
                                                     None if det else _ptr(grad_v), stream))
         if det and R * S:
-            _lib.check(lib.tn_interpolate_values_backward_vm_det(4, V, R * S, 3, _ptr(vertex_indices), _ptr(barycentric_coordinates),
+            # the gather's adjoint skips an id >= V but still adds w * (-0) through the other three ids of that sample, which
+            # is NaN for a non-finite w: a sample with any id that is EMPTY or >= V hands it four EMPTY ids
+            absent = ((vertex_indices < 0) | (vertex_indices >= V)).any(-1, keepdim=True)
+            ids = torch.where(absent, torch.full_like(vertex_indices, -1), vertex_indices)
+            _lib.check(lib.tn_interpolate_values_backward_vm_det(4, V, R * S, 3, _ptr(ids), _ptr(barycentric_coordinates),
                                                                  _ptr(points.neg()), _ptr(grad_v), stream))
     return (points if want_points else None), origins, directions, grad_v
 
