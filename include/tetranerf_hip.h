@@ -744,6 +744,40 @@ int tn_composite_backward_aux(size_t num_rays, uint32_t num_samples, const float
                               const float *d_out_depth_moment, const float *d_out_distortion, float *d_sigma, float *d_rgb,
                               void *stream);
 
+/* The RAdam step of a training iteration (addition, same ABI version: nothing existing changes).  Replaces torch.optim.RAdam
+ * (torch/optim/radam.py, the single-tensor form), the optimiser of the reference's one parameter group "fields" -- the vertex
+ * field and the MLP (tetranerf/nerfstudio/registration.py:37-45) -- which PyTorch runs as a chain of element-wise launches over
+ * whole tensors, and the transposition that its in-place step causes before the next gather.  Per element, every line one fp32
+ * operation and one rounding, every scalar rounded to fp32 once by the caller:
+ *   decay_mode 1 (coupled, decay = wd):            g = g + decay * p
+ *   decay_mode 2 (decoupled, decay = 1 - lr wd):   p = p * decay
+ *   m = m + one_minus_beta1 * (g - m)
+ *   v = beta2 * v + (one_minus_beta2 * g) * g
+ *   adaptive != 0:  p = p - (step_size * m) / (sqrt(v) + eps)        adaptive == 0:  p = p - step_size * m
+ * with, for step count t >= 1 in double precision on the host: bc1 = 1 - b1^t, bc2 = 1 - b2^t, rho_inf = 2 / (1 - b2) - 1,
+ * rho_t = rho_inf - 2 t b2^t / bc2; rho_t > 5: step_size = lr sqrt((rho_t-4)(rho_t-2) rho_inf / ((rho_inf-4)(rho_inf-2) rho_t))
+ * sqrt(bc2) / bc1, adaptive = 1; otherwise step_size = lr / bc1, adaptive = 0.  m = exp_avg and v = exp_avg_sq keep torch's
+ * layout (the parameter's), so optimiser state interchanges with torch.optim.RAdam.  fp32 denormals are kept and non-finite
+ * gradients propagate as in torch; neither is part of the contract.  The caller's stream; no synchronisation, no allocation. */
+typedef struct tn_radam_hyper {
+    float one_minus_beta1, beta2, one_minus_beta2, eps, decay;
+    int decay_mode;              /* 0: no weight decay, 1: coupled, 2: decoupled */
+} tn_radam_hyper;
+typedef struct tn_radam_tensor {
+    float *param;                /* count contiguous f32; 4-byte alignment suffices */
+    const float *grad;
+    float *exp_avg, *exp_avg_sq;
+    size_t count;
+    float step_size;             /* of THIS tensor's step count: parameters of a group can sit at different counts */
+    int adaptive;
+} tn_radam_tensor;
+/* field, grad, exp_avg, exp_avg_sq f32 [64, num_vertices] feature-major, updated in place in one pass; shadow_vm f32
+ * [num_vertices, 64] (nullable) receives the new field vertex-major in the same pass, bit-equal to tn_transpose_f32 of it. */
+int tn_radam_step_field(uint32_t num_vertices, float *field, const float *grad, float *exp_avg, float *exp_avg_sq, float *shadow_vm,
+                        float step_size, int adaptive, const tn_radam_hyper *hyper, void *stream);
+/* num_tensors contiguous tensors of one parameter group, one launch per 32 of them; a tensor of count 0 is skipped. */
+int tn_radam_step(size_t num_tensors, const tn_radam_tensor *tensors, const tn_radam_hyper *hyper, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ SYMBOLS = (
     "tn_sample_live", "tn_live_to_distance",       # the occupancy-guided sampler: the reference declares the field and never uses it
     "tn_composite_aux", "tn_composite_backward_aux",   # expected-depth moment + distortion loss and their adjoint (nerfstudio renderers / losses)
     "tn_tet_quality", "tn_limit_vertex_step",      # the vertex step limiter: the reference has no counterpart (it never moves vertices)
+    "tn_radam_step_field", "tn_radam_step",        # the optimiser step (registration.py:37-45: RAdam on the field and the MLP)
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -129,6 +130,8 @@ def load():
     lib.tn_mlp_param_grads_indexed.argtypes = [vp, sz, sz, u32, vp, vp, vp, vp, i32, vp]
     lib.tn_mlp_ray_head_grad_indexed.argtypes = [sz, sz, u32, vp, vp, vp, vp]
     lib.tn_compact_rows.argtypes = [u32, sz, vp, vp, vp, vp]
+    lib.tn_radam_step_field.argtypes = [u32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp]
+    lib.tn_radam_step.argtypes = [sz, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int and name not in ("tn_last_error", "tn_version", "tn_abi_version", "tn_num_faces", "tn_refit_table_bytes"):

@@ -155,4 +155,47 @@ int tn_scatter_ema_uint32(int elem_size, uint32_t num_result, uint32_t num_indic
     });
 }
 
+/* the RAdam step (tn_optim.hip): what torch.optim.RAdam runs as a chain of element-wise launches; the statement is in
+ * include/tetranerf_hip.h */
+static tn::RadamHyper radam_hyper(const tn_radam_hyper *hyper) {
+    if (!hyper) throw tn::Error("radam step: hyper is null");
+    if (hyper->decay_mode < 0 || hyper->decay_mode > 2) throw tn::Error("radam step: decay_mode must be 0, 1 or 2");
+    return tn::RadamHyper{hyper->one_minus_beta1, hyper->beta2, hyper->one_minus_beta2, hyper->eps, hyper->decay, hyper->decay_mode};
+}
+
+int tn_radam_step_field(uint32_t num_vertices, float *field, const float *grad, float *exp_avg, float *exp_avg_sq, float *shadow_vm,
+                        float step_size, int adaptive, const tn_radam_hyper *hyper, void *stream_) {
+    return guarded([&] {
+        const tn::RadamHyper h = radam_hyper(hyper);
+        if (num_vertices == 0) return;
+        if (!field || !grad || !exp_avg || !exp_avg_sq) throw tn::Error("radam step: null pointer");
+        tn::launch_radam_field(num_vertices, field, grad, exp_avg, exp_avg_sq, shadow_vm, h, step_size, adaptive != 0,
+                               (hipStream_t)stream_);
+        TN_HIP(hipGetLastError());
+    });
+}
+
+int tn_radam_step(size_t num_tensors, const tn_radam_tensor *tensors, const tn_radam_hyper *hyper, void *stream_) {
+    return guarded([&] {
+        const tn::RadamHyper h = radam_hyper(hyper);
+        if (num_tensors == 0) return;
+        if (!tensors) throw tn::Error("radam step: the tensor table is null");
+        // the table of one launch is built from at most RADAM_TABLE entries at a time: no allocation here
+        for (size_t i = 0; i < num_tensors; ++i) {      // (all of them before the first launch: a refused call writes nothing)
+            const tn_radam_tensor &t = tensors[i];
+            if (t.count && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)) throw tn::Error("radam step: null pointer");
+        }
+        tn::RadamTensor part[tn::RADAM_TABLE];
+        for (size_t i0 = 0; i0 < num_tensors; i0 += tn::RADAM_TABLE) {
+            const size_t k = num_tensors - i0 < tn::RADAM_TABLE ? num_tensors - i0 : tn::RADAM_TABLE;
+            for (size_t i = 0; i < k; ++i) {
+                const tn_radam_tensor &t = tensors[i0 + i];
+                part[i] =tn::RadamTensor{t.param, t.grad, t.exp_avg, t.exp_avg_sq, (uint64_t)t.count, t.step_size, t.adaptive != 0, 0u};
+            }
+            tn::launch_radam_flat(k, part, h, (hipStream_t)stream_);
+            TN_HIP(hipGetLastError());
+        }
+    });
+}
+
 }  // extern "C"

@@ -303,6 +303,17 @@ void launch_composite_backward_aux(size_t R, uint32_t S, const float *sigma, con
                                    const float *d_out_rgb, const float *d_out_acc, const float *d_out_moment, const float *d_out_dist,
                                    float *d_sigma, float *d_rgb, hipStream_t stream);
 void launch_transpose(const float *in, float *out, uint32_t rows, uint32_t cols, hipStream_t stream);
+// The RAdam step (tn_optim.hip; the statement is there).  RadamHyper: the scalars of a parameter group, each rounded to fp32
+// once by the caller; decay_mode 0 none, 1 coupled (decay = wd: g += wd p), 2 decoupled (decay = 1 - lr wd: p *= decay).
+struct RadamHyper { float one_minus_beta1, beta2, one_minus_beta2, eps, decay; int decay_mode; };
+// one contiguous tensor of n elements with the step size and branch of ITS step count; first_block is the launcher's
+struct RadamTensor { float *p; const float *g; float *m; float *v; uint64_t n; float a; int adaptive; uint32_t first_block; };
+constexpr uint32_t RADAM_TABLE = 32;   // tensors per launch of k_radam_flat (the table is a kernel argument: 32 x 56 B)
+struct RadamTable { RadamTensor t[RADAM_TABLE]; uint32_t count; };
+// field [64, V] feature-major with g / m / v in the same layout; shadow [V, 64] (nullable) receives the new field, vertex-major
+void launch_radam_field(uint32_t V, float *p, const float *g, float *m, float *v, float *shadow, const RadamHyper &h, float a,
+                        bool adaptive, hipStream_t stream);
+void launch_radam_flat(size_t count, const RadamTensor *tensors, const RadamHyper &h, hipStream_t stream);
 // everything between trace_rays and the frame as ONE persistent launch (tn_render_rays.hip): coarse sampler -> match -> gather +
 // MLP (density) -> weights -> PDF sampler -> match -> gather + MLP + heads -> composite, scattered into out_* (arrays over ALL rays)
 // at the hitting rays ray_index[0 .. *count) (count null: r_max); S_fine = 0: one pass.  dirs [R_all, 3], ray_bias [R_all, 128] or

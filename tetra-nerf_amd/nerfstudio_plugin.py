@@ -435,6 +435,26 @@ def make_fused_model_class(base_cls):
     return FusedTetrahedraNerf
 
 
+def use_fused_radam(trainer_config) -> List[str]:
+    """Opt in to the HIP optimiser step: every entry of `trainer_config.optimizers` (name -> {"optimizer": config, ...},
+    registration.py:37-45: the one group "fields", RAdamOptimizerConfig) whose optimiser config's `_target` is torch.optim.RAdam
+    gets `_target = optim.FusedRAdam` -- nerfstudio's `setup` calls `_target(params, lr=, eps=, weight_decay=)`, which FusedRAdam
+    takes with torch's names and defaults.  Duck-typed: no nerfstudio import.  Returns the names it changed; nothing is installed
+    unless this is called."""
+    from .optim import FusedRAdam
+
+    changed = []
+    for name, entry in (getattr(trainer_config, "optimizers", None) or {}).items():
+        cfg = entry.get("optimizer") if isinstance(entry, dict) else getattr(entry, "optimizer", None)
+        if cfg is not None and getattr(cfg, "_target", None) is torch.optim.RAdam:
+            try:
+                cfg._target = FusedRAdam
+            except AttributeError:           # (a frozen dataclass)
+                object.__setattr__(cfg, "_target", FusedRAdam)
+            changed.append(name)
+    return changed
+
+
 def load_reference_checkpoint(model, state_dict, prefix: str = ""):
     """Copy a reference checkpoint's parameters into a model through `copy_` (bumps the version counters the weight /
     field caches watch) after checking the architecture; returns the model."""

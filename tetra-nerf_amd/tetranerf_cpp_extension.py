@@ -480,6 +480,27 @@ def register_field(field):
     return field
 
 
+def field_is_registered(field) -> bool:
+    hit = _FIELD_VM.get(id(field))
+    return hit is not None and hit[0]() is field
+
+
+def install_field_shadow(field, shadow, event=None):
+    """Hand the cache of a registered `field` [F, V] a vertex-major `shadow` [V, F] that a kernel on the current stream has just
+    written for the field's CURRENT version (optim.FusedRAdam: the step stores it in the pass that updates the field): the next
+    field_vertex_major(field) returns it without a transposition.  `event` (a torch.cuda.Event to reuse; default a new one) is
+    recorded on the current stream, as after a transposition.  The caller owns the claim that the two agree
+    (TETRANERF_HIP_CHECK_CACHES=1 compares them at every use)."""
+    hit = _FIELD_VM.get(id(field))
+    _check(hit is not None and hit[0]() is field, "install_field_shadow: the field is not registered (cpp.register_field)")
+    _check(shadow.dtype == torch.float32 and shadow.is_contiguous() and shadow.device == field.device
+           and tuple(shadow.shape) == (field.shape[1], field.shape[0]), "install_field_shadow: shadow must be f32 [V, F] on the field's device")
+    ev = torch.cuda.Event() if event is None else event
+    ev.record(torch.cuda.current_stream(field.device))
+    _FIELD_VM[id(field)] = (hit[0], field._version, field.data_ptr(), shadow, ev)
+    return ev
+
+
 def unregister_field(field):
     _FIELD_VM.pop(id(field), None)
 
