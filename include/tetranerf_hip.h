@@ -116,6 +116,42 @@ int tn_tet_quality(tn_tracer_t tracer, size_t num_vertices, const float *xyz, fl
 int tn_limit_vertex_step(tn_tracer_t tracer, size_t num_vertices, const float *xyz_old, float *xyz_new, float fraction,
                          float *star_width, uint32_t *counters, uint32_t flags, void *stream);
 
+/* Delaunay monitor (no reference counterpart: the reference never moves vertices).  A limited vertex step keeps every tetrahedron
+ * valid, not the mesh Delaunay; this entry counts the interior faces of the loaded mesh that are not locally Delaunay on `xyz`
+ * (csrc/tn_delaunay.hip, csrc/tn_delaunay_core.h).  One lane per face of the loaded face table: with
+ * face_tets[f] = (t0, t1), p0..p3 = xyz[cells[t0]] in stored order and e = xyz[the vertex of cells[t1] that cells[t0] does not
+ * name], the face is VIOLATED iff e lies strictly inside the circumsphere of t0, i.e. iff the 4 x 4 in-sphere determinant
+ * (translated by e) and the 3 x 3 orientation determinant (translated by p3) have the same sign.  Both are Shewchuk's stage-A
+ * expressions in double on the fp32 coordinates, each with its permanent; a determinant is CERTAIN iff its magnitude exceeds
+ * (16 + 224 eps) eps permanent (in-sphere) or (7 + 56 eps) eps permanent (orientation), eps = 2^-53 -- a-priori bounds that cover
+ * the rounding of the differences, so a certain sign is the exact sign.  There is no exact fallback on the device.
+ *   face_state     i8 [F], optional: 0 hull face (t1 empty), 1 regular (both certain, e not inside), 2 violated (both certain,
+ *                  e inside), 3 uncertain (either filter fails: cospherical points, zero-volume tetrahedra, NaN).
+ *   tet_violations u8 [T], optional: the violated faces of every tetrahedron, 0..4.  Counted through 32-bit atomics: the storage
+ *                  must be 4-byte aligned and 4 ceil(T / 4) bytes long; all of it is zeroed by the call.
+ *   counters       u32 [4], zeroed by the call: interior faces, violated, uncertain, and violated faces whose t0 is certainly of
+ *                  negative orientation AS STORED (((p1-p0) x (p2-p0)) . (p3-p0) < 0).  In a table stored with positive
+ *                  orientations the last one counts inverted cells: the caller moved vertices without tn_limit_vertex_step.
+ * Works on any loaded tracer, host or device build (it reads the borrowed `cells` and the face table), leaves the tracer alone,
+ * launches on `stream`, reads nothing back and allocates nothing.
+ * Errors (nothing is touched): tracer not loaded; num_vertices != the loaded V; xyz / counters null; tet_violations misaligned. */
+int tn_delaunay_check(tn_tracer_t tracer, size_t num_vertices, const float *xyz, uint32_t *counters, int8_t *face_state,
+                      uint8_t *tet_violations, void *stream);
+
+/* Per-tetrahedron state across a change of cells, without point location (csrc/tn_delaunay.hip).  For values >= 0 (the occupancy
+ * field):   star_max[v] = max{ old_values[t] : old_cells[t] names v }  (0 where no old cell names v),
+ *           new_values[t'] = max of star_max over the four vertices of new_cells[t'].
+ * Conservative: a new tetrahedron gets at least the value of every old tetrahedron around each of its vertices, so nothing that was
+ * live is culled by the transfer; the price is a dilation by one ring of tetrahedra.  The rule the kernels follow is the maximum
+ * of the values' BIT PATTERNS as unsigned integers, which is the maximum of non-negative floats; NaN and negative values are not
+ * checked and follow that rule (a set sign bit beats everything).  Vertex ids >= num_vertices are passed over.
+ * old_cells u32 [num_old_cells, 4], old_values f32 [num_old_cells], new_cells u32 [num_new_cells, 4], new_values f32
+ * [num_new_cells] (out), star_max f32 [num_vertices] (out: the call's scratch), all on the current device.  Needs no tracer;
+ * launches on `stream`, reads nothing back and allocates nothing.  Errors (nothing is touched): a null pointer beside a non-zero
+ * count. */
+int tn_remap_tet_values(size_t num_vertices, size_t num_old_cells, const uint32_t *old_cells, const float *old_values,
+                        size_t num_new_cells, const uint32_t *new_cells, float *new_values, float *star_max, void *stream);
+
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);
 

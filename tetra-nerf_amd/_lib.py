@@ -34,6 +34,7 @@ SYMBOLS = (
     "tn_sample_live", "tn_live_to_distance",       # the occupancy-guided sampler: the reference declares the field and never uses it
     "tn_composite_aux", "tn_composite_backward_aux",   # expected-depth moment + distortion loss and their adjoint (nerfstudio renderers / losses)
     "tn_tet_quality", "tn_limit_vertex_step",      # the vertex step limiter: the reference has no counterpart (it never moves vertices)
+    "tn_delaunay_check", "tn_remap_tet_values",    # the Delaunay monitor and the per-tetrahedron state transfer of a re-triangulation
     "tn_radam_step_field", "tn_radam_step",        # the optimiser step (registration.py:37-45: RAdam on the field and the MLP)
 )
 
@@ -68,6 +69,8 @@ def load():
     lib.tn_update_vertices.argtypes = [vp, sz, vp, vp]
     lib.tn_tet_quality.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.tn_limit_vertex_step.argtypes = [vp, sz, vp, vp, C.c_float, vp, vp, u32, vp]
+    lib.tn_delaunay_check.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.tn_remap_tet_values.argtypes = [sz, sz, vp, vp, sz, vp, vp, vp, vp]
     lib.tn_refit_table_bytes.restype = sz
     lib.tn_refit_table_bytes.argtypes = [vp]
     lib.tn_num_faces.restype = sz

@@ -629,6 +629,32 @@ int tn_limit_vertex_step(tn_tracer_t tracer, size_t V, const float *xyz_old, flo
     });
 }
 
+int tn_delaunay_check(tn_tracer_t tracer, size_t V, const float *xyz, uint32_t *counters, int8_t *face_state, uint8_t *tet_violations,
+                      void *stream_) {
+    return guarded([&] {
+        tn_tracer *t = checked(tracer);
+        std::lock_guard<std::mutex> lock(t->mu);
+        check_guard_mesh(t, "tn_delaunay_check", V);
+        const tn::DeviceMesh &m = t->mesh.view;
+        if (!xyz || !counters) throw tn::Error("tn_delaunay_check: xyz and counters must not be null");
+        if ((uintptr_t)tet_violations & 3u)
+            throw tn::Error("tn_delaunay_check: tet_violations must be 4-byte aligned (its bytes are counted through 32-bit atomics)");
+        DeviceGuard g(t->device);
+        tn::launch_delaunay_check(m.T, m.F, m.cells, m.face_tets, xyz, counters, face_state, tet_violations, (hipStream_t)stream_);
+    });
+}
+
+int tn_remap_tet_values(size_t V, size_t num_old_cells, const uint32_t *old_cells, const float *old_values, size_t num_new_cells,
+                        const uint32_t *new_cells, float *new_values, float *star_max, void *stream_) {
+    return guarded([&] {
+        if (V >= 0xFFFFFFFFull) throw tn::Error("tn_remap_tet_values: too many vertices (uint32 ids)");
+        if ((num_old_cells && (!old_cells || !old_values)) || (num_new_cells && (!new_cells || !new_values)) || (V && !star_max))
+            throw tn::Error("tn_remap_tet_values: old_cells, old_values, new_cells, new_values and star_max must not be null");
+        tn::launch_remap_tet_values(V, num_old_cells, old_cells, old_values, num_new_cells, new_cells, new_values, star_max,
+                                    (hipStream_t)stream_);
+    });
+}
+
 size_t tn_num_faces(tn_tracer_t tracer) { return tracer && tracer->mesh.loaded ? tracer->mesh.view.F : 0; }
 
 int tn_get_faces(tn_tracer_t tracer, uint32_t *faces_host, uint32_t *face_tets_host) {

@@ -76,4 +76,14 @@ void launch_tet_quality(size_t V, size_t T, const uint32_t *cells, const float *
 void launch_limit_vertex_step(size_t V, size_t T, const uint32_t *cells, const float *xyz_old, float *xyz_new, float fraction,
                               float *star_width, uint32_t *counters, bool verify, hipStream_t s);
 
+// The Delaunay monitor and the per-tetrahedron state transfer (tn_delaunay.hip; the predicate and the rule: tn_delaunay_core.h).
+// Both enqueue on `s` and return: no read-back, no device allocation.  launch_delaunay_check: counters u32 [4] zeroed and then =
+// interior faces, violated, uncertain, violated with an inverted first tetrahedron; face_state i8 [F] and tet_violations u8 [T]
+// (zeroed here; 4-byte aligned storage of 4 ceil(T / 4) bytes) may be null.  launch_remap_tet_values: star_max f32 [V] is the
+// call's scratch (zeroed here); vertex ids >= V are passed over.
+void launch_delaunay_check(size_t T, size_t F, const uint32_t *cells, const uint32_t *face_tets, const float *xyz, uint32_t *counters,
+                           int8_t *face_state, uint8_t *tet_violations, hipStream_t s);
+void launch_remap_tet_values(size_t V, size_t T_old, const uint32_t *old_cells, const float *old_values, size_t T_new,
+                             const uint32_t *new_cells, float *new_values, float *star_max, hipStream_t s);
+
 }  // namespace tn

@@ -1,4 +1,5 @@
-"""The position gradients, and the vertex step limiter (at the end of the file), stated once in plain torch (any device).
+"""The position gradients, the vertex step limiter and (at the end of the file) the Delaunay monitor with its state transfer,
+stated once in plain torch / numpy (any device).
 
 What csrc/tn_position_grad.hip computes on the device, as the definition the tests hold it to -- the way ray_order.py
 states the binning key.  Nothing here needs a GPU or the library.
@@ -24,6 +25,7 @@ from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
 EMPTY = 0xFFFFFFFF
@@ -206,3 +208,151 @@ def limit_vertex_step_statement(xyz_old: torch.Tensor, xyz_new: torch.Tensor, ce
     counters = torch.stack([clamped.sum(), (frozen & (new != old).any(-1)).sum(), (before * after < 0).sum(),
                             ((before != 0) & (after == 0)).sum()])
     return {"xyz": out, "star_width": star, "frozen": frozen, "clamped": clamped, "counters": counters}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The Delaunay monitor and the per-tetrahedron state transfer (csrc/tn_delaunay_core.h, csrc/tn_delaunay.hip; DESIGN.md
+# section 4.16), stated in float64 on numpy arrays -- or on torch tensors of any device, through the same text: the expressions
+# use nothing but + - * abs and comparisons, one rounding per operation in the order written here, which is the order of the
+# element functions.  IEEE double + - * are correctly rounded everywhere, so the results are, bit for bit, what the kernels give.
+
+DELAUNAY_EPS = 2.0 ** -53
+INSPHERE_BOUND = (16.0 + 224.0 * DELAUNAY_EPS) * DELAUNAY_EPS      # Shewchuk's stage-A bound of the in-sphere determinant
+ORIENT_BOUND = (7.0 + 56.0 * DELAUNAY_EPS) * DELAUNAY_EPS          # ... and of the orientation determinant
+FACE_HULL, FACE_REGULAR, FACE_VIOLATED, FACE_UNCERTAIN = 0, 1, 2, 3
+
+
+def orient_det(p):
+    """p float64 [n, 4, 3] -> (det, permanent) of the 3 x 3 orientation determinant translated by p3 (its sign is the opposite
+    of tet_orient's)"""
+    adx, ady, adz = p[:, 0, 0] - p[:, 3, 0], p[:, 0, 1] - p[:, 3, 1], p[:, 0, 2] - p[:, 3, 2]
+    bdx, bdy, bdz = p[:, 1, 0] - p[:, 3, 0], p[:, 1, 1] - p[:, 3, 1], p[:, 1, 2] - p[:, 3, 2]
+    cdx, cdy, cdz = p[:, 2, 0] - p[:, 3, 0], p[:, 2, 1] - p[:, 3, 1], p[:, 2, 2] - p[:, 3, 2]
+    bdxcdy, cdxbdy = bdx * cdy, cdx * bdy
+    cdxady, adxcdy = cdx * ady, adx * cdy
+    adxbdy, bdxady = adx * bdy, bdx * ady
+    det = (adz * (bdxcdy - cdxbdy) + bdz * (cdxady - adxcdy)) + cdz * (adxbdy - bdxady)
+    perm = ((abs(bdxcdy) + abs(cdxbdy)) * abs(adz) + (abs(cdxady) + abs(adxcdy)) * abs(bdz)) + (abs(adxbdy) + abs(bdxady)) * abs(cdz)
+    return det, perm
+
+
+def insphere_det(p, e):
+    """p float64 [n, 4, 3], e float64 [n, 3] -> (det, permanent) of the 4 x 4 in-sphere determinant translated by e"""
+    aex, aey, aez = p[:, 0, 0] - e[:, 0], p[:, 0, 1] - e[:, 1], p[:, 0, 2] - e[:, 2]
+    bex, bey, bez = p[:, 1, 0] - e[:, 0], p[:, 1, 1] - e[:, 1], p[:, 1, 2] - e[:, 2]
+    cex, cey, cez = p[:, 2, 0] - e[:, 0], p[:, 2, 1] - e[:, 1], p[:, 2, 2] - e[:, 2]
+    dex, dey, dez = p[:, 3, 0] - e[:, 0], p[:, 3, 1] - e[:, 1], p[:, 3, 2] - e[:, 2]
+    aexbey, bexaey = aex * bey, bex * aey
+    ab = aexbey - bexaey
+    bexcey, cexbey = bex * cey, cex * bey
+    bc = bexcey - cexbey
+    cexdey, dexcey = cex * dey, dex * cey
+    cd = cexdey - dexcey
+    dexaey, aexdey = dex * aey, aex * dey
+    da = dexaey - aexdey
+    aexcey, cexaey = aex * cey, cex * aey
+    ac = aexcey - cexaey
+    bexdey, dexbey = bex * dey, dex * bey
+    bd = bexdey - dexbey
+    abc = (aez * bc - bez * ac) + cez * ab
+    bcd = (bez * cd - cez * bd) + dez * bc
+    cda = (cez * da + dez * ac) + aez * cd
+    dab = (dez * ab + aez * bd) + bez * da
+    alift = (aex * aex + aey * aey) + aez * aez
+    blift = (bex * bex + bey * bey) + bez * bez
+    clift = (cex * cex + cey * cey) + cez * cez
+    dlift = (dex * dex + dey * dey) + dez * dez
+    det = (dlift * abc - clift * dab) + (blift * cda - alift * bcd)
+    aezp, bezp, cezp, dezp = abs(aez), abs(bez), abs(cez), abs(dez)
+    abp, bcp, cdp = abs(aexbey) + abs(bexaey), abs(bexcey) + abs(cexbey), abs(cexdey) + abs(dexcey)
+    dap, acp, bdp = abs(dexaey) + abs(aexdey), abs(aexcey) + abs(cexaey), abs(bexdey) + abs(dexbey)
+    perm = ((((cdp * bezp + bdp * cezp) + bcp * dezp) * alift + ((dap * cezp + acp * dezp) + cdp * aezp) * blift) +
+            (((abp * dezp + bdp * aezp) + dap * bezp) * clift + ((bcp * aezp + acp * bezp) + abp * cezp) * dlift))
+    return det, perm
+
+
+def _as_index(x):
+    """int64 ids of an integer array or tensor; the int32 view of a uint32 id (EMPTY = -1) comes back as the uint32"""
+    if isinstance(x, torch.Tensor):
+        v = x.long()
+        return torch.where(v < 0, v + (1 << 32), v)
+    v = np.asarray(x).astype(np.int64)
+    return np.where(v < 0, v + (1 << 32), v)
+
+
+def delaunay_faces(cells, face_tets):
+    """The gather of the monitor.  cells integer [T, 4], face_tets integer [F, 2] (TetrahedraTracer.face_tables) ->
+    (interior bool [F], t0 [n], t1 [n], e [n]) over the n interior faces: e = the first vertex of cells[t1] that cells[t0] does not
+    name (the last one where it names all four)."""
+    xp = torch if isinstance(cells, torch.Tensor) else np
+    c, ft = _as_index(cells), _as_index(face_tets)
+    interior = ft[:, 1] != EMPTY
+    t0, t1 = ft[:, 0][interior], ft[:, 1][interior]
+    c0, c1 = c[t0], c[t1]
+    new = (c1[:, :, None] != c0[:, None, :]).all(-1)
+    e = c1[:, 3]
+    for k in (2, 1, 0):
+        e = xp.where(new[:, k], c1[:, k], e)
+    return interior, t0, t1, e
+
+
+def delaunay_face_statement(cells, face_tets, xyz):
+    """What tn_delaunay_check computes.  cells integer [T, 4], face_tets integer [F, 2], xyz float32 [V, 3]: numpy arrays, or
+    torch tensors of one device (the result is of the same kind).  Returns a dict: "face_state" int8 [F] (0 hull, 1 regular,
+    2 violated, 3 uncertain), "tet_violations" uint8 [T], "counters" int64 [4] = interior faces, violated, uncertain, violated
+    with t0 certainly of negative orientation as stored; and, over the interior faces only, "interior" bool [F], "insphere" /
+    "orient" = (det, permanent) of the two determinants."""
+    as_torch = isinstance(xyz, torch.Tensor)
+    xp = torch if as_torch else np
+    if not as_torch:
+        cells, face_tets, xyz = np.asarray(cells), np.asarray(face_tets), np.asarray(xyz)
+    interior, t0, t1, e = delaunay_faces(cells, face_tets)
+    x = xyz.double() if as_torch else xyz.astype(np.float64)
+    p = x[_as_index(cells)[t0]]
+    ins, ori = insphere_det(p, x[e]), orient_det(p)
+    certain = (abs(ins[0]) > INSPHERE_BOUND * ins[1]) & (abs(ori[0]) > ORIENT_BOUND * ori[1])
+    inside = (ins[0] > 0) == (ori[0] > 0)
+    violated = certain & inside
+    inverted = violated & (ori[0] > 0)
+    T, F = len(cells), len(face_tets)
+    if as_torch:
+        state = torch.where(certain, torch.where(inside, FACE_VIOLATED, FACE_REGULAR), FACE_UNCERTAIN).to(torch.int8)
+        face_state = torch.zeros(F, dtype=torch.int8, device=xyz.device)
+        face_state[interior] = state
+        per_tet = torch.bincount(torch.cat([t0[violated], t1[violated]]), minlength=T).to(torch.uint8)
+        counters = torch.stack([interior.sum(), violated.sum(), (~certain).sum(), inverted.sum()])
+    else:
+        state = np.where(certain, np.where(inside, FACE_VIOLATED, FACE_REGULAR), FACE_UNCERTAIN).astype(np.int8)
+        face_state = np.zeros(F, np.int8)
+        face_state[interior] = state
+        per_tet = np.bincount(np.concatenate([t0[violated], t1[violated]]), minlength=T).astype(np.uint8)
+        counters = np.array([interior.sum(), violated.sum(), (~certain).sum(), inverted.sum()], np.int64)
+    return {"face_state": face_state, "tet_violations": per_tet, "counters": counters, "interior": interior, "insphere": ins,
+            "orient": ori}
+
+
+def remap_tet_values_statement(old_cells, new_cells, values, num_vertices: int):
+    """What tn_remap_tet_values computes.  old_cells integer [T, 4], values float32 [T], new_cells integer [T', 4]: numpy arrays, or
+    torch tensors of one device.  star_max[v] = the largest value over the old cells that name v (0 where none does), new value
+    = the largest star_max of the new cell's four vertices -- "largest" by the values' BIT PATTERNS as unsigned integers, which is
+    the larger float for the non-negative values the transfer is for; NaN and negative values follow that rule unchecked.
+    Vertex ids >= num_vertices are passed over.  Returns {"values": float32 [T'], "star_max": float32 [num_vertices]}."""
+    V = int(num_vertices)
+    if isinstance(values, torch.Tensor):
+        co, cn = _as_index(old_cells), _as_index(new_cells)
+        bits = values.contiguous().view(torch.int32).long() & 0xFFFFFFFF
+        ok = co < V
+        star = torch.zeros(V, dtype=torch.int64, device=values.device)
+        star.scatter_reduce_(0, co[ok], bits[:, None].expand(-1, 4)[ok], "amax", include_self=True)
+        okn = cn < V
+        got = torch.where(okn, star[torch.where(okn, cn, torch.zeros_like(cn))], torch.zeros_like(cn)).amax(1) if len(cn) else star[:0]
+        f32 = lambda b: torch.where(b >= (1 << 31), b - (1 << 32), b).to(torch.int32).view(torch.float32)   # noqa: E731
+        return {"values": f32(got), "star_max": f32(star)}
+    co, cn = _as_index(old_cells), _as_index(new_cells)
+    bits = np.ascontiguousarray(values, np.float32).view(np.uint32)
+    ok = co < V
+    star = np.zeros(V, np.uint32)
+    np.maximum.at(star, co[ok], np.broadcast_to(bits[:, None], co.shape)[ok])
+    okn = cn < V
+    got = np.where(okn, star[np.where(okn, cn, 0)], 0).astype(np.uint32).max(1) if len(cn) else star[:0]
+    return {"values": got.view(np.float32), "star_max": star.view(np.float32)}

@@ -46,7 +46,9 @@ used) -- `occupancy_threshold` (evaluation renders skip the network in tetrahedr
 batches update the buffer: max(decay occupancy, max density seen)) and `occupancy_train_threshold` (training batches skip the
 network in tetrahedra below it, except every `occupancy_refresh_every`-th one, default 16, which runs unculled); and
 `refit_vertices` (the tracer follows a vertex table an optimiser moves: `_follow_vertices` below) with `vertex_step_fraction`
-(each followed move is first shortened so that no tetrahedron turns inside out: `TetrahedraTracer.limit_vertex_step`).
+(each followed move is first shortened so that no tetrahedron turns inside out: `TetrahedraTracer.limit_vertex_step`) and
+`delaunay_check_every` / `retriangulate_above` (every so many followed iterations the interior faces that stopped being Delaunay
+are counted, and above that fraction of them the vertices get new cells: `_monitor_delaunay` below).
 
 nerfstudio is not installed in this environment: the adapter is duck-typed (it only touches the attribute names listed
 above) and is tested with stand-ins of nerfstudio's MLP / FieldHead / RayBundle (tests/golden/nerfstudio_standins.py).
@@ -228,7 +230,45 @@ def _renderer_for(model, tracer):
     return rd
 
 
-def _follow_vertices(tracer, model=None, fraction=None):
+def _monitor_delaunay(tracer, model, above, keep_snapshot):
+    """One look at the Delaunay monitor (`config.delaunay_check_every`), and a re-triangulation where
+    `config.retriangulate_above` asks for one.  The counters of `tracer.delaunay_check()` on the vertices the tracer follows
+    (interior faces, violated, uncertain, violated with an inverted first tetrahedron) accumulate in
+    `model._tn_delaunay_counters`, an int64 tensor on the device.  With a threshold the first two are read back -- the ONE host
+    synchronisation of the monitor -- and when violated / interior exceeds it `tracer.retriangulate` gives the vertices new cells
+    (blocking: Qhull on the CPU, then a load): the model's `tetrahedra_cells` buffer and, where it has one, its
+    `tetrahedra_occupancy` buffer (carried over conservatively: `remap_tet_values`) are REPLACED by tensors of the new size under
+    their names, so a state dict keeps its keys, and `config.num_tetrahedra_cells`, which sizes both at construction, follows.
+    What is keyed by vertex -- the field, its optimiser state -- does not change.  Returns True after a re-triangulation."""
+    counters = tracer.delaunay_check()["counters"]
+    total = getattr(model, "_tn_delaunay_counters", None) if model is not None else None
+    if total is None or total.device != counters.device:
+        total = torch.zeros(4, dtype=torch.int64, device=counters.device)
+        if model is not None:
+            model._tn_delaunay_counters = total
+    total += counters
+    if above is None:
+        return False
+    interior, violated = counters[:2].tolist()
+    if interior == 0 or violated <= float(above) * interior:
+        return False
+    occupancy = getattr(model, "tetrahedra_occupancy", None) if model is not None else None
+    out = tracer.retriangulate(tracer.tetrahedra_vertices, () if occupancy is None else (occupancy.detach(),))
+    if model is not None:
+        model.tetrahedra_cells = out["cells"]
+        if occupancy is not None:
+            model.tetrahedra_occupancy = out["tet_values"][0]
+        if hasattr(getattr(model, "config", None), "num_tetrahedra_cells"):
+            model.config.num_tetrahedra_cells = int(out["num_tetrahedra"])
+        model._tn_retriangulations = getattr(model, "_tn_retriangulations", 0) + 1
+    v = tracer.tetrahedra_vertices
+    if keep_snapshot:
+        tracer._tn_vertex_snapshot = v.detach().clone()
+    tracer._tn_vertex_key = (v._version, v.data_ptr())
+    return True
+
+
+def _follow_vertices(tracer, model=None, fraction=None, delaunay_check_every=None, retriangulate_above=None):
     """`config.refit_vertices` (opt-in; no such field in the reference's config): the tracer's tables follow the vertex table
     it borrows.  The (version counter, storage) of `tracer.tetrahedra_vertices` is remembered at load / refit and the tracer is
     refitted (`update_vertices`: the cells stay, everything that holds positions is recomputed) before the trace whenever
@@ -241,9 +281,15 @@ def _follow_vertices(tracer, model=None, fraction=None):
     fraction)` writes the vertex tensor in place, so the optimiser's parameter itself holds the limited positions -- then the
     tracer is refitted and the snapshot updated.  The key is taken again after the in-place write.  The call's counters
     (clamped, frozen but asked to move, flipped, collapsed) accumulate in `model._tn_vertex_step_counters`, an int64 tensor on
-    the device; nothing is read back here."""
+    the device; nothing is read back here.
+
+    `config.delaunay_check_every` (opt-in, with refit_vertices; absent or None: nothing new runs) with `config.retriangulate_above`
+    (a fraction of the interior faces; None: the monitor only counts): on every delaunay_check_every-th call, after the tracer
+    has followed the vertices, `_monitor_delaunay` above."""
     if not getattr(tracer, "supports_refit", False):
         raise RuntimeError("config.refit_vertices needs a tracer with update_vertices (tetranerf_cpp_extension.TetrahedraTracer)")
+    if delaunay_check_every is not None and not getattr(tracer, "supports_delaunay_check", False):
+        raise RuntimeError("config.delaunay_check_every needs a tracer with delaunay_check (tetranerf_cpp_extension.TetrahedraTracer)")
     if fraction is not None and not getattr(tracer, "supports_vertex_step_limit", False):
         raise RuntimeError("config.vertex_step_fraction needs a tracer with limit_vertex_step (tetranerf_cpp_extension.TetrahedraTracer)")
     v = tracer.tetrahedra_vertices
@@ -270,6 +316,10 @@ def _follow_vertices(tracer, model=None, fraction=None):
     if fraction is not None and snapshot is None:
         tracer._tn_vertex_snapshot = v.detach().clone()
     tracer._tn_vertex_key = key
+    if delaunay_check_every is not None:
+        calls = tracer._tn_follow_calls = getattr(tracer, "_tn_follow_calls", 0) + 1
+        if int(delaunay_check_every) >= 1 and calls % int(delaunay_check_every) == 0:
+            _monitor_delaunay(tracer, model, retriangulate_above, fraction is not None)
 
 
 def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
@@ -290,8 +340,15 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
         raise ValueError("populate_fields() must be called before get_outputs")
     tracer = model.get_tetrahedra_tracer()          # lazy mesh initialisation + structure build (model.py:394-407)
     step_fraction = getattr(model.config, "vertex_step_fraction", None)
+    check_every = getattr(model.config, "delaunay_check_every", None)
     if getattr(model.config, "refit_vertices", False):
-        _follow_vertices(tracer, model, step_fraction)
+        if check_every is None:
+            _follow_vertices(tracer, model, step_fraction)
+        else:
+            _follow_vertices(tracer, model, step_fraction, check_every, getattr(model.config, "retriangulate_above", None))
+    elif check_every is not None:
+        raise ValueError("config.delaunay_check_every needs config.refit_vertices = True: the monitor looks at the vertices the "
+                         "tracer follows, and a re-triangulation reloads that tracer")
     elif step_fraction is not None:
         raise ValueError("config.vertex_step_fraction needs config.refit_vertices = True: the limiter shortens a move against "
                          "the vertices of the last refit, and only a tracer that follows the vertices has one")

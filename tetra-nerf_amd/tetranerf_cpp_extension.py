@@ -234,6 +234,52 @@ class TetrahedraTracer:
                                                           _ptr(counters), 0 if verify else 1, _stream(dev)))
             return counters, star
 
+    supports_delaunay_check = True
+    DELAUNAY_GRID_LANES = 1024 * 256         # lanes of the monitor's kernels at their grid cap (tn_delaunay.hip: DELAUNAY_BLOCKS * BT)
+
+    def delaunay_check(self, xyz=None, face_state: bool = False, tet_violations: bool = False):
+        """Is the loaded mesh still Delaunay on `xyz` (None: the loaded vertices)?  (No reference counterpart; tn_delaunay_check,
+        geometry.delaunay_face_statement; the predicate and its bound: DESIGN.md section 4.16.)  Every interior face is tested
+        once: it is violated iff the vertex behind it lies strictly inside the circumsphere of the tetrahedron in front of it, in
+        double with a proven error bound; a face the bound cannot decide (cospherical points, zero-volume tetrahedra) is uncertain.
+        Returns {"counters": int32 [4] on the device -- interior faces, violated, uncertain, violated with a first tetrahedron of
+        negative orientation as stored; "face_state": int8 [F] (0 hull, 1 regular, 2 violated, 3 uncertain; rows as
+        face_tables()) or None; "tet_violations": uint8 [T], the violated faces of each tetrahedron, or None}.
+        Nothing is read back: look at the counters when you would synchronise anyway.  The tracer is not touched."""
+        with torch.no_grad():
+            if xyz is None:
+                xyz = self.tetrahedra_vertices
+                _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
+            self._check_loaded_vertices(xyz, "xyz")
+            V, T, dev = xyz.size(0), self.tetrahedra_cells.numel() // 4, self._device
+            counters = _empty((4,), dtype=torch.int32, device=dev)
+            state = _empty((int(self._lib.tn_num_faces(self._h)),), dtype=torch.int8, device=dev) if face_state else None
+            # counted through 32-bit atomics: whole words of storage behind the T bytes that are returned
+            per_tet = _empty((4 * ((T + 3) // 4),), dtype=torch.uint8, device=dev) if tet_violations else None
+            with _on(dev):
+                _lib.check(self._lib.tn_delaunay_check(self._h, V, _ptr(xyz), _ptr(counters), _ptr(state), _ptr(per_tet), _stream(dev)))
+            return {"counters": counters, "face_state": state, "tet_violations": None if per_tet is None else per_tet[:T]}
+
+    def retriangulate(self, xyz, tet_values=()):
+        """Give the vertices `xyz` (float32 [V, 3] on the tracer's device, the loaded V) new cells and load them: cells =
+        triangulate(xyz) -- Qhull, on the CPU --, every array of `tet_values` (float32 [T] of values >= 0 on the loaded cells: the
+        occupancy field) carried to the new cells by remap_tet_values, then load_tetrahedra(xyz, cells, refittable=what this tracer
+        was loaded with).  Returns {"cells": int32 [T', 4] (borrowed by the tracer from now on), "tet_values": the carried arrays
+        in the order given, "num_tetrahedra": T'}.  BLOCKING: a copy of the vertices to the host, the triangulation, and the load.
+        If the triangulation fails the tracer stays as it was.  The field cache is invalidated, as by every load."""
+        with torch.no_grad():
+            self._check_loaded_vertices(xyz, "xyz")
+            old_cells, V = self.tetrahedra_cells, xyz.size(0)
+            tet_values = tuple(tet_values)
+            for t in tet_values:
+                _check_input(t, "tet_values")
+                _check(t.dtype == torch.float32 and t.dim() == 1 and t.numel() == old_cells.numel() // 4 and t.device == self._device,
+                       "tet_values must be float32 [T] arrays over the loaded cells, on the tracer's device")
+            cells = triangulate(xyz).to(torch.int32).contiguous()         # raises on a Qhull failure: nothing touched so far
+            carried = [remap_tet_values(old_cells, cells, t, V) for t in tet_values]
+            self.load_tetrahedra(xyz, cells, refittable=self._refittable)
+            return {"cells": cells, "tet_values": carried, "num_tetrahedra": cells.size(0)}
+
     supports_compact_rows = True
     supports_bin_rays = True
 
@@ -967,6 +1013,33 @@ def occupancy_update(occupancy, cells, sigma, decay, samples_per_ray=None, count
         _lib.check(_lib.load().tn_occupancy_update(occupancy.numel(), n, _ptr(cells), _ptr(sigma), float(decay), _ptr(occupancy),
                                                    int(samples_per_ray or 0), _ptr(count), _stream(dev)))
     return occupancy
+
+
+def remap_tet_values(old_cells, new_cells, values, num_vertices, return_star_max=False):
+    """Per-tetrahedron values (>= 0: the occupancy field) carried from `old_cells` to `new_cells` over the same vertices, without
+    point location (tn_remap_tet_values; statement: geometry.remap_tet_values_statement):
+        star_max[v] = max{ values[t] : old_cells[t] names v },  new[t'] = max of star_max over the four vertices of new_cells[t'].
+    Conservative -- a new tetrahedron is at least as live as every old one around each of its vertices -- at the price of a
+    dilation by one ring, which the next occupancy_update decays.  old_cells i32 [T, 4], values f32 [T], new_cells i32 [T', 4] on one
+    device.  NaN and negative values are not checked: the kernels take the maximum of the BIT PATTERNS as unsigned integers.
+    Caller's stream, no host synchronisation.  Returns f32 [T'] (with return_star_max: also star_max f32 [num_vertices])."""
+    for c, name in ((old_cells, "old_cells"), (new_cells, "new_cells")):
+        _check_input(c, name)
+        _check(c.dtype == torch.int32 and c.dim() == 2 and c.size(1) == 4, f"{name} must be int32 [num_cells, 4]")
+    _check_input(values, "values")
+    dev = values.device
+    _check(values.dtype == torch.float32 and values.dim() == 1 and values.numel() == old_cells.size(0),
+           "values must be f32 with one value per row of old_cells")
+    _check(old_cells.device == dev and new_cells.device == dev, "old_cells, new_cells and values must be on the same device")
+    V = int(num_vertices)
+    _check(V >= 0, "num_vertices must not be negative")
+    with torch.no_grad():
+        out = _empty((new_cells.size(0),), dtype=torch.float32, device=dev)
+        star = _empty((V,), dtype=torch.float32, device=dev)
+        with _on(dev):
+            _lib.check(_lib.load().tn_remap_tet_values(V, old_cells.size(0), _ptr(old_cells), _ptr(values), new_cells.size(0),
+                                                       _ptr(new_cells), _ptr(out), _ptr(star), _stream(dev)))
+    return (out, star) if return_star_max else out
 
 
 _CULL_SCRATCH = {}   # device -> i32 scratch of cull_samples (tile counts), allocated once and grown on demand
