@@ -152,6 +152,39 @@ int tn_delaunay_check(tn_tracer_t tracer, size_t num_vertices, const float *xyz,
 int tn_remap_tet_values(size_t num_vertices, size_t num_old_cells, const uint32_t *old_cells, const float *old_values,
                         size_t num_new_cells, const uint32_t *new_cells, float *new_values, float *star_max, void *stream);
 
+/* Isosurface extraction (no reference counterpart: the reference renders its field and never meshes it).  Marching tetrahedra on
+ * the mesh the field lives on: the level set { values = level } of the piecewise-linear interpolant of a per-vertex scalar over
+ * any tetrahedron soup, as a WELDED, consistently ORIENTED triangle mesh in a DETERMINISTIC order (csrc/tn_isosurface.hip, the
+ * rule once in csrc/tn_isosurface_core.h; every output is bit-equal to geometry.isosurface_statement).
+ *   xyz f32 [V,3], cells u32 [T,4], values f32 [V], tet_mask u8 [T] (nullable; 0 = skip), all on the current device.
+ *   inside(v) = values[v] >= level.  A tetrahedron is skipped if its mask byte is 0, an id is >= V, or one of its four values is
+ *   not finite or is >= 2^126 in magnitude.  Tet edges 0..5 = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) in stored corner order; an edge
+ *   crosses if its ends differ in `inside`; three crossing edges give one triangle, four give two.  Each triangle is oriented so
+ *   that (q1-q0) x (q2-q0) points towards values < level in a tetrahedron whose ((p1-p0) x (p2-p0)) . (p3-p0) is >= 0 as
+ *   evaluated by tn_tet_quality's orientation, and the other way round in one where it is negative.
+ *   A surface vertex belongs to a mesh edge (a, b), a < b, and is computed once from the sorted pair, in fp32 with one rounding
+ *   per operation and no fused multiply-add:  t = (level - values[a]) / (values[b] - values[a]) in [0, 1],
+ *   p = xyz[a] + t (xyz[b] - xyz[a]).  A value equal to level is inside and yields the endpoint itself; the zero-area triangles
+ *   this makes are kept.  Vertices ascend by (a << 32 | b); triangles ascend by tetrahedron, then by table row.
+ * Two entries with one small read-back between them, which is the caller's:
+ * tn_isosurface_count: tri_offsets / ref_offsets u32 [T+1] = exclusive sums over the tetrahedra of their triangles (0, 1, 2) and
+ *   crossing edges (0, 3, 4); the totals num_triangles / num_refs are the last elements.
+ * tn_isosurface_emit:  given those arrays and totals (host values), triangles u32 [num_triangles,3] (welded vertex ids),
+ *   triangle_tets u32 [num_triangles] (the source tetrahedron), and -- capacity num_refs each, the first *num_out_vertices rows
+ *   written -- edge_vertices u32 [.,2] = (a, b), edge_t f32 [.], positions f32 [.,3]; num_out_vertices u32 [1] on the device.
+ *   Every store is bounded by the totals passed: a caller who changed `values` between the two entries gets a wrong mesh, never
+ *   a write outside its buffers.
+ * Neither needs a tracer.  Both launch on `stream`, read nothing back, use no atomics and take their scratch as one
+ * stream-ordered allocation.  T == 0, or no crossing edge, gives empties (offsets of zeros, *num_out_vertices = 0) without a
+ * launch.  Errors (nothing is touched): a null pointer beside a non-zero count; level not finite or >= 2^126 in magnitude;
+ * num_cells >= 2^30; num_vertices >= 2^32 - 1; num_triangles > 2 num_cells or num_refs > 4 num_cells. */
+int tn_isosurface_count(size_t num_vertices, size_t num_cells, const uint32_t *cells, const float *values, float level,
+                        const uint8_t *tet_mask, uint32_t *tri_offsets, uint32_t *ref_offsets, void *stream);
+int tn_isosurface_emit(size_t num_vertices, size_t num_cells, const float *xyz, const uint32_t *cells, const float *values,
+                       float level, const uint8_t *tet_mask, const uint32_t *tri_offsets, const uint32_t *ref_offsets,
+                       size_t num_triangles, size_t num_refs, uint32_t *triangles, uint32_t *triangle_tets,
+                       uint32_t *edge_vertices, float *edge_t, float *positions, uint32_t *num_out_vertices, void *stream);
+
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);
 

@@ -35,6 +35,7 @@ SYMBOLS = (
     "tn_composite_aux", "tn_composite_backward_aux",   # expected-depth moment + distortion loss and their adjoint (nerfstudio renderers / losses)
     "tn_tet_quality", "tn_limit_vertex_step",      # the vertex step limiter: the reference has no counterpart (it never moves vertices)
     "tn_delaunay_check", "tn_remap_tet_values",    # the Delaunay monitor and the per-tetrahedron state transfer of a re-triangulation
+    "tn_isosurface_count", "tn_isosurface_emit",   # marching tetrahedra on the field's own mesh: the reference never meshes its field
     "tn_radam_step_field", "tn_radam_step",        # the optimiser step (registration.py:37-45: RAdam on the field and the MLP)
 )
 
@@ -71,6 +72,8 @@ def load():
     lib.tn_limit_vertex_step.argtypes = [vp, sz, vp, vp, C.c_float, vp, vp, u32, vp]
     lib.tn_delaunay_check.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.tn_remap_tet_values.argtypes = [sz, sz, vp, vp, sz, vp, vp, vp, vp]
+    lib.tn_isosurface_count.argtypes = [sz, sz, vp, vp, C.c_float, vp, vp, vp, vp]
+    lib.tn_isosurface_emit.argtypes = [sz, sz, vp, vp, vp, C.c_float, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_refit_table_bytes.restype = sz
     lib.tn_refit_table_bytes.argtypes = [vp]
     lib.tn_num_faces.restype = sz

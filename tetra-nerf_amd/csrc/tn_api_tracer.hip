@@ -9,6 +9,7 @@
 #include "tn_api_common.h"
 #include "tn_build.h"
 #include "tn_devbuf.h"
+#include "tn_isosurface_core.h"
 #include "tn_kernels.h"
 
 using tn::check_loaded;
@@ -652,6 +653,42 @@ int tn_remap_tet_values(size_t V, size_t num_old_cells, const uint32_t *old_cell
             throw tn::Error("tn_remap_tet_values: old_cells, old_values, new_cells, new_values and star_max must not be null");
         tn::launch_remap_tet_values(V, num_old_cells, old_cells, old_values, num_new_cells, new_cells, new_values, star_max,
                                     (hipStream_t)stream_);
+    });
+}
+
+namespace {
+// the checks both isosurface entries share (nothing is touched when one fails)
+void check_isosurface_args(const char *who, size_t V, size_t T, const uint32_t *cells, const float *values, float level) {
+    if (V >= 0xFFFFFFFFull) throw tn::Error(std::string(who) + ": too many vertices (uint32 ids)");
+    if (T >= tn::iso::MAX_TETS) throw tn::Error(std::string(who) + ": num_cells must be below 2^30");
+    if (!tn::iso::in_range(level)) throw tn::Error(std::string(who) + ": level must be finite and below 2^126 in magnitude");
+    if (T && (!cells || (V && !values))) throw tn::Error(std::string(who) + ": cells and values must not be null");
+}
+}  // namespace
+
+int tn_isosurface_count(size_t V, size_t T, const uint32_t *cells, const float *values, float level, const uint8_t *tet_mask,
+                        uint32_t *tri_offsets, uint32_t *ref_offsets, void *stream_) {
+    return guarded([&] {
+        check_isosurface_args("tn_isosurface_count", V, T, cells, values, level);
+        if (!tri_offsets || !ref_offsets) throw tn::Error("tn_isosurface_count: tri_offsets and ref_offsets must not be null");
+        tn::launch_isosurface_count(V, T, cells, values, level, tet_mask, tri_offsets, ref_offsets, (hipStream_t)stream_);
+    });
+}
+
+int tn_isosurface_emit(size_t V, size_t T, const float *xyz, const uint32_t *cells, const float *values, float level,
+                       const uint8_t *tet_mask, const uint32_t *tri_offsets, const uint32_t *ref_offsets, size_t num_triangles,
+                       size_t num_refs, uint32_t *triangles, uint32_t *triangle_tets, uint32_t *edge_vertices, float *edge_t,
+                       float *positions, uint32_t *num_out_vertices, void *stream_) {
+    return guarded([&] {
+        check_isosurface_args("tn_isosurface_emit", V, T, cells, values, level);
+        if (num_triangles > 2 * T || num_refs > 4 * T)
+            throw tn::Error("tn_isosurface_emit: num_triangles / num_refs exceed what num_cells tetrahedra can emit (2 / 4 each)");
+        if (!num_out_vertices || (T && (!tri_offsets || !ref_offsets)) || (T && V && !xyz) ||
+            (num_triangles && (!triangles || !triangle_tets)) || (num_refs && (!edge_vertices || !edge_t || !positions)))
+            throw tn::Error("tn_isosurface_emit: a null pointer beside a non-zero count");
+        tn::launch_isosurface_emit(V, T, xyz, cells, values, level, tet_mask, tri_offsets, ref_offsets, num_triangles, num_refs,
+                                   triangles, triangle_tets, edge_vertices, edge_t, positions, num_out_vertices,
+                                   (hipStream_t)stream_);
     });
 }
 

@@ -86,4 +86,16 @@ void launch_delaunay_check(size_t T, size_t F, const uint32_t *cells, const uint
 void launch_remap_tet_values(size_t V, size_t T_old, const uint32_t *old_cells, const float *old_values, size_t T_new,
                              const uint32_t *new_cells, float *new_values, float *star_max, hipStream_t s);
 
+// The isosurface extraction (tn_isosurface.hip; the rule: tn_isosurface_core.h).  Both enqueue on `s` and return: no read-back; one
+// stream-ordered allocation each.  launch_isosurface_count: tri_offsets / ref_offsets u32 [T + 1] = exclusive sums of the triangles
+// and crossing edges per tetrahedron, the totals last.  launch_isosurface_emit: the caller read those totals back and passes
+// them as num_triangles / num_refs, which bound every store; the vertex outputs have capacity num_refs, *num_out_vertices
+// receives the welded count.  tet_mask u8 [T] may be null.  The entries (tn_api_tracer.hip) have checked the arguments.
+void launch_isosurface_count(size_t V, size_t T, const uint32_t *cells, const float *values, float level, const uint8_t *tet_mask,
+                             uint32_t *tri_offsets, uint32_t *ref_offsets, hipStream_t s);
+void launch_isosurface_emit(size_t V, size_t T, const float *xyz, const uint32_t *cells, const float *values, float level,
+                            const uint8_t *tet_mask, const uint32_t *tri_offsets, const uint32_t *ref_offsets, size_t num_triangles,
+                            size_t num_refs, uint32_t *triangles, uint32_t *triangle_tets, uint32_t *edge_vertices, float *edge_t,
+                            float *positions, uint32_t *num_out_vertices, hipStream_t s);
+
 }  // namespace tn

@@ -1,5 +1,5 @@
-"""The position gradients, the vertex step limiter and (at the end of the file) the Delaunay monitor with its state transfer,
-stated once in plain torch / numpy (any device).
+"""The position gradients, the vertex step limiter, the Delaunay monitor with its state transfer and (at the end of the file) the
+isosurface extraction, stated once in plain torch / numpy (any device).
 
 What csrc/tn_position_grad.hip computes on the device, as the definition the tests hold it to -- the way ray_order.py
 states the binning key.  Nothing here needs a GPU or the library.
@@ -356,3 +356,108 @@ def remap_tet_values_statement(old_cells, new_cells, values, num_vertices: int):
     okn = cn < V
     got = np.where(okn, star[np.where(okn, cn, 0)], 0).astype(np.uint32).max(1) if len(cn) else star[:0]
     return {"values": got.view(np.float32), "star_max": star.view(np.float32)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The isosurface extraction (csrc/tn_isosurface_core.h, csrc/tn_isosurface.hip), stated in numpy: marching
+# tetrahedra on the mesh itself.  The positions are float32 + - * / on float32 arrays -- numpy rounds every operation once and
+# fuses nothing, which is the arithmetic of the element functions -- and the orientation is _vol6 in float64, the expression of
+# tn::guard::tet_orient.  Every array is, bit for bit, what the kernels give.
+
+ISO_VALUE_LIMIT = 2.0 ** 126           # values and level must be below it in magnitude
+ISO_MAX_TETS = 1 << 30
+ISO_EDGE_CORNERS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
+# ISO_TRI_TABLE[code][row] = the three tet edges of triangle `row` for the inside code (bit c = corner c is inside), -1 = none;
+# written for a tetrahedron of non-negative orientation so that (q1-q0) x (q2-q0) points towards values < level
+ISO_TRI_TABLE = (
+    ((-1, -1, -1), (-1, -1, -1)),
+    ((0, 1, 2), (-1, -1, -1)),
+    ((0, 4, 3), (-1, -1, -1)),
+    ((1, 2, 4), (1, 4, 3)),
+    ((1, 3, 5), (-1, -1, -1)),
+    ((0, 3, 5), (0, 5, 2)),
+    ((0, 4, 5), (0, 5, 1)),
+    ((2, 4, 5), (-1, -1, -1)),
+    ((2, 5, 4), (-1, -1, -1)),
+    ((0, 1, 5), (0, 5, 4)),
+    ((0, 2, 5), (0, 5, 3)),
+    ((1, 5, 3), (-1, -1, -1)),
+    ((1, 3, 4), (1, 4, 2)),
+    ((0, 3, 4), (-1, -1, -1)),
+    ((0, 2, 1), (-1, -1, -1)),
+    ((-1, -1, -1), (-1, -1, -1)),
+)
+
+
+def _to_numpy(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def isosurface_statement(xyz, cells, values, level, tet_mask=None):
+    """What tn_isosurface_count + tn_isosurface_emit compute.  xyz float32 [V, 3], cells integer [T, 4] (any tetrahedron soup),
+    values float32 [V], level a float (finite, |level| < 2^126: ValueError otherwise), tet_mask [T] or None (0 = skip): numpy
+    arrays, or torch tensors (copied to the host).
+
+    inside(v) = values[v] >= level.  A tetrahedron is skipped if its mask is 0, an id is >= V, or one of its four values is not
+    finite or is >= 2^126 in magnitude.  Tet edges 0..5 = ISO_EDGE_CORNERS in stored corner order; an edge crosses if its ends
+    differ in `inside`; ISO_TRI_TABLE names the edges of the one or two triangles, corners 1 and 2 swapped where tet_orient is
+    negative.  A surface vertex belongs to a mesh edge (a, b), a < b, and is xyz[a] + t (xyz[b] - xyz[a]) with
+    t = (level - values[a]) / (values[b] - values[a]), all in float32, one rounding per operation.  Vertices ascend by
+    (a << 32 | b), triangles by tetrahedron and then by table row.
+
+    Returns a dict of numpy arrays: "positions" float32 [N, 3], "triangles" int32 [M, 3] (vertex ids), "triangle_tets" int32 [M],
+    "edge_vertices" int32 [N, 2] = (a, b), "edge_t" float32 [N]; "tri_offsets" / "ref_offsets" uint32 [T + 1] (exclusive sums of
+    the triangles / crossing edges per tetrahedron) and the ints "num_triangles" = M, "num_refs" (edge references before welding)."""
+    xyz = np.ascontiguousarray(_to_numpy(xyz), np.float32).reshape(-1, 3)
+    values = np.ascontiguousarray(_to_numpy(values), np.float32).reshape(-1)
+    c = _as_index(_to_numpy(cells)).reshape(-1, 4)
+    with np.errstate(over="ignore"):
+        level = np.float32(level)                                             # the entries take a float
+    if not abs(float(level)) < ISO_VALUE_LIMIT:
+        raise ValueError("level must be finite and below 2^126 in magnitude")
+    V, T = len(values), len(c)
+    if T >= ISO_MAX_TETS:
+        raise ValueError("num_cells must be below 2^30")
+    ok = np.ones(T, bool) if tet_mask is None else _to_numpy(tet_mask).reshape(-1) != 0
+    ok = ok & (c < V).all(1)
+    safe = np.where(ok[:, None], c, 0)
+    v = values[safe] if V else np.zeros((T, 4), np.float32)
+    with np.errstate(invalid="ignore"):
+        ok = ok & (np.abs(v) < np.float32(ISO_VALUE_LIMIT)).all(1)
+        code = np.where(ok, ((v >= level) * np.array([1, 2, 4, 8])).sum(1), 0)
+    table = np.asarray(ISO_TRI_TABLE, np.int64)
+    ec = np.asarray(ISO_EDGE_CORNERS, np.int64)
+    ntri = (table[code, :, 0] >= 0).sum(1)
+    cross = (((code[:, None] >> ec[None, :, 0]) ^ (code[:, None] >> ec[None, :, 1])) & 1).astype(bool)       # [T, 6]
+    nref = cross.sum(1)
+    tri_offsets = np.concatenate([[0], np.cumsum(ntri)]).astype(np.uint32)
+    ref_offsets = np.concatenate([[0], np.cumsum(nref)]).astype(np.uint32)
+    # the edge references in slot order: by tetrahedron, then by tet edge
+    tt, ee = np.nonzero(cross)
+    u, w = c[tt, ec[ee, 0]], c[tt, ec[ee, 1]]
+    key = (np.minimum(u, w).astype(np.uint64) << np.uint64(32)) | np.maximum(u, w).astype(np.uint64)
+    ukey, slot_id = np.unique(key, return_inverse=True)
+    slot_id = slot_id.reshape(-1)
+    a, b = (ukey >> np.uint64(32)).astype(np.int64), (ukey & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    va, vb = values[a], values[b]
+    t = (level - va) / (vb - va)
+    positions = xyz[a] + t[:, None] * (xyz[b] - xyz[a])
+    # the triangles
+    M = int(tri_offsets[-1])
+    triangles, triangle_tets = np.zeros((M, 3), np.int64), np.zeros(M, np.int64)
+    rank = np.cumsum(cross, 1) - cross                                        # position of edge e among the crossing edges
+    emitting = np.nonzero(ntri > 0)[0]
+    negative = np.zeros(T, bool)
+    negative[emitting] = _vol6(xyz.astype(np.float64)[c[emitting]]) < 0
+    for row in (0, 1):
+        tets = np.nonzero(ntri > row)[0]
+        edges = table[code[tets], row]                                        # [n, 3]
+        edges = np.where(negative[tets, None], edges[:, [0, 2, 1]], edges)
+        slots = ref_offsets[tets].astype(np.int64)[:, None] + rank[tets[:, None], edges]
+        index = tri_offsets[tets].astype(np.int64) + row
+        triangles[index] = slot_id[slots]
+        triangle_tets[index] = tets
+    return {"positions": positions.astype(np.float32), "triangles": triangles.astype(np.int32),
+            "triangle_tets": triangle_tets.astype(np.int32),
+            "edge_vertices": np.stack([a, b], 1).astype(np.uint32).view(np.int32).reshape(-1, 2), "edge_t": t.astype(np.float32),
+            "tri_offsets": tri_offsets, "ref_offsets": ref_offsets, "num_triangles": M, "num_refs": int(ref_offsets[-1])}

@@ -521,3 +521,30 @@ def load_reference_checkpoint(model, state_dict, prefix: str = ""):
             dst.copy_(src)
         model.tetrahedra_field.copy_(field)
     return model
+
+
+def extract_mesh(model, level, path=None):
+    """The density isosurface of a TetrahedraNerf as a coloured triangle mesh (render.extract_mesh on the model's own buffers:
+    `tetrahedra_vertices`, `tetrahedra_cells`, `tetrahedra_field` and its modules' weights).  Where the
+    model has the `tetrahedra_occupancy` buffer AND `config.occupancy_threshold`, the tetrahedra an evaluation render culls are
+    masked out of the surface.  level: the density of the surface.  path: also written there as a binary PLY
+    (tetrahedra_io.save_mesh_ply, colours as uint8).  The colours are the head's answer to a viewer looking at the surface along
+    minus its normal, without the appearance-embedding term.  Blocking (two small read-backs; the file).  Returns
+    render.extract_mesh's dict."""
+    from . import render, tetrahedra_io
+
+    ok, why = fused_config_supported(model.config)
+    if not ok:
+        raise RuntimeError(f"extract_mesh needs the architecture of the fused kernels ({why})")
+    occupancy = getattr(model, "tetrahedra_occupancy", None)
+    threshold = getattr(model.config, "occupancy_threshold", None)
+    if occupancy is None or threshold is None:
+        occupancy = threshold = None
+    field = model.tetrahedra_field
+    mesh = render.extract_mesh(model.tetrahedra_vertices.detach().to(field.device), model.tetrahedra_cells.to(field.device).reshape(-1, 4),
+                               field, ModelMLP(model), level, occupancy=None if occupancy is None else occupancy.detach(),
+                               occupancy_threshold=threshold)
+    if path is not None:
+        tetrahedra_io.save_mesh_ply(path, mesh["positions"], mesh["triangles"],
+                                    (mesh["colors"].clamp(0, 1) * 255.0).round().to(torch.uint8))
+    return mesh

@@ -459,6 +459,56 @@ def occupancy_from_field(cells: torch.Tensor, field: torch.Tensor, mlp, mode: st
     return sigma.view(T, 5).max(dim=1).values
 
 
+def vertex_normals(positions: torch.Tensor, triangles: torch.Tensor) -> torch.Tensor:
+    """f32 [N, 3]: the area-weighted normal of every mesh vertex -- the sum of (p1-p0) x (p2-p0) over its triangles, normalised;
+    (0, 0, 1) where that sum is zero or not finite (a vertex of zero-area triangles only).  Plain torch."""
+    p, t = positions, triangles.long()
+    n = torch.linalg.cross(p[t[:, 1]] - p[t[:, 0]], p[t[:, 2]] - p[t[:, 0]])
+    total = torch.zeros_like(p).index_add_(0, t.reshape(-1), n.repeat_interleave(3, 0))
+    length = total.norm(dim=-1, keepdim=True)
+    up = torch.tensor([0.0, 0.0, 1.0], dtype=p.dtype, device=p.device)
+    return torch.where((length > 0) & torch.isfinite(length), total / length.clamp_min(1e-30), up)
+
+
+def extract_mesh(xyz: torch.Tensor, cells: torch.Tensor, field: torch.Tensor, mlp, level: float,
+                 occupancy: Optional[torch.Tensor] = None, occupancy_threshold: Optional[float] = None, colors: bool = True,
+                 mode: str = "fp32") -> Dict[str, torch.Tensor]:
+    """The density isosurface of a trained field as a triangle mesh, everything on the device:
+    the density AT every vertex from the density-only fused forward on the [64, V] field as stored (cpp.mlp_forward(dirs=None));
+    the level set { density = level } of its piecewise-linear interpolant by cpp.isosurface; with `occupancy` f32 [T] and
+    `occupancy_threshold` (both or neither) the tetrahedra an evaluation render would cull (cull_mask_statement) are masked out.
+    colors: per-vertex colours from the gathering forward (cpp.mlp_forward_gather) at the mesh vertices -- vertex_indices
+    (a, b, a, a), barycentrics (t, 0, 0), one sample per ray -- looking AT the surface: dirs = minus the vertex normal.
+    xyz f32 [V, 3], cells i32 [T, 4], mlp: a TetraMLP or an adapter (mlp_weights).  Runs under no_grad: nothing here has a gradient.
+    NOT the level set of the network: inside a tetrahedron the density is an MLP of linearly interpolated features, the mesh
+    interpolates the vertex densities linearly.  Open where the surface reaches the hull or a masked tetrahedron.
+    Returns cpp.isosurface's dict plus "densities" f32 [V], "directions" f32 [N, 3] and "colors" f32 [N, 3] in [0, 1] (the last two
+    None with colors=False).  Blocks on the two read-backs of cpp.isosurface."""
+    from . import tetranerf_cpp_extension as cpp
+
+    if (occupancy is None) != (occupancy_threshold is None):
+        raise ValueError("extract_mesh: occupancy and occupancy_threshold come together (both or neither)")
+    with torch.no_grad():
+        w = [x.detach() for x in mlp_weights(mlp)]
+        densities = cpp.mlp_forward(field.detach(), None, w, 1, mode=mode)
+        mask = None
+        if occupancy is not None and float(occupancy_threshold) > 0:
+            mask = (~(occupancy.detach() < float(occupancy_threshold))).to(torch.uint8)
+        out = cpp.isosurface(xyz.detach(), cells, densities, level, mask)
+        out["densities"], out["directions"], out["colors"] = densities, None, None
+        N = out["positions"].shape[0]
+        if colors:
+            dirs = -vertex_normals(out["positions"], out["triangles"])
+            rgb = torch.zeros((0, 3), dtype=torch.float32, device=field.device)
+            if N:
+                ev = out["edge_vertices"]
+                vi = torch.stack([ev[:, 0], ev[:, 1], ev[:, 0], ev[:, 0]], 1).contiguous()
+                bc = torch.stack([out["edge_t"], torch.zeros_like(out["edge_t"]), torch.zeros_like(out["edge_t"])], 1).contiguous()
+                rgb = cpp.mlp_forward_gather(vi, bc, field.detach(), dirs.contiguous(), w, 1, mode=mode)[1]
+            out["directions"], out["colors"] = dirs, rgb
+    return out
+
+
 def render_reference(tracer, interpolate_values, field: torch.Tensor, mlp: TetraMLP, origins: torch.Tensor,
                      directions: torch.Tensor, num_samples: int = 256, max_ray_triangles: int = 512,
                      far_plane: float = 1000.0, num_fine_samples: int = 0, biased: bool = False,

@@ -280,6 +280,19 @@ class TetrahedraTracer:
             self.load_tetrahedra(xyz, cells, refittable=self._refittable)
             return {"cells": cells, "tet_values": carried, "num_tetrahedra": cells.size(0)}
 
+    supports_isosurface = True
+    ISOSURFACE_GRID_LANES = 1024 * 256       # lanes of the extraction's kernels at their grid cap (tn_isosurface.hip: ISO_BLOCKS * BT)
+
+    def isosurface(self, values, level, tet_mask=None, xyz=None):
+        """The level set { values = level } of a per-vertex scalar on the LOADED cells, as a triangle mesh: `isosurface` (below)
+        on the tracer's own tables.  values f32 [V]; tet_mask uint8 / bool [T] or None; xyz (None: the loaded vertices) f32 [V, 3],
+        any positions of the loaded mesh's vertices.  Blocks on two small read-backs.  The tracer is not touched."""
+        if xyz is None:
+            xyz = self.tetrahedra_vertices
+            _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
+        self._check_loaded_vertices(xyz, "xyz")
+        return isosurface(xyz.detach(), self.tetrahedra_cells.reshape(-1, 4), values, level, tet_mask)
+
     supports_compact_rows = True
     supports_bin_rays = True
 
@@ -869,22 +882,25 @@ def mlp_forward(feats_fm, dirs, weights, samples_per_ray, mode="fp32"):
     dirs f32 [n // samples_per_ray, 3], weights: 12 contiguous fp32 CUDA tensors in nn.Linear layout
     (w1,b1,w2,b2,w3,b3,wd,bd,wh,bh,wr,br).  mode: "fp32" (exact fp32 MFMA chain), "bf16x3" (bf16 MFMA on 3-way
     split operands; opt-in) or "bf16" (one bf16 MFMA per product, fp32 accumulation; opt-in, NOT at the 1e-5 parity bar of the
-    other two: render.mlp_forward_bf16_statement states it).  Returns sigma [n], rgb [n,3]."""
+    other two: render.mlp_forward_bf16_statement states it).  Returns sigma [n], rgb [n,3].
+    dirs=None: density only (mlp_base + density head; the entry's rgb == NULL) -> sigma [n].  The field itself, [64, V] as stored,
+    is such a buffer: its columns are the features AT the vertices."""
     _check_input(feats_fm, "feats")
-    _check_input(dirs, "dirs")
     _check(feats_fm.dtype == torch.float32 and feats_fm.dim() == 2 and feats_fm.size(0) == 64, "feats must be f32 [64, n]")
     n = feats_fm.size(1)
     S = int(samples_per_ray)
     _check(S > 0 and n % S == 0, "n must be a multiple of samples_per_ray")
-    _check(dirs.dtype == torch.float32 and tuple(dirs.shape) == (n // S, 3), "dirs must be f32 [n/samples_per_ray, 3]")
+    if dirs is not None:
+        _check_input(dirs, "dirs")
+        _check(dirs.dtype == torch.float32 and tuple(dirs.shape) == (n // S, 3), "dirs must be f32 [n/samples_per_ray, 3]")
     m = fused_mlp(weights)
     dev = feats_fm.device
     sigma = _empty((n,), dtype=torch.float32, device=dev)
-    rgb = _empty((n, 3), dtype=torch.float32, device=dev)
+    rgb = None if dirs is None else _empty((n, 3), dtype=torch.float32, device=dev)
     with _on(dev):
         _lib.check(_lib.load().tn_mlp_forward(m.handle, n, S, _ptr(feats_fm), _ptr(dirs), _mode(mode), _ptr(sigma), _ptr(rgb),
                                               _stream(dev)))
-    return sigma, rgb
+    return sigma if dirs is None else (sigma, rgb)
 
 
 def _ray_bias(ray_head_bias, rays, dev):
@@ -1040,6 +1056,54 @@ def remap_tet_values(old_cells, new_cells, values, num_vertices, return_star_max
             _lib.check(_lib.load().tn_remap_tet_values(V, old_cells.size(0), _ptr(old_cells), _ptr(values), new_cells.size(0),
                                                        _ptr(new_cells), _ptr(out), _ptr(star), _stream(dev)))
     return (out, star) if return_star_max else out
+
+
+def isosurface(xyz, cells, values, level, tet_mask=None):
+    """Marching tetrahedra on the mesh itself (no reference counterpart; tn_isosurface_count + tn_isosurface_emit; statement:
+    geometry.isosurface_statement, bit for bit; the rule: DESIGN.md section 4.17): the level set { values = level } of the
+    piecewise-linear interpolant of a per-vertex scalar, welded, consistently oriented -- (q1-q0) x (q2-q0) points towards
+    values < level -- and in a deterministic order.  xyz f32 [V, 3], cells i32 [T, 4] (any tetrahedron soup; a row with an id
+    outside [0, V) is skipped), values f32 [V], tet_mask uint8 / bool [T] or None (0 = skip the tetrahedron), all on one device;
+    level: finite, below 2^126 in magnitude.  A tetrahedron with a non-finite value is skipped; a value equal to `level` counts as
+    inside, and the zero-area triangles that makes are kept.
+    Returns {"positions": f32 [N, 3], "triangles": i32 [M, 3] (rows of positions), "triangle_tets": i32 [M] (the source
+    tetrahedron), "edge_vertices": i32 [N, 2] = the mesh edge (a, b), a < b, each vertex lies on, "edge_t": f32 [N] with
+    positions = xyz[a] + edge_t (xyz[b] - xyz[a]), "num_triangles": M, "num_refs": the edge references before welding,
+    "tri_offsets" / "ref_offsets": i32 [T + 1], the triangles / edge references in front of every tetrahedron: the triangles of
+    tetrahedron t are rows tri_offsets[t] .. tri_offsets[t + 1]}.
+    BLOCKS on two small read-backs: the two totals between the entries (they size the outputs), and the welded vertex count."""
+    for x, name in ((xyz, "xyz"), (cells, "cells"), (values, "values")):
+        _check_input(x, name)
+    dev = values.device
+    _check(values.dtype == torch.float32 and values.dim() == 1, "values must be f32 [V]")
+    V = values.numel()
+    _check(xyz.dtype == torch.float32 and tuple(xyz.shape) == (V, 3) and xyz.device == dev, "xyz must be f32 [V, 3] on the device of values")
+    _check(cells.dtype == torch.int32 and cells.dim() == 2 and cells.size(1) == 4 and cells.device == dev,
+           "cells must be int32 [num_cells, 4] on the device of values")
+    T = cells.size(0)
+    if tet_mask is not None:
+        _check_input(tet_mask, "tet_mask")
+        _check(tet_mask.dtype in (torch.uint8, torch.bool) and tet_mask.numel() == T and tet_mask.device == dev,
+               "tet_mask must be uint8 or bool [num_cells] on the device of values")
+    lib, level = _lib.load(), float(level)
+    with torch.no_grad(), _on(dev):
+        offsets = _empty((2, T + 1), dtype=torch.int32, device=dev)
+        _lib.check(lib.tn_isosurface_count(V, T, _ptr(cells), _ptr(values), level, _ptr(tet_mask), _ptr(offsets[0]), _ptr(offsets[1]),
+                                           _stream(dev)))
+        num_triangles, num_refs = offsets[:, T].tolist()                       # read-back 1
+        triangles = _empty((num_triangles, 3), dtype=torch.int32, device=dev)
+        triangle_tets = _empty((num_triangles,), dtype=torch.int32, device=dev)
+        edge_vertices = _empty((num_refs, 2), dtype=torch.int32, device=dev)
+        edge_t = _empty((num_refs,), dtype=torch.float32, device=dev)
+        positions = _empty((num_refs, 3), dtype=torch.float32, device=dev)
+        count = _empty((1,), dtype=torch.int32, device=dev)
+        _lib.check(lib.tn_isosurface_emit(V, T, _ptr(xyz), _ptr(cells), _ptr(values), level, _ptr(tet_mask), _ptr(offsets[0]),
+                                          _ptr(offsets[1]), num_triangles, num_refs, _ptr(triangles), _ptr(triangle_tets),
+                                          _ptr(edge_vertices), _ptr(edge_t), _ptr(positions), _ptr(count), _stream(dev)))
+        N = int(count.item())                                                  # read-back 2
+    return {"positions": positions[:N], "triangles": triangles, "triangle_tets": triangle_tets, "edge_vertices": edge_vertices[:N],
+            "edge_t": edge_t[:N], "num_triangles": num_triangles, "num_refs": num_refs, "tri_offsets": offsets[0],
+            "ref_offsets": offsets[1]}
 
 
 _CULL_SCRATCH = {}   # device -> i32 scratch of cull_samples (tile counts), allocated once and grown on demand
