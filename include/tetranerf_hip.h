@@ -185,6 +185,45 @@ int tn_isosurface_emit(size_t num_vertices, size_t num_cells, const float *xyz, 
                        size_t num_triangles, size_t num_refs, uint32_t *triangles, uint32_t *triangle_tets,
                        uint32_t *edge_vertices, float *edge_t, float *positions, uint32_t *num_out_vertices, void *stream);
 
+/* Isosurface refinement (no reference counterpart: the reference never meshes its field).  The mesh of tn_isosurface_emit is the
+ * level set of the LINEAR interpolant of the vertex values; where the values are a network's density, which is not linear along a
+ * mesh edge, these four steps move every welded vertex along its own edge (a, b) onto a crossing of the density the CALLER
+ * evaluates between them.  The topology is not touched: same triangles, same welding, same order (csrc/tn_isosurface_refine.hip,
+ * the rule once in csrc/tn_isosurface_core.h; every output is bit-equal to
+ * geometry.isosurface_refine_statement on the same densities).
+ *   N = num_surface_vertices; edge_vertices u32 [N,2] = tn_isosurface_emit's (8-byte aligned); brackets f32 [N,4] =
+ *   (t_lo, t_hi, s_lo, s_hi) (16-byte aligned); frozen u8 [N]: 0, 1 = frozen, 2 = an id >= num_vertices.
+ * tn_isosurface_refine_begin:    brackets = (0, 1, values[a], values[b]), frozen = 0; an edge whose values are not finite, are
+ *   >= 2^126 in magnitude or lie on one side of `level` starts frozen; an id >= num_vertices gives (0, 1, 0, 0) and frozen = 2.
+ * tn_isosurface_refine_points:   for round `round` (0..7) the 7 N candidates as the inputs of tn_mlp_forward_gather:
+ *   vertex_indices u32 [N,7,4] = (a, b, a, a) (16-byte aligned), barycentric f32 [N,7,3] = (t_j, 0, 0),
+ *   t_j = t_lo + (j / 8) (t_hi - t_lo), j = 1..7, in fp32 with one rounding per operation: t_lo <= t_1 <= ... <= t_7 <= t_hi.
+ *   An edge with frozen = 2 asks for vertex 0.  The caller then evaluates densities f32 [N,7] there, e.g. by
+ *   tn_mlp_forward_gather(n = 7 N, samples_per_ray = 1, dirs = NULL, rgb = NULL) in any of its modes.
+ * tn_isosurface_refine_select:   in place; with (t_0, s_0) = (t_lo, s_lo) and (t_8, s_8) = (t_hi, s_hi) the new bracket is
+ *   (t_j, t_j+1, s_j, s_j+1) for the FIRST j in 0..7 whose ends differ in inside(s) = s >= level: of several crossings the one
+ *   nearest a.  If one of the seven densities is not finite or is >= 2^126 in magnitude the edge is frozen: frozen = 1, and its
+ *   bracket stays as it is in this and every later round.
+ * tn_isosurface_refine_vertices: edge_t f32 [N], positions f32 [N,3] of the brackets as they stand:
+ *   q = (level - s_lo) / (s_hi - s_lo), t = t_lo + q (t_hi - t_lo) put back into [t_lo, t_hi] (t = q (t_hi - t_lo) where
+ *   t_lo == 0), p = xyz[a] + t (xyz[b] - xyz[a]).  Straight after _begin these are tn_isosurface_emit's edge_t and positions, bit
+ *   for bit.  An id >= num_vertices gives t = 0, p = 0, as tn_isosurface_emit writes it.
+ * A refinement of R <= 8 rounds is begin, R x (points, the caller's densities, select), vertices.  None needs a tracer; each is
+ * one kernel on `stream`, a lane per element, one writer per element, no atomics, no allocation, nothing read back.
+ * num_surface_vertices == 0 is a valid call without a launch.  Errors (nothing is touched): a null or misaligned pointer beside
+ * a non-zero count; level not finite or >= 2^126 in magnitude; round >= 8; num_vertices >= 2^32 - 1; num_surface_vertices above
+ * what 2^30 tetrahedra emit; tn_isosurface_refine_points with num_vertices == 0. */
+int tn_isosurface_refine_begin(size_t num_vertices, size_t num_surface_vertices, const uint32_t *edge_vertices,
+                               const float *values, float level, float *brackets, uint8_t *frozen, void *stream);
+int tn_isosurface_refine_points(size_t num_vertices, size_t num_surface_vertices, uint32_t round, const uint32_t *edge_vertices,
+                                const float *brackets, const uint8_t *frozen, uint32_t *vertex_indices, float *barycentric,
+                                void *stream);
+int tn_isosurface_refine_select(size_t num_surface_vertices, uint32_t round, float level, const float *densities,
+                                float *brackets, uint8_t *frozen, void *stream);
+int tn_isosurface_refine_vertices(size_t num_vertices, size_t num_surface_vertices, const float *xyz,
+                                  const uint32_t *edge_vertices, const float *brackets, float level, float *edge_t,
+                                  float *positions, void *stream);
+
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);
 

@@ -36,7 +36,8 @@ SYMBOLS = (
     "tn_tet_quality", "tn_limit_vertex_step",      # the vertex step limiter: the reference has no counterpart (it never moves vertices)
     "tn_delaunay_check", "tn_remap_tet_values",    # the Delaunay monitor and the per-tetrahedron state transfer of a re-triangulation
     "tn_isosurface_count", "tn_isosurface_emit",   # marching tetrahedra on the field's own mesh: the reference never meshes its field
-    "tn_radam_step_field", "tn_radam_step",        # the optimiser step (registration.py:37-45: RAdam on the field and the MLP)
+    "tn_isosurface_refine_begin", "tn_isosurface_refine_points", "tn_isosurface_refine_select", "tn_isosurface_refine_vertices",
+    "tn_radam_step_field", "tn_radam_step",       # the optimiser step (registration.py:37-45: RAdam on the field and the MLP)
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -74,6 +75,10 @@ def load():
     lib.tn_remap_tet_values.argtypes = [sz, sz, vp, vp, sz, vp, vp, vp, vp]
     lib.tn_isosurface_count.argtypes = [sz, sz, vp, vp, C.c_float, vp, vp, vp, vp]
     lib.tn_isosurface_emit.argtypes = [sz, sz, vp, vp, vp, C.c_float, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.tn_isosurface_refine_begin.argtypes = [sz, sz, vp, vp, C.c_float, vp, vp, vp]
+    lib.tn_isosurface_refine_points.argtypes = [sz, sz, u32, vp, vp, vp, vp, vp, vp]
+    lib.tn_isosurface_refine_select.argtypes = [sz, u32, C.c_float, vp, vp, vp, vp]
+    lib.tn_isosurface_refine_vertices.argtypes = [sz, sz, vp, vp, vp, C.c_float, vp, vp, vp]
     lib.tn_refit_table_bytes.restype = sz
     lib.tn_refit_table_bytes.argtypes = [vp]
     lib.tn_num_faces.restype = sz

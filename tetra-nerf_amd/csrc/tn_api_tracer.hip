@@ -692,6 +692,80 @@ int tn_isosurface_emit(size_t V, size_t T, const float *xyz, const uint32_t *cel
     });
 }
 
+namespace {
+// the checks the four refinement entries share (nothing is touched when one fails)
+void check_refine_args(const char *who, size_t V, size_t N, float level, uint32_t round) {
+    const std::string w(who);
+    if (V >= 0xFFFFFFFFull) throw tn::Error(w + ": too many vertices (uint32 ids)");
+    if (N > 4 * (tn::iso::MAX_TETS - 1)) throw tn::Error(w + ": more surface vertices than 2^30 tetrahedra can emit");
+    if (!tn::iso::in_range(level)) throw tn::Error(w + ": level must be finite and below 2^126 in magnitude");
+    if (round >= tn::iso::REFINE_MAX_ROUNDS) throw tn::Error(w + ": round must be below 8 (at most 8 rounds of refinement)");
+}
+void check_refine_pointer(const char *who, const void *p, size_t alignment, const char *name) {
+    if (!p) throw tn::Error(std::string(who) + ": " + name + " must not be null");
+    if ((uintptr_t)p & (alignment - 1))
+        throw tn::Error(std::string(who) + ": " + name + " must be " + std::to_string(alignment) + "-byte aligned");
+}
+}  // namespace
+
+int tn_isosurface_refine_begin(size_t V, size_t N, const uint32_t *edge_vertices, const float *values, float level,
+                               float *brackets, uint8_t *frozen, void *stream_) {
+    return guarded([&] {
+        const char *who = "tn_isosurface_refine_begin";
+        check_refine_args(who, V, N, level, 0);
+        if (N == 0) return;
+        check_refine_pointer(who, edge_vertices, 8, "edge_vertices");
+        check_refine_pointer(who, brackets, 16, "brackets");
+        check_refine_pointer(who, frozen, 1, "frozen");
+        if (V && !values) throw tn::Error("tn_isosurface_refine_begin: values must not be null");
+        tn::launch_isosurface_refine_begin(V, N, edge_vertices, values, level, brackets, frozen, (hipStream_t)stream_);
+    });
+}
+
+int tn_isosurface_refine_points(size_t V, size_t N, uint32_t round, const uint32_t *edge_vertices, const float *brackets,
+                                const uint8_t *frozen, uint32_t *vertex_indices, float *barycentric, void *stream_) {
+    return guarded([&] {
+        const char *who = "tn_isosurface_refine_points";
+        check_refine_args(who, V, N, 0.f, round);
+        if (N == 0) return;
+        if (V == 0) throw tn::Error("tn_isosurface_refine_points: surface vertices without mesh vertices (the candidates name vertex 0)");
+        check_refine_pointer(who, edge_vertices, 8, "edge_vertices");
+        check_refine_pointer(who, brackets, 16, "brackets");
+        check_refine_pointer(who, frozen, 1, "frozen");
+        check_refine_pointer(who, vertex_indices, 16, "vertex_indices");
+        check_refine_pointer(who, barycentric, 4, "barycentric");
+        tn::launch_isosurface_refine_points(N, edge_vertices, brackets, frozen, vertex_indices, barycentric, (hipStream_t)stream_);
+    });
+}
+
+int tn_isosurface_refine_select(size_t N, uint32_t round, float level, const float *densities, float *brackets, uint8_t *frozen,
+                                void *stream_) {
+    return guarded([&] {
+        const char *who = "tn_isosurface_refine_select";
+        check_refine_args(who, 0, N, level, round);
+        if (N == 0) return;
+        check_refine_pointer(who, densities, 4, "densities");
+        check_refine_pointer(who, brackets, 16, "brackets");
+        check_refine_pointer(who, frozen, 1, "frozen");
+        tn::launch_isosurface_refine_select(N, level, densities, brackets, frozen, (hipStream_t)stream_);
+    });
+}
+
+int tn_isosurface_refine_vertices(size_t V, size_t N, const float *xyz, const uint32_t *edge_vertices, const float *brackets,
+                                  float level, float *edge_t, float *positions, void *stream_) {
+    return guarded([&] {
+        const char *who = "tn_isosurface_refine_vertices";
+        check_refine_args(who, V, N, level, 0);
+        if (N == 0) return;
+        check_refine_pointer(who, edge_vertices, 8, "edge_vertices");
+        check_refine_pointer(who, brackets, 16, "brackets");
+        check_refine_pointer(who, edge_t, 4, "edge_t");
+        check_refine_pointer(who, positions, 4, "positions");
+        if (V && !xyz) throw tn::Error("tn_isosurface_refine_vertices: xyz must not be null");
+        tn::launch_isosurface_refine_vertices(V, N, xyz, edge_vertices, brackets, level, edge_t, positions, (hipStream_t)stream_);
+    });
+}
+
 size_t tn_num_faces(tn_tracer_t tracer) { return tracer && tracer->mesh.loaded ? tracer->mesh.view.F : 0; }
 
 int tn_get_faces(tn_tracer_t tracer, uint32_t *faces_host, uint32_t *face_tets_host) {

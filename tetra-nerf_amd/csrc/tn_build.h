@@ -98,4 +98,17 @@ void launch_isosurface_emit(size_t V, size_t T, const float *xyz, const uint32_t
                             size_t num_refs, uint32_t *triangles, uint32_t *triangle_tets, uint32_t *edge_vertices, float *edge_t,
                             float *positions, uint32_t *num_out_vertices, hipStream_t s);
 
+// The refinement of the extracted vertices (tn_isosurface_refine.hip; the rule: tn_isosurface_core.h).  N welded vertices;
+// edge_vertices u32 [N, 2] (8-byte aligned), brackets f32 [N, 4] (16-byte aligned), flags u8 [N], vertex_indices u32 [7 N, 4]
+// (16-byte aligned), barycentric f32 [7 N, 3], densities f32 [7 N].  Each enqueues one kernel on `s` (none for N == 0), allocates
+// nothing and reads nothing back.  The entries (tn_api_tracer.hip) have checked the arguments.
+void launch_isosurface_refine_begin(size_t V, size_t N, const uint32_t *edge_vertices, const float *values, float level,
+                                    float *brackets, uint8_t *flags, hipStream_t s);
+void launch_isosurface_refine_points(size_t N, const uint32_t *edge_vertices, const float *brackets, const uint8_t *flags,
+                                     uint32_t *vertex_indices, float *barycentric, hipStream_t s);
+void launch_isosurface_refine_select(size_t N, float level, const float *densities, float *brackets, uint8_t *flags,
+                                     hipStream_t s);
+void launch_isosurface_refine_vertices(size_t V, size_t N, const float *xyz, const uint32_t *edge_vertices, const float *brackets,
+                                       float level, float *edge_t, float *positions, hipStream_t s);
+
 }  // namespace tn

@@ -461,3 +461,108 @@ def isosurface_statement(xyz, cells, values, level, tet_mask=None):
             "triangle_tets": triangle_tets.astype(np.int32),
             "edge_vertices": np.stack([a, b], 1).astype(np.uint32).view(np.int32).reshape(-1, 2), "edge_t": t.astype(np.float32),
             "tri_offsets": tri_offsets, "ref_offsets": ref_offsets, "num_triangles": M, "num_refs": int(ref_offsets[-1])}
+
+
+# The refinement of the surface vertices (csrc/tn_isosurface_core.h: refine_begin / refine_candidate / refine_select /
+# refine_vertex; csrc/tn_isosurface_refine.hip), stated in numpy with the same float32 operations.
+
+ISO_REFINE_CANDIDATES = 7
+ISO_REFINE_MAX_ROUNDS = 8
+ISO_REFINE_FROZEN, ISO_REFINE_BAD_IDS = 1, 2
+
+
+def isosurface_refine_candidates(t_lo, t_hi):
+    """The 7 candidates of every bracket, float32 [N, 7]: t_j = t_lo + (j / 8) * (t_hi - t_lo), j = 1..7, one rounding per
+    operation; t_lo <= t_1 <= ... <= t_7 <= t_hi for 0 <= t_lo <= t_hi <= 1 (the proof: tn_isosurface_core.h)."""
+    t_lo, t_hi = np.asarray(t_lo, np.float32).reshape(-1, 1), np.asarray(t_hi, np.float32).reshape(-1, 1)
+    j = (np.arange(1, ISO_REFINE_CANDIDATES + 1, dtype=np.float32) * np.float32(0.125))[None]
+    return (t_lo + j * (t_hi - t_lo)).astype(np.float32)
+
+
+def isosurface_refine_select(bracket, flags, densities, level):
+    """One round on the brackets float32 [N, 4] = (t_lo, t_hi, s_lo, s_hi) and flags uint8 [N], given the densities float32
+    [N, 7] at isosurface_refine_candidates: returns the new (bracket, flags).  The first interval from t_lo whose ends differ in
+    inside(s) = s >= level; a candidate that is not finite or is >= 2^126 in magnitude freezes its edge; a flagged edge stays."""
+    bracket, flags = np.array(bracket, np.float32).reshape(-1, 4), np.array(flags, np.uint8).reshape(-1)
+    s = np.asarray(densities, np.float32).reshape(-1, ISO_REFINE_CANDIDATES)
+    level = np.float32(level)
+    t = isosurface_refine_candidates(bracket[:, 0], bracket[:, 1])
+    ts = np.concatenate([bracket[:, 0:1], t, bracket[:, 1:2]], 1)                 # [N, 9]
+    ss = np.concatenate([bracket[:, 2:3], s, bracket[:, 3:4]], 1)
+    with np.errstate(invalid="ignore"):
+        bad = ~(np.abs(s) < np.float32(ISO_VALUE_LIMIT)).all(1)
+        inside = ss >= level
+    differ = inside[:, :-1] != inside[:, 1:]                                      # [N, 8]
+    first = differ.argmax(1)
+    live = flags == 0
+    frozen_now = live & (bad | ~differ.any(1))
+    move = live & ~frozen_now
+    rows = np.nonzero(move)[0]
+    bracket[rows] = np.stack([ts[rows, first[rows]], ts[rows, first[rows] + 1], ss[rows, first[rows]], ss[rows, first[rows] + 1]], 1)
+    flags[frozen_now] = ISO_REFINE_FROZEN
+    return bracket, flags
+
+
+def isosurface_refine_vertices(xyz, edge_vertices, bracket, level):
+    """(edge_t float32 [N], positions float32 [N, 3]) of the brackets: q = (level - s_lo) / (s_hi - s_lo),
+    t = t_lo + q (t_hi - t_lo) put back into [t_lo, t_hi] (t = q (t_hi - t_lo) where t_lo == 0: the sign of a zero stays),
+    p = xyz[a] + t (xyz[b] - xyz[a]); an edge with an id >= V gives t = 0, p = 0."""
+    xyz = np.ascontiguousarray(_to_numpy(xyz), np.float32).reshape(-1, 3)
+    ev = _as_index(_to_numpy(edge_vertices)).reshape(-1, 2)
+    br = np.asarray(bracket, np.float32).reshape(-1, 4)
+    level = np.float32(level)
+    ok = (ev < len(xyz)).all(1)
+    a, b = np.where(ok, ev[:, 0], 0), np.where(ok, ev[:, 1], 0)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        q = (level - br[:, 2]) / (br[:, 3] - br[:, 2])
+        m = q * (br[:, 1] - br[:, 0])
+        t = np.where(br[:, 0] == 0, m, br[:, 0] + m)
+        t = np.where(~(t >= br[:, 0]), br[:, 0], np.where(t > br[:, 1], br[:, 1], t)).astype(np.float32)
+        xa, xb = (xyz[a], xyz[b]) if len(xyz) else (np.zeros((len(ev), 3), np.float32),) * 2
+        p = xa + t[:, None] * (xb - xa)
+    t = np.where(ok, t, np.float32(0)).astype(np.float32)
+    return t, np.where(ok[:, None], p, np.float32(0)).astype(np.float32)
+
+
+def isosurface_refine_statement(xyz, edge_vertices, values, level, density_fn, rounds):
+    """What tn_isosurface_refine_begin, `rounds` x (tn_isosurface_refine_points, density_fn, tn_isosurface_refine_select) and
+    tn_isosurface_refine_vertices compute: every welded vertex of isosurface_statement moves along its own mesh edge (a, b) onto a
+    crossing of density_fn, the topology untouched.  xyz float32 [V, 3], edge_vertices integer [N, 2] (a < b, as emitted), values
+    float32 [V], level a float (finite, |level| < 2^126), rounds in 0..8 (ValueError otherwise).
+    density_fn(a_ids int64 [n], b_ids int64 [n], t float32 [n]) -> float32 [n]: the density at xyz[a] + t (xyz[b] - xyz[a]); it is
+    asked for all 7 N candidates of a round at once, in [N, 7] order.  rounds = 0 never calls it and returns
+    isosurface_statement's edge_t and positions bit for bit.
+    NOT covered: a tetrahedron whose four vertex values lie on one side is never visited (thin features between vertices stay
+    missing); the triangles are chords of the surface, so the enclosed volume can shrink; of several crossings on one edge the one
+    nearest a is taken; zero-area triangles are kept.
+    Returns {"edge_t": float32 [N], "positions": float32 [N, 3], "edge_bracket": float32 [N, 4] = (t_lo, t_hi, s_lo, s_hi),
+    "edge_frozen": uint8 [N] (0; 1 = frozen: a density or a value out of range, or values on one side; 2 = an id >= V),
+    "brackets": the list of the rounds + 1 bracket arrays from the start on}."""
+    xyz = np.ascontiguousarray(_to_numpy(xyz), np.float32).reshape(-1, 3)
+    values = np.ascontiguousarray(_to_numpy(values), np.float32).reshape(-1)
+    ev = _as_index(_to_numpy(edge_vertices)).reshape(-1, 2)
+    with np.errstate(over="ignore"):
+        level = np.float32(level)
+    if not abs(float(level)) < ISO_VALUE_LIMIT:
+        raise ValueError("level must be finite and below 2^126 in magnitude")
+    rounds = int(rounds)
+    if not 0 <= rounds <= ISO_REFINE_MAX_ROUNDS:
+        raise ValueError("rounds must be in 0..8")
+    if len(xyz) != len(values):
+        raise ValueError("xyz and values must have one row per vertex")
+    V, N = len(values), len(ev)
+    ok = (ev < V).all(1)
+    a, b = np.where(ok, ev[:, 0], 0), np.where(ok, ev[:, 1], 0)
+    va, vb = (values[a], values[b]) if V else (np.zeros(N, np.float32),) * 2
+    bracket = np.stack([np.zeros(N, np.float32), np.ones(N, np.float32), np.where(ok, va, 0), np.where(ok, vb, 0)], 1).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        fine = (np.abs(va) < np.float32(ISO_VALUE_LIMIT)) & (np.abs(vb) < np.float32(ISO_VALUE_LIMIT)) & ((va >= level) != (vb >= level))
+    flags = np.where(ok, np.where(fine, 0, ISO_REFINE_FROZEN), ISO_REFINE_BAD_IDS).astype(np.uint8)
+    history = [bracket.copy()]
+    for _ in range(rounds):
+        t = isosurface_refine_candidates(bracket[:, 0], bracket[:, 1])
+        s = np.asarray(density_fn(np.repeat(a, ISO_REFINE_CANDIDATES), np.repeat(b, ISO_REFINE_CANDIDATES), t.reshape(-1)), np.float32)
+        bracket, flags = isosurface_refine_select(bracket, flags, s.reshape(N, ISO_REFINE_CANDIDATES), level)
+        history.append(bracket.copy())
+    edge_t, positions = isosurface_refine_vertices(xyz, ev, bracket, level)
+    return {"edge_t": edge_t, "positions": positions, "edge_bracket": bracket, "edge_frozen": flags, "brackets": history}

@@ -523,13 +523,14 @@ def load_reference_checkpoint(model, state_dict, prefix: str = ""):
     return model
 
 
-def extract_mesh(model, level, path=None):
+def extract_mesh(model, level, path=None, refine_rounds=0):
     """The density isosurface of a TetrahedraNerf as a coloured triangle mesh (render.extract_mesh on the model's own buffers:
     `tetrahedra_vertices`, `tetrahedra_cells`, `tetrahedra_field` and its modules' weights).  Where the
     model has the `tetrahedra_occupancy` buffer AND `config.occupancy_threshold`, the tetrahedra an evaluation render culls are
     masked out of the surface.  level: the density of the surface.  path: also written there as a binary PLY
     (tetrahedra_io.save_mesh_ply, colours as uint8).  The colours are the head's answer to a viewer looking at the surface along
-    minus its normal, without the appearance-embedding term.  Blocking (two small read-backs; the file).  Returns
+    minus its normal, without the appearance-embedding term.  refine_rounds (0..8; 0: the linear placement, unchanged): the
+    vertices move along their mesh edges onto the network's own level set first (render.extract_mesh).  Blocking (two small read-backs; the file).  Returns
     render.extract_mesh's dict."""
     from . import render, tetrahedra_io
 
@@ -543,7 +544,7 @@ def extract_mesh(model, level, path=None):
     field = model.tetrahedra_field
     mesh = render.extract_mesh(model.tetrahedra_vertices.detach().to(field.device), model.tetrahedra_cells.to(field.device).reshape(-1, 4),
                                field, ModelMLP(model), level, occupancy=None if occupancy is None else occupancy.detach(),
-                               occupancy_threshold=threshold)
+                               occupancy_threshold=threshold, **({"refine_rounds": refine_rounds} if refine_rounds else {}))
     if path is not None:
         tetrahedra_io.save_mesh_ply(path, mesh["positions"], mesh["triangles"],
                                     (mesh["colors"].clamp(0, 1) * 255.0).round().to(torch.uint8))

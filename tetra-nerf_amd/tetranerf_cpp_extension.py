@@ -283,15 +283,26 @@ class TetrahedraTracer:
     supports_isosurface = True
     ISOSURFACE_GRID_LANES = 1024 * 256       # lanes of the extraction's kernels at their grid cap (tn_isosurface.hip: ISO_BLOCKS * BT)
 
-    def isosurface(self, values, level, tet_mask=None, xyz=None):
+    def isosurface(self, values, level, tet_mask=None, xyz=None, refine=None):
         """The level set { values = level } of a per-vertex scalar on the LOADED cells, as a triangle mesh: `isosurface` (below)
         on the tracer's own tables.  values f32 [V]; tet_mask uint8 / bool [T] or None; xyz (None: the loaded vertices) f32 [V, 3],
-        any positions of the loaded mesh's vertices.  Blocks on two small read-backs.  The tracer is not touched."""
+        any positions of the loaded mesh's vertices.  Blocks on two small read-backs.  The tracer is not touched.
+        refine (None: the extraction alone, nothing else runs): a dict with "rounds" (0..8) and either "field" f32 [64, V] and
+        "weights" (optionally "mode") -- isosurface_refine on the network whose vertex densities `values` are -- or "density_fn",
+        the callback of isosurface_refine_with; the vertices then move along their edges onto that density's level set."""
         if xyz is None:
             xyz = self.tetrahedra_vertices
             _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
         self._check_loaded_vertices(xyz, "xyz")
-        return isosurface(xyz.detach(), self.tetrahedra_cells.reshape(-1, 4), values, level, tet_mask)
+        surface = isosurface(xyz.detach(), self.tetrahedra_cells.reshape(-1, 4), values, level, tet_mask)
+        if refine is None:
+            return surface
+        _check(isinstance(refine, dict) and "rounds" in refine and (("density_fn" in refine) != ("field" in refine and "weights" in refine)),
+               'refine must be a dict with "rounds" and either "density_fn" or "field" and "weights"')
+        if "density_fn" in refine:
+            return isosurface_refine_with(surface, xyz.detach(), values, level, refine["density_fn"], refine["rounds"])
+        return isosurface_refine(surface, xyz.detach(), values, level, refine["field"], refine["weights"], refine["rounds"],
+                                 mode=refine.get("mode", "fp32"))
 
     supports_compact_rows = True
     supports_bin_rays = True
@@ -1104,6 +1115,75 @@ def isosurface(xyz, cells, values, level, tet_mask=None):
     return {"positions": positions[:N], "triangles": triangles, "triangle_tets": triangle_tets, "edge_vertices": edge_vertices[:N],
             "edge_t": edge_t[:N], "num_triangles": num_triangles, "num_refs": num_refs, "tri_offsets": offsets[0],
             "ref_offsets": offsets[1]}
+
+
+ISOSURFACE_REFINE_MAX_ROUNDS = 8     # tn_isosurface_core.h: REFINE_MAX_ROUNDS (8^-8 = one ulp of t = 1)
+ISOSURFACE_REFINE_CANDIDATES = 7     # tn_isosurface_core.h: REFINE_CANDIDATES
+
+
+def isosurface_refine_with(surface, xyz, values, level, density_fn, rounds):
+    """The refinement of `isosurface`'s vertices with the densities of a CALLBACK (no reference counterpart; the four
+    tn_isosurface_refine_* entries; statement: geometry.isosurface_refine_statement, bit for bit on the same densities; the rule:
+    DESIGN.md section 4.17).  surface: isosurface's dict; xyz f32 [V, 3], values f32 [V] as passed to it; rounds in 0..8.
+    density_fn(vertex_indices i32 [7 N, 4], barycentric f32 [7 N, 3]) -> f32 [7 N] on the same device: the density at the 7
+    candidates of every vertex -- the inputs are those of mlp_forward_gather, (a, b, a, a) and (t, 0, 0), vertex-major.  It is
+    called once per round, on the caller's stream; nothing is read back here and the host never waits.
+    Every welded vertex moves along its own mesh edge to the crossing of the density nearest a, bracketed to 8^-rounds of the edge;
+    triangles, welding and order are untouched.  rounds = 0 never calls density_fn and returns isosurface's positions and edge_t
+    bit for bit (in new arrays: the first and the last kernel still run).
+    Returns a new dict: "positions" and "edge_t" replaced, "edge_bracket" f32 [N, 4] = (t_lo, t_hi, s_lo, s_hi) and "edge_frozen"
+    u8 [N] (1: a density out of range froze the edge; 2: an id >= V) added; every other entry is the same object.  NOT covered: tetrahedra whose four vertex values lie on one side are never visited; the triangles are chords of
+    the surface, so the enclosed volume can shrink; of several crossings on one edge the one nearest a is taken; zero-area
+    triangles are kept."""
+    rounds = int(rounds)
+    _check(0 <= rounds <= ISOSURFACE_REFINE_MAX_ROUNDS, "isosurface_refine: rounds must be in 0..8")
+    out = dict(surface)
+    ev = surface["edge_vertices"]
+    for x, name in ((xyz, "xyz"), (values, "values"), (ev, "edge_vertices")):
+        _check_input(x, name)
+    dev = values.device
+    _check(values.dtype == torch.float32 and values.dim() == 1, "values must be f32 [V]")
+    V = values.numel()
+    _check(xyz.dtype == torch.float32 and tuple(xyz.shape) == (V, 3) and xyz.device == dev, "xyz must be f32 [V, 3] on the device of values")
+    _check(ev.dtype == torch.int32 and ev.dim() == 2 and ev.size(1) == 2 and ev.device == dev,
+           "surface['edge_vertices'] must be int32 [N, 2] on the device of values")
+    N, C = ev.size(0), ISOSURFACE_REFINE_CANDIDATES
+    lib, level = _lib.load(), float(level)
+    with torch.no_grad(), _on(dev):
+        bracket = _empty((N, 4), dtype=torch.float32, device=dev)
+        frozen = _empty((N,), dtype=torch.uint8, device=dev)
+        vi = _empty((N * C, 4), dtype=torch.int32, device=dev)
+        bc = _empty((N * C, 3), dtype=torch.float32, device=dev)
+        edge_t = _empty((N,), dtype=torch.float32, device=dev)
+        positions = _empty((N, 3), dtype=torch.float32, device=dev)
+        _lib.check(lib.tn_isosurface_refine_begin(V, N, _ptr(ev), _ptr(values), level, _ptr(bracket), _ptr(frozen), _stream(dev)))
+        for r in range(rounds):
+            _lib.check(lib.tn_isosurface_refine_points(V, N, r, _ptr(ev), _ptr(bracket), _ptr(frozen), _ptr(vi), _ptr(bc), _stream(dev)))
+            s = density_fn(vi, bc) if N else _empty((0,), dtype=torch.float32, device=dev)
+            _check(isinstance(s, torch.Tensor) and s.dtype == torch.float32 and s.numel() == N * C and s.device == dev and s.is_contiguous(),
+                   "isosurface_refine: density_fn must return a contiguous f32 tensor with one value per candidate, on the same device")
+            _lib.check(lib.tn_isosurface_refine_select(N, r, level, _ptr(s), _ptr(bracket), _ptr(frozen), _stream(dev)))
+        _lib.check(lib.tn_isosurface_refine_vertices(V, N, _ptr(xyz), _ptr(ev), _ptr(bracket), level, _ptr(edge_t), _ptr(positions),
+                                                     _stream(dev)))
+    out.update(positions=positions, edge_t=edge_t, edge_bracket=bracket, edge_frozen=frozen)
+    return out
+
+
+def isosurface_refine(surface, xyz, values, level, field, weights, rounds, mode="fp32"):
+    """isosurface_refine_with on the NETWORK's density: every round's 7 N candidates go through the density-only gathering
+    forward (mlp_forward_gather(dirs=None), one sample per ray) on field f32 [64, V] and `weights` in `mode` ("fp32", "bf16x3",
+    "bf16": whatever that forward accepts).  `values` should be that network's density at the vertices in the same mode
+    (mlp_forward(field, None, weights, 1, mode)), as render.extract_mesh passes it.  The mesh `isosurface` gives is the level set of
+    the linear interpolant of the vertex densities; this moves its vertices onto the level set of the network along their edges.
+    What it returns, and what it does not cover: isosurface_refine_with."""
+    def density(vi, bc):
+        return mlp_forward_gather(vi, bc, field, None, weights, 1, mode=mode)
+
+    if int(rounds) > 0:
+        _check_input(field, "field")
+        _check(field.dtype == torch.float32 and field.dim() == 2 and field.size(0) == 64 and field.size(1) == values.numel(),
+               "field must be f32 [64, V], one column per entry of values")
+    return isosurface_refine_with(surface, xyz, values, level, density, rounds)
 
 
 _CULL_SCRATCH = {}   # device -> i32 scratch of cull_samples (tile counts), allocated once and grown on demand
