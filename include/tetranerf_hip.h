@@ -224,6 +224,45 @@ int tn_isosurface_refine_vertices(size_t num_vertices, size_t num_surface_vertic
                                   const uint32_t *edge_vertices, const float *brackets, float level, float *edge_t,
                                   float *positions, void *stream);
 
+/* Tetrahedron split (no reference counterpart: the reference's mesh is its input point cloud for the whole run).  Selected
+ * tetrahedra are split 1 -> 4 at their centroids, which changes the RESOLUTION of the mesh and nothing else: the four outer faces
+ * of a split tetrahedron stay, so the mesh stays conforming without touching a neighbour (csrc/tn_split.hip, the rule once in
+ * csrc/tn_split_core.h; every output is bit-equal to geometry.split_tetrahedra_statement /
+ * geometry.split_vertex_rows_statement).
+ *   xyz f32 [V,3], cells u32 [T,4], select u8 [T] (non-zero = asked), all on the current device.
+ *   Tetrahedron t is ACCEPTED iff it is asked, its four ids are < V, the orientation s of its stored row -- the sign of
+ *   ((p1-p0) x (p2-p0)) . (p3-p0) as tn_tet_quality evaluates it, 0 also for NaN -- is not 0, and each of its four children has
+ *   that orientation s.  Child i is the stored row with slot i replaced by the centroid c = ((p0 + p1) + (p2 + p3)) * 0.25f per
+ *   coordinate, in fp32 with one rounding per operation and no fused multiply-add.  (A child fails where the rounded centroid
+ *   lies on or across a face; the children are compared with the parent's own sign, stored rows being of either sign.)
+ *   With k = the accepted tetrahedra below t and K their total: the new vertex is V + k; child 0 overwrites row t; children 1,
+ *   2, 3 are rows T + 3k, T + 3k + 1, T + 3k + 2; cell_parent[row] = row for a row < T and the parent for an appended row;
+ *   vertex_parents[k] = the parent's row as stored.
+ * tn_split_count: offsets u32 [T+1] = exclusive sums of the accepted flags, K last (reading it back is the caller's one
+ *   synchronisation); counters u32 [4], zeroed by the call: asked, accepted, refused for a flat or inverted parent or child,
+ *   refused for an id >= V.
+ * tn_split_emit: given offsets and num_new = K (a host value): xyz_out f32 [V+num_new,3], cells_out u32 [T+3 num_new,4],
+ *   cell_parent u32 [T+3 num_new], vertex_parents u32 [num_new,4].  Accepted means offsets[t+1] > offsets[t]; select is not read
+ *   again.  Every store is bounded by the num_new passed: a caller who changed the inputs between the two entries gets a wrong
+ *   mesh, never a write outside its buffers.
+ * tn_split_vertex_rows: a per-vertex array grown by the new vertices: out f32 [rows,V+K] = values f32 [rows,V] followed by K
+ *   new columns, new_mode 0: ((x[a] + x[b]) + (x[c] + x[d])) * 0.25f with (a,b,c,d) = vertex_parents[k], the centroid's form;
+ *   new_mode 1: zeros.  A parent id >= V gives 0.  out_vm f32 [V+K,rows] (nullable) is the transposition of out, bit-equal to
+ *   tn_transpose_f32 of it, written in the same pass.  values_vm f32 [V,rows] (nullable) is the caller's transposition of values
+ *   (the vertex-major shadow of the field): where given, the parent columns are read from it as rows and the old part of out_vm
+ *   is a copy of it.  Carries the [64,V] field and both moments of its optimiser.
+ * None needs a tracer.  All launch on `stream` and read nothing back; the only atomics are the four counters (one add per block);
+ * tn_split_count takes its scratch as one stream-ordered allocation.  T == 0 or num_new == 0 gives empties or plain copies.
+ * Errors (nothing is touched): a null pointer beside a non-zero count; num_new > num_cells; num_vertices + num_new >= 2^32 - 1;
+ * num_cells + 3 num_new >= 2^30; rows == 0; an unknown new_mode. */
+int tn_split_count(size_t num_vertices, size_t num_cells, const float *xyz, const uint32_t *cells, const uint8_t *select,
+                   uint32_t *offsets, uint32_t *counters, void *stream);
+int tn_split_emit(size_t num_vertices, size_t num_cells, const float *xyz, const uint32_t *cells, const uint32_t *offsets,
+                  size_t num_new, float *xyz_out, uint32_t *cells_out, uint32_t *cell_parent, uint32_t *vertex_parents,
+                  void *stream);
+int tn_split_vertex_rows(size_t rows, size_t num_vertices, size_t num_new, const float *values, const float *values_vm,
+                         const uint32_t *vertex_parents, uint32_t new_mode, float *out, float *out_vm, void *stream);
+
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);
 

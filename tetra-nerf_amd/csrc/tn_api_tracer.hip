@@ -11,6 +11,7 @@
 #include "tn_devbuf.h"
 #include "tn_isosurface_core.h"
 #include "tn_kernels.h"
+#include "tn_split_core.h"
 
 using tn::check_loaded;
 using tn::check_pow2_M;
@@ -763,6 +764,51 @@ int tn_isosurface_refine_vertices(size_t V, size_t N, const float *xyz, const ui
         check_refine_pointer(who, positions, 4, "positions");
         if (V && !xyz) throw tn::Error("tn_isosurface_refine_vertices: xyz must not be null");
         tn::launch_isosurface_refine_vertices(V, N, xyz, edge_vertices, brackets, level, edge_t, positions, (hipStream_t)stream_);
+    });
+}
+
+namespace {
+// the size checks the split entries share (nothing is touched when one fails); K = the new vertices the call may write
+void check_split_sizes(const char *who, size_t V, size_t T, size_t K) {
+    const std::string w(who);
+    if (K > T) throw tn::Error(w + ": num_new exceeds num_cells (a tetrahedron is split at most once)");
+    if (V >= 0xFFFFFFFFull || V + K >= 0xFFFFFFFFull) throw tn::Error(w + ": too many vertices (uint32 ids)");
+    if (T >= tn::split::MAX_CELLS || T + 3 * K >= tn::split::MAX_CELLS) throw tn::Error(w + ": num_cells + 3 num_new must be below 2^30");
+}
+}  // namespace
+
+int tn_split_count(size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint8_t *select, uint32_t *offsets,
+                   uint32_t *counters, void *stream_) {
+    return guarded([&] {
+        check_split_sizes("tn_split_count", V, T, 0);
+        if (!offsets || !counters || (T && (!cells || !select)) || (T && V && !xyz))
+            throw tn::Error("tn_split_count: a null pointer beside a non-zero count");
+        tn::launch_split_count(V, T, xyz, cells, select, offsets, counters, (hipStream_t)stream_);
+    });
+}
+
+int tn_split_emit(size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint32_t *offsets, size_t num_new,
+                  float *xyz_out, uint32_t *cells_out, uint32_t *cell_parent, uint32_t *vertex_parents, void *stream_) {
+    return guarded([&] {
+        check_split_sizes("tn_split_emit", V, T, num_new);
+        if ((T && (!cells || !offsets || !cells_out || !cell_parent)) || (V && (!xyz || !xyz_out)) ||
+            (num_new && (!xyz_out || !vertex_parents)))
+            throw tn::Error("tn_split_emit: a null pointer beside a non-zero count");
+        tn::launch_split_emit(V, T, xyz, cells, offsets, num_new, xyz_out, cells_out, cell_parent, vertex_parents,
+                              (hipStream_t)stream_);
+    });
+}
+
+int tn_split_vertex_rows(size_t rows, size_t V, size_t K, const float *values, const float *values_vm,
+                         const uint32_t *vertex_parents, uint32_t new_mode, float *out, float *out_vm, void *stream_) {
+    return guarded([&] {
+        if (rows == 0) throw tn::Error("tn_split_vertex_rows: rows must not be 0");
+        if (rows >= 0xFFFFFFFFull) throw tn::Error("tn_split_vertex_rows: too many rows");
+        if (new_mode > tn::split::MODE_ZERO) throw tn::Error("tn_split_vertex_rows: unknown new_mode (0 = mean of the parents, 1 = zeros)");
+        if (V >= 0xFFFFFFFFull || V + K >= 0xFFFFFFFFull) throw tn::Error("tn_split_vertex_rows: too many vertices (uint32 ids)");
+        if ((V && !values) || (K && !vertex_parents) || (V + K && !out))
+            throw tn::Error("tn_split_vertex_rows: a null pointer beside a non-zero count");
+        tn::launch_split_vertex_rows(rows, V, K, values, values_vm, vertex_parents, new_mode, out, out_vm, (hipStream_t)stream_);
     });
 }
 

@@ -111,4 +111,22 @@ void launch_isosurface_refine_select(size_t N, float level, const float *densiti
 void launch_isosurface_refine_vertices(size_t V, size_t N, const float *xyz, const uint32_t *edge_vertices, const float *brackets,
                                        float level, float *edge_t, float *positions, hipStream_t s);
 
+// The tetrahedron split (tn_split.hip; the rule: tn_split_core.h; no reference counterpart: the reference never changes its
+// mesh).  A selected tetrahedron is split 1 -> 4 at its centroid c = ((p0 + p1) + (p2 + p3)) * 0.25f iff its ids are < V, its
+// orientation s (guard::tet_orient) is not 0 and each of its four children has orientation s.  All three enqueue on `s` and
+// return: no read-back.  launch_split_count: offsets u32 [T + 1] = exclusive sums of the accepted flags, the total K last;
+// counters u32 [4] zeroed and then = asked, accepted, refused flat or inverted, refused for an id >= V; one stream-ordered
+// allocation.  launch_split_emit: the caller read K back and passes it as num_new, which bounds every store; xyz_out f32
+// [V + num_new, 3], cells_out u32 [T + 3 num_new, 4], cell_parent u32 [T + 3 num_new], vertex_parents u32 [num_new, 4].
+// launch_split_vertex_rows: out f32 [rows, V + K] = values f32 [rows, V] with K new columns (new_mode 0: the mean4 of the four
+// parent columns, 1: zeros; a parent id >= V gives 0), out_vm f32 [V + K, rows] (nullable) its transposition; values_vm f32
+// [V, rows] (nullable) = the transposition of values, then read in the place of the parent columns.  The entries
+// (tn_api_tracer.hip) have checked the arguments.
+void launch_split_count(size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint8_t *select, uint32_t *offsets,
+                        uint32_t *counters, hipStream_t s);
+void launch_split_emit(size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint32_t *offsets, size_t num_new,
+                       float *xyz_out, uint32_t *cells_out, uint32_t *cell_parent, uint32_t *vertex_parents, hipStream_t s);
+void launch_split_vertex_rows(size_t rows, size_t V, size_t K, const float *values, const float *values_vm,
+                              const uint32_t *vertex_parents, uint32_t new_mode, float *out, float *out_vm, hipStream_t s);
+
 }  // namespace tn

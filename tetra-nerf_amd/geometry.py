@@ -566,3 +566,95 @@ def isosurface_refine_statement(xyz, edge_vertices, values, level, density_fn, r
         history.append(bracket.copy())
     edge_t, positions = isosurface_refine_vertices(xyz, ev, bracket, level)
     return {"edge_t": edge_t, "positions": positions, "edge_bracket": bracket, "edge_frozen": flags, "brackets": history}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The tetrahedron split (csrc/tn_split_core.h, csrc/tn_split.hip), stated in numpy: selected tetrahedra
+# are split 1 -> 4 at their centroids.  The centroid and the new per-vertex values are float32 + and * on float32 arrays, one
+# rounding per operation in the order written; the orientations are _vol6 in float64, the expression of tn::guard::tet_orient.
+# Every array is, bit for bit, what the kernels give.
+
+SPLIT_MAX_CELLS = 1 << 30
+
+
+def _sign64(v):
+    return (v > 0).astype(np.int8) - (v < 0).astype(np.int8)                  # 0 also for NaN
+
+
+def _mean4_f32(a, b, c, d):
+    """((a + b) + (c + d)) * 0.25f on float32 arrays: split::mean4"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return ((a + b) + (c + d)) * np.float32(0.25)
+
+
+def split_tetrahedra_statement(xyz, cells, select):
+    """What tn_split_count + tn_split_emit compute.  xyz float32 [V, 3], cells integer [T, 4] (any tetrahedron soup), select [T]
+    (non-zero = asked): numpy arrays, or torch tensors (copied to the host).
+
+    Tetrahedron t is accepted iff it is asked, its four ids are < V, the orientation s of its stored row (the sign of _vol6 in
+    float64 on the float32 coordinates, 0 also for NaN) is not 0, and each of its four children has that orientation s.  Child i is
+    the stored row with slot i replaced by the centroid c = ((p0 + p1) + (p2 + p3)) * 0.25f per coordinate in float32.  With k =
+    the accepted tetrahedra below t and K their total, the new vertex is V + k, child 0 overwrites row t, children 1, 2, 3 are
+    rows T + 3k, T + 3k + 1, T + 3k + 2.
+
+    Returns a dict of numpy arrays: "vertices" float32 [V + K, 3], "cells" int32 [T + 3K, 4], "cell_parent" int32 [T + 3K] (the
+    row itself below T, the parent for an appended row), "vertex_parents" int32 [K, 4] (the parent's row as stored), "offsets"
+    uint32 [T + 1] (exclusive sums of the accepted flags), "counters" uint32 [4] = asked, accepted, refused for a flat or inverted
+    parent or child, refused for an id >= V; and the int "num_new" = K."""
+    xyz = np.ascontiguousarray(_to_numpy(xyz), np.float32).reshape(-1, 3)
+    c = _as_index(_to_numpy(cells)).reshape(-1, 4)
+    asked = _to_numpy(select).reshape(-1) != 0
+    V, T = len(xyz), len(c)
+    if len(asked) != T:
+        raise ValueError("select must have one entry per row of cells")
+    ids_ok = (c < V).all(1)
+    judged = np.nonzero(asked & ids_ok)[0]
+    p = xyz[c[judged]]                                                        # float32 [n, 4, 3]
+    cen = _mean4_f32(p[:, 0], p[:, 1], p[:, 2], p[:, 3])                      # float32 [n, 3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = _sign64(_vol6(p.astype(np.float64)))
+        fine = s != 0
+        for i in range(4):
+            q = p.copy()
+            q[:, i] = cen
+            fine &= _sign64(_vol6(q.astype(np.float64))) == s
+    accepted = np.zeros(T, bool)
+    accepted[judged] = fine
+    offsets = np.concatenate([[0], np.cumsum(accepted)]).astype(np.uint32)
+    K = int(offsets[-1])
+    if T + 3 * K >= SPLIT_MAX_CELLS or V + K >= 0xFFFFFFFF:
+        raise ValueError("num_cells + 3 num_new must be below 2^30 and num_vertices + num_new below 2^32 - 1")
+    parents = np.nonzero(accepted)[0]
+    new_id = V + np.arange(K, dtype=np.int64)
+    vertices = np.concatenate([xyz, cen[fine]], 0).astype(np.float32)
+    out = np.concatenate([c, np.zeros((3 * K, 4), np.int64)], 0)
+    cell_parent = np.concatenate([np.arange(T, dtype=np.int64), np.repeat(parents, 3)])
+    for i in range(4):
+        child = c[parents].copy()
+        child[:, i] = new_id
+        rows = parents if i == 0 else T + 3 * np.arange(K, dtype=np.int64) + (i - 1)
+        out[rows] = child
+    counters = np.array([asked.sum(), K, (asked & ids_ok).sum() - K, (asked & ~ids_ok).sum()], np.uint32)
+    return {"vertices": vertices, "cells": out.astype(np.uint32).view(np.int32).reshape(-1, 4),
+            "cell_parent": cell_parent.astype(np.int32), "vertex_parents": c[parents].astype(np.uint32).view(np.int32).reshape(-1, 4),
+            "offsets": offsets, "counters": counters, "num_new": K}
+
+
+def split_vertex_rows_statement(values, vertex_parents, new="mean"):
+    """What tn_split_vertex_rows computes.  values float32 [rows, V], vertex_parents integer [K, 4] -> float32 [rows, V + K]: the
+    old columns, then for new vertex k either ((x[a] + x[b]) + (x[c] + x[d])) * 0.25f in float32 with (a, b, c, d) =
+    vertex_parents[k] (new = "mean": the centroid's form, so an affine function of the position is carried exactly up to these
+    three roundings) or 0 (new = "zero").  A row of vertex_parents with an id >= V gives 0."""
+    if new not in ("mean", "zero"):
+        raise ValueError('new must be "mean" or "zero"')
+    values = np.ascontiguousarray(_to_numpy(values), np.float32)
+    if values.ndim != 2 or values.shape[0] == 0:
+        raise ValueError("values must be [rows, V] with rows > 0")
+    vp = _as_index(_to_numpy(vertex_parents)).reshape(-1, 4)
+    rows, V = values.shape
+    fresh = np.zeros((rows, len(vp)), np.float32)
+    ok = (vp < V).all(1)
+    if new == "mean" and ok.any():
+        a, b, c, d = (values[:, vp[ok, j]] for j in range(4))
+        fresh[:, ok] = _mean4_f32(a, b, c, d)
+    return np.concatenate([values, fresh], 1)

@@ -549,3 +549,135 @@ def extract_mesh(model, level, path=None, refine_rounds=0):
         tetrahedra_io.save_mesh_ply(path, mesh["positions"], mesh["triangles"],
                                     (mesh["colors"].clamp(0, 1) * 255.0).round().to(torch.uint8))
     return mesh
+
+
+def _set_tensor(model, name, value, like=None):
+    """`model.<name> = value` under the kind the attribute has: a Parameter stays one (requires_grad as before), a buffer a buffer"""
+    if isinstance(like, torch.nn.Parameter):
+        value = torch.nn.Parameter(value, requires_grad=like.requires_grad)
+    setattr(model, name, value)
+    return value
+
+
+def _grow_moments(optimizer, old, vertex_parents, new_moments, vertex_major):
+    """(exp_avg, exp_avg_sq) of `old` carried to the split mesh, or (None, None) where the optimiser holds none for it.
+    vertex_major: the moments are [V, ...] (the vertex table's) and are carried in plain torch; else [rows, V] (the field's)."""
+    from . import tetranerf_cpp_extension as cpp
+
+    state = optimizer.state.get(old) if optimizer is not None else None
+    if not state or "exp_avg" not in state:
+        return None, None
+    out = []
+    for key in ("exp_avg", "exp_avg_sq"):
+        m = state[key]
+        if not vertex_major:
+            out.append(cpp.split_vertex_rows(m, vertex_parents, new=new_moments))
+            continue
+        fresh = m.new_zeros((vertex_parents.size(0),) + tuple(m.shape[1:]))
+        if new_moments == "mean":
+            a, b, c, d = m[vertex_parents.long()].unbind(1)
+            fresh = ((a + b) + (c + d)) * 0.25
+        out.append(torch.cat([m, fresh], 0))
+    return tuple(out)
+
+
+def densify(model, select=None, *, occupancy_threshold=None, min_width=None, max_new=None, optimizer=None, new_moments="mean",
+            retriangulate=False):
+    """Raise the resolution of a TetrahedraNerf's mesh where asked: the selected tetrahedra are split 1 -> 4 at their centroids
+    (`tracer.split_tetrahedra`), the new vertices take the mean of their four parents' field columns, so
+    the piecewise-linear field -- and with it the next frame and the next loss -- is the one of the unsplit mesh up to rounding.
+    An explicit call, like extract_mesh, not a config switch: get_outputs cannot reach the trainer's optimisers.
+
+    select: bool / uint8 [T] over the model's cells, or None: then the mask is occupancy >= occupancy_threshold (needs the
+    `tetrahedra_occupancy` buffer) and width >= min_width (`tracer.tet_quality()`), whichever are given.  max_new: the mask is cut
+    to the max_new widest tetrahedra (torch.topk).  The policy is the caller's; tetrahedra the rule refuses (flat, or so thin that
+    the fp32 centroid lands on a face) stay as they are.
+    optimizer: the optimiser that holds `tetrahedra_field` (and `tetrahedra_vertices`, where that is optimised): its state moves
+    through optim.grow_parameter -- step kept, the moments of a new vertex the mean of its parents' (new_moments="mean") or 0
+    ("zero").  Without it the caller re-creates its optimiser.
+    retriangulate: afterwards `tracer.retriangulate` gives the grown vertex table Delaunay cells; the field is per vertex and
+    survives, the occupancy goes through remap_tet_values.  This trades the exact preservation for a Delaunay mesh.
+
+    REPLACED under their names, so a state dict keeps its keys: `tetrahedra_vertices`, `tetrahedra_cells`, `tetrahedra_field` (a
+    new nn.Parameter: the old one leaves the field cache, the new one is registered iff the old was, with its vertex-major shadow
+    already installed), `tetrahedra_occupancy` where present, and `config.num_tetrahedra_vertices` / `config.num_tetrahedra_cells`.
+    What `_follow_vertices` remembers of the vertex table is reset.  BLOCKS on the read-back of the number of accepted tetrahedra
+    and on the load.  With nothing accepted nothing is touched.
+    Returns {"counters": int32 [4] on the device (asked, accepted, refused flat or inverted, refused for an id), "num_new",
+    "num_vertices", "num_cells", "retriangulated"}."""
+    from . import optim as tn_optim
+    from . import tetranerf_cpp_extension as cpp
+
+    if new_moments not in ("mean", "zero"):
+        raise ValueError('densify: new_moments must be "mean" or "zero"')
+    tracer = model.get_tetrahedra_tracer()
+    if not getattr(tracer, "supports_split", False):
+        raise RuntimeError("densify needs a tracer with split_tetrahedra (tetranerf_cpp_extension.TetrahedraTracer)")
+    field, vertices = model.tetrahedra_field, model.tetrahedra_vertices
+    occupancy = getattr(model, "tetrahedra_occupancy", None)
+    T = tracer.tetrahedra_cells.numel() // 4
+    with torch.no_grad():
+        width = tracer.tet_quality()["width"] if (select is None and min_width is not None) or max_new is not None else None
+        if select is None:
+            if occupancy_threshold is None and min_width is None:
+                raise ValueError("densify: give `select`, or occupancy_threshold and / or min_width")
+            mask = torch.ones(T, dtype=torch.bool, device=tracer.device)
+            if occupancy_threshold is not None:
+                if occupancy is None:
+                    raise ValueError("densify: occupancy_threshold needs the model's tetrahedra_occupancy buffer")
+                mask &= occupancy.detach() >= float(occupancy_threshold)
+            if min_width is not None:
+                mask &= width >= float(min_width)
+        else:
+            mask = select.to(tracer.device).reshape(-1) != 0
+            if mask.numel() != T:
+                raise ValueError("densify: select must have one entry per tetrahedron")
+        if max_new is not None and T:
+            keep = torch.topk(torch.where(mask, width, width.new_full((), -1.0)), min(int(max_new), T)).indices
+            cut = torch.zeros_like(mask)
+            cut[keep] = True
+            mask &= cut
+        registered = cpp.field_is_registered(field)
+        field_vm = cpp.field_vertex_major(field) if registered else None        # (before the load below forgets it)
+        out = tracer.split_tetrahedra(mask.contiguous(), tet_values=() if occupancy is None else (occupancy.detach(),))
+        K = int(out["num_new"])
+        result = {"counters": out["counters"], "num_new": K, "num_vertices": vertices.shape[0] + K, "num_cells": T + 3 * K,
+                  "retriangulated": False}
+        if K == 0:
+            return result
+        parents = out["vertex_parents"]
+        new_field, new_vm = cpp.split_vertex_rows(field.detach(), parents, "mean", values_vm=field_vm, want_vertex_major=True)
+        field_moments = _grow_moments(optimizer, field, parents, new_moments, False)
+        vertex_moments = _grow_moments(optimizer, vertices, parents, new_moments, True)
+        new_vertices = _set_tensor(model, "tetrahedra_vertices", out["vertices"], vertices)
+        tracer.tetrahedra_vertices = new_vertices                              # the same storage the tracer borrows
+        model.tetrahedra_cells = out["cells"]
+        if occupancy is not None:
+            model.tetrahedra_occupancy = out["tet_values"][0]
+        new_field = _set_tensor(model, "tetrahedra_field", new_field, field)
+        cpp.unregister_field(field)
+        if registered:
+            cpp.register_field(new_field)
+            cpp.install_field_shadow(new_field, new_vm)
+        if optimizer is not None:
+            if field_moments[0] is not None or any(p is field for g in optimizer.param_groups for p in g["params"]):
+                tn_optim.grow_parameter(optimizer, field, new_field, *field_moments)
+            if any(p is vertices for g in optimizer.param_groups for p in g["params"]):
+                tn_optim.grow_parameter(optimizer, vertices, new_vertices, *vertex_moments)
+        if retriangulate:
+            occ = getattr(model, "tetrahedra_occupancy", None)
+            again = tracer.retriangulate(tracer.tetrahedra_vertices.detach(), () if occ is None else (occ.detach(),))
+            tracer.tetrahedra_vertices = new_vertices
+            model.tetrahedra_cells = again["cells"]
+            if occ is not None:
+                model.tetrahedra_occupancy = again["tet_values"][0]
+            result.update(num_cells=int(again["num_tetrahedra"]), retriangulated=True)
+        cfg = getattr(model, "config", None)
+        if hasattr(cfg, "num_tetrahedra_vertices"):
+            cfg.num_tetrahedra_vertices = result["num_vertices"]
+        if hasattr(cfg, "num_tetrahedra_cells"):
+            cfg.num_tetrahedra_cells = result["num_cells"]
+        if getattr(tracer, "_tn_vertex_snapshot", None) is not None:
+            tracer._tn_vertex_snapshot = new_vertices.detach().clone()
+        tracer._tn_vertex_key = (new_vertices._version, new_vertices.data_ptr())
+        return result

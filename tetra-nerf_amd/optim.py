@@ -246,3 +246,35 @@ class FusedRAdam(torch.optim.Optimizer):
                     torch.autograd.graph.increment_version(m)
                     torch.autograd.graph.increment_version(v)
         return loss
+
+
+def grow_parameter(optimizer, old, new, exp_avg=None, exp_avg_sq=None):
+    """Replace the parameter `old` of `optimizer` by `new` -- the same quantity on a mesh with more vertices (cpp.split_vertex_rows)
+    -- in its parameter group, and move its state: `step` is kept (the bias corrections and the rectification go on where they
+    were), `exp_avg` / `exp_avg_sq` are the tensors given (the old moments carried by split_vertex_rows) or zeros of the new
+    shape.  A parameter that has not been stepped yet has no state, and gets none.  Works on torch.optim.RAdam and on FusedRAdam,
+    whose state layouts are the same: the state_dict of either still loads into the other.  Raises ValueError if `old` is not a
+    parameter of the optimiser, or a moment has not the new parameter's shape, dtype and device.  Returns `new`."""
+    group = next((g for g in optimizer.param_groups if any(p is old for p in g["params"])), None)
+    if group is None:
+        raise ValueError("grow_parameter: `old` is not a parameter of this optimiser")
+    if any(p is new for g in optimizer.param_groups for p in g["params"]):
+        raise ValueError("grow_parameter: `new` is already a parameter of this optimiser")
+    for name, m in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if m is not None and (m.shape != new.shape or m.dtype != new.dtype or m.device != new.device):
+            raise ValueError(f"grow_parameter: {name} must have the shape, dtype and device of the new parameter")
+    if isinstance(optimizer, FusedRAdam):
+        _check_param(new)
+    state = optimizer.state.pop(old, None)
+    group["params"] = [new if p is old else p for p in group["params"]]
+    if state:
+        moved = dict(state)                                                    # `step` and whatever else the class keeps
+        with torch.no_grad():
+            for name, m in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+                if name in state:
+                    moved[name] = torch.zeros_like(new, memory_format=torch.preserve_format) if m is None else m.detach().contiguous()
+        optimizer.state[new] = moved
+    shadows = getattr(optimizer, "_shadows", None)
+    if shadows is not None:
+        shadows.pop(id(old), None)                                             # the [V, 64] buffer of the old field goes with it
+    return new

@@ -304,6 +304,44 @@ class TetrahedraTracer:
         return isosurface_refine(surface, xyz.detach(), values, level, refine["field"], refine["weights"], refine["rounds"],
                                  mode=refine.get("mode", "fp32"))
 
+    supports_split = True
+    SPLIT_GRID_LANES = 1024 * 256            # lanes of the split's kernels at their grid cap (tn_split.hip: SPLIT_BLOCKS * BT)
+
+    def split_tetrahedra(self, select, vertex_rows=(), tet_values=()):
+        """Split the selected tetrahedra of the LOADED mesh 1 -> 4 at their centroids and load the result: `split_tetrahedra`
+        (below) on the tracer's own tables, every array of `vertex_rows` (f32 [rows, V]: the field, its optimiser's moments)
+        carried by split_vertex_rows(new="mean"), every array of `tet_values` ([T, ...] on the loaded cells: the occupancy)
+        carried as values[cell_parent] -- a child lies inside its parent, so this is exact --, then load_tetrahedra(new vertices,
+        new cells, refittable=what this tracer was loaded with).  select: uint8 / bool [T].
+        Returns split_tetrahedra's dict with "vertex_rows" and "tet_values" (the carried arrays in the order given) added; the
+        tracer borrows "vertices" and "cells" from now on.  With K == 0 (nothing asked, or everything refused) the tracer is not
+        touched and the inputs come back as they are.  BLOCKS on the one read-back of K, and on what load_tetrahedra reads back.
+        The field cache is invalidated, as by every load."""
+        with torch.no_grad():
+            xyz, cells = self.tetrahedra_vertices, self.tetrahedra_cells
+            _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
+            xyz, cells = xyz.detach().reshape(-1, 3), cells.reshape(-1, 4)
+            V, T = xyz.size(0), cells.size(0)
+            vertex_rows, tet_values = tuple(vertex_rows), tuple(tet_values)
+            for v in vertex_rows:
+                _check_input(v, "vertex_rows")
+                _check(v.dtype == torch.float32 and v.dim() == 2 and v.size(1) == V and v.device == self._device,
+                       "vertex_rows must be float32 [rows, V] arrays over the loaded vertices, on the tracer's device")
+            for t in tet_values:
+                _check_input(t, "tet_values")
+                _check(t.dim() >= 1 and t.size(0) == T and t.device == self._device,
+                       "tet_values must be [T, ...] arrays over the loaded cells, on the tracer's device")
+            out = split_tetrahedra(xyz, cells, select)
+            if out["num_new"] == 0:
+                out.update(vertices=self.tetrahedra_vertices, cells=self.tetrahedra_cells, vertex_rows=list(vertex_rows),
+                           tet_values=list(tet_values))
+                return out
+            out["vertex_rows"] = [split_vertex_rows(v.detach(), out["vertex_parents"]) for v in vertex_rows]
+            parent = out["cell_parent"].long()
+            out["tet_values"] = [t.detach()[parent] for t in tet_values]
+            self.load_tetrahedra(out["vertices"], out["cells"], refittable=self._refittable)
+            return out
+
     supports_compact_rows = True
     supports_bin_rays = True
 
@@ -1184,6 +1222,80 @@ def isosurface_refine(surface, xyz, values, level, field, weights, rounds, mode=
         _check(field.dtype == torch.float32 and field.dim() == 2 and field.size(0) == 64 and field.size(1) == values.numel(),
                "field must be f32 [64, V], one column per entry of values")
     return isosurface_refine_with(surface, xyz, values, level, density, rounds)
+
+
+def split_tetrahedra(xyz, cells, select):
+    """Split the selected tetrahedra 1 -> 4 at their centroids (no reference counterpart: the reference's mesh is its input point
+    cloud for the whole run; tn_split_count + tn_split_emit; statement: geometry.split_tetrahedra_statement, bit for bit; the
+    rule: DESIGN.md section 4.18).  xyz f32 [V, 3], cells i32 [T, 4] (any tetrahedron soup), select uint8 / bool [T] (non-zero =
+    asked), all on one device.  A tetrahedron is ACCEPTED iff it is asked, its ids are in [0, V), its stored row is not flat
+    (orientation 0, also for NaN) and each of its four children -- the row with one slot replaced by the fp32 centroid
+    ((p0 + p1) + (p2 + p3)) * 0.25f -- has the parent's orientation.  The four outer faces stay: the mesh stays conforming.
+    Returns {"vertices": f32 [V + K, 3] (the old rows, then the centroids), "cells": i32 [T + 3K, 4] (child 0 in the parent's row,
+    children 1..3 appended, three rows per accepted tetrahedron in ascending order), "cell_parent": i32 [T + 3K] (the row itself
+    below T, the parent for an appended row: values[cell_parent] carries a per-tetrahedron array), "vertex_parents": i32 [K, 4]
+    (the parent's row as stored: split_vertex_rows carries a per-vertex array), "counters": i32 [4] on the device -- asked,
+    accepted, refused for a flat or inverted parent or child, refused for an id outside [0, V) --, "num_new": K}.
+    BLOCKS on one small read-back: K between the two entries (it sizes the outputs).  With K == 0 the second entry is not called:
+    "vertices" and "cells" are the inputs themselves."""
+    for x, name in ((xyz, "xyz"), (cells, "cells"), (select, "select")):
+        _check_input(x, name)
+    dev = xyz.device
+    _check(xyz.dtype == torch.float32 and xyz.dim() == 2 and xyz.size(1) == 3, "xyz must be f32 [V, 3]")
+    _check(cells.dtype == torch.int32 and cells.dim() == 2 and cells.size(1) == 4 and cells.device == dev,
+           "cells must be int32 [num_cells, 4] on the device of xyz")
+    V, T = xyz.size(0), cells.size(0)
+    _check(select.dtype in (torch.uint8, torch.bool) and select.numel() == T and select.device == dev,
+           "select must be uint8 or bool [num_cells] on the device of xyz")
+    lib = _lib.load()
+    with torch.no_grad(), _on(dev):
+        offsets = _empty((T + 1,), dtype=torch.int32, device=dev)
+        counters = _empty((4,), dtype=torch.int32, device=dev)
+        _lib.check(lib.tn_split_count(V, T, _ptr(xyz), _ptr(cells), _ptr(select), _ptr(offsets), _ptr(counters), _stream(dev)))
+        K = int(offsets[T].item())                                             # the read-back
+        if K == 0:
+            return {"vertices": xyz, "cells": cells, "cell_parent": torch.arange(T, dtype=torch.int32, device=dev),
+                    "vertex_parents": _empty((0, 4), dtype=torch.int32, device=dev), "counters": counters, "num_new": 0}
+        vertices = _empty((V + K, 3), dtype=torch.float32, device=dev)
+        new_cells = _empty((T + 3 * K, 4), dtype=torch.int32, device=dev)
+        cell_parent = _empty((T + 3 * K,), dtype=torch.int32, device=dev)
+        vertex_parents = _empty((K, 4), dtype=torch.int32, device=dev)
+        _lib.check(lib.tn_split_emit(V, T, _ptr(xyz), _ptr(cells), _ptr(offsets), K, _ptr(vertices), _ptr(new_cells), _ptr(cell_parent),
+                                     _ptr(vertex_parents), _stream(dev)))
+    return {"vertices": vertices, "cells": new_cells, "cell_parent": cell_parent, "vertex_parents": vertex_parents,
+            "counters": counters, "num_new": K}
+
+
+SPLIT_NEW_MODES = {"mean": 0, "zero": 1}     # tn_split_core.h: MODE_MEAN, MODE_ZERO
+
+
+def split_vertex_rows(values, vertex_parents, new="mean", values_vm=None, want_vertex_major=False):
+    """A per-vertex array grown by the vertices of a split (tn_split_vertex_rows; statement: geometry.split_vertex_rows_statement,
+    bit for bit).  values f32 [rows, V] (the [64, V] field, a moment of its optimiser), vertex_parents i32 [K, 4]
+    (split_tetrahedra's) -> f32 [rows, V + K]: the old columns, then per new vertex ((x[a] + x[b]) + (x[c] + x[d])) * 0.25f of its
+    four parents' columns (new="mean": the centroid's own form, so the piecewise-linear field stays the function it was, up to
+    rounding) or 0 (new="zero").  values_vm f32 [V, rows] (optional): the caller's vertex-major shadow of `values`
+    (field_vertex_major); the parent columns are then read from it as whole rows.  want_vertex_major: also return the shadow
+    f32 [V + K, rows] of the result, written in the same pass and bit-equal to its transposition: (out, out_vm).
+    Caller's stream, no host synchronisation."""
+    _check(new in SPLIT_NEW_MODES, 'split_vertex_rows: new must be "mean" or "zero"')
+    for x, name in ((values, "values"), (vertex_parents, "vertex_parents")):
+        _check_input(x, name)
+    dev = values.device
+    _check(values.dtype == torch.float32 and values.dim() == 2 and values.size(0) > 0, "values must be f32 [rows, V] with rows > 0")
+    _check(vertex_parents.dtype == torch.int32 and vertex_parents.dim() == 2 and vertex_parents.size(1) == 4 and vertex_parents.device == dev,
+           "vertex_parents must be int32 [K, 4] on the device of values")
+    rows, V, K = values.size(0), values.size(1), vertex_parents.size(0)
+    if values_vm is not None:
+        _check_input(values_vm, "values_vm")
+        _check(values_vm.dtype == torch.float32 and tuple(values_vm.shape) == (V, rows) and values_vm.device == dev,
+               "values_vm must be f32 [V, rows] on the device of values")
+    with torch.no_grad(), _on(dev):
+        out = _empty((rows, V + K), dtype=torch.float32, device=dev)
+        out_vm = _empty((V + K, rows), dtype=torch.float32, device=dev) if want_vertex_major else None
+        _lib.check(_lib.load().tn_split_vertex_rows(rows, V, K, _ptr(values), _ptr(values_vm), _ptr(vertex_parents), SPLIT_NEW_MODES[new],
+                                                    _ptr(out), _ptr(out_vm), _stream(dev)))
+    return (out, out_vm) if want_vertex_major else out
 
 
 _CULL_SCRATCH = {}   # device -> i32 scratch of cull_samples (tile counts), allocated once and grown on demand
