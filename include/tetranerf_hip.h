@@ -670,6 +670,28 @@ int tn_mlp_forward_gather_indexed(tn_mlp_t mlp, size_t n_max, uint32_t samples_p
                                   const float *field_vm, const float *dirs, int mode, float *sigma, float *rgb,
                                   const float *ray_head_bias, const uint32_t *count, void *stream);
 
+/* ---- per-tetrahedron training statistics (addition; no reference counterpart: the reference never changes its mesh) ---------
+ * tn_tet_stats_accumulate: stats i64 [num_cells, 3], ACCUMULATED in place (the caller zeroes it): per tetrahedron the number of
+ * samples matched to it, the sum of their composite weights and the sum of weight x per-ray value (the caller's error of the
+ * rendered pixel), the last two in fixed point with 32 fractional bits.  What a densification policy selects by.
+ * Row q < min(num_rows, *count) (count nullable: all rows) holds samples_per_ray = S samples: cells u32 [num_rows, S] (the matched
+ * tetrahedron, 0xFFFFFFFF = unmatched), sigma f32 [num_rows, S], edges f32 [num_rows, S + 1], and belongs to ray
+ * r = ray_index ? ray_index[q] : q of ray_value f32 [rays] (nullable: every value 1; ray_index[q] must be a valid index of it).
+ *   w   = the weight tn_composite(..., rgb = NULL, out_weights) writes for the same sigma and edges, bit for bit (the kernel calls
+ *         the same device function; NaN -> 0 included)
+ *   w^  = w >= 0 ? min(w, 1) : 0;     v^ = v >= 0 ? min(v, 256) : 0 with v = ray_value[r]   (NaN, negative, -0 -> 0)
+ *   for every sample with cell t < num_cells (others contribute nothing):
+ *     stats[t, 0] += 1;   stats[t, 1] += rint(w^ * 2^32);   stats[t, 2] += rint(fl32(w^ * v^) * 2^32)     (rint: half to even)
+ * Rows from *count on are NOT read: they are the padded duplicates of the sync-free training form (tn_compact_hits) and would
+ * be counted twice.  Integer sums: the result does not depend on the order of the samples or of the atomics, is identical from
+ * run to run and equals the numpy statement (render.tet_stats_statement) byte for byte.  A term is at most 2^32 (weight) or 2^40
+ * (error): a tetrahedron holds 2^31 resp. 2^23 = 8,388,608 accepted samples before a sum could pass 2^63; nothing saturates --
+ * reset before that.  One wavefront per row, the row's weights in LDS, three 64-bit integer atomic adds per run of equal cells.
+ * samples_per_ray: 1 .. 8192, more is refused (not truncated).  Caller's stream, no host synchronisation. */
+int tn_tet_stats_accumulate(uint32_t num_cells, size_t num_rows, uint32_t samples_per_ray, const uint32_t *cells, const float *sigma,
+                            const float *edges, const float *ray_value, const uint32_t *ray_index, const uint32_t *count,
+                            int64_t *stats, void *stream);
+
 /* ---- occupancy-guided coarse sampler (addition; model.py:98-99,256-265 declares the occupancy field and leaves it unused) -----
  * One wavefront per HITTING ray; the trace rows (num_visited u32 [R], visited u32 [R,M], hit_distances f32 [R,M,2]) are read in
  * place through ray_index u32 [r]; count as for tn_sample_coarse (rows from *count on are left unwritten).

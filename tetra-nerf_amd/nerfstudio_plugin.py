@@ -261,6 +261,8 @@ def _monitor_delaunay(tracer, model, above, keep_snapshot):
         if hasattr(getattr(model, "config", None), "num_tetrahedra_cells"):
             model.config.num_tetrahedra_cells = int(out["num_tetrahedra"])
         model._tn_retriangulations = getattr(model, "_tn_retriangulations", 0) + 1
+        if getattr(model, "_tn_tet_stats", None) is not None:     # statistics of cells that no longer exist
+            model_tet_stats(model, reset=True, num_cells=int(out["num_tetrahedra"]))
     v = tracer.tetrahedra_vertices
     if keep_snapshot:
         tracer._tn_vertex_snapshot = v.detach().clone()
@@ -403,8 +405,19 @@ def fused_get_outputs(model, ray_bundle) -> Dict[str, torch.Tensor]:
                     kw["occupancy_sampler"] = True
         if _wants_aux_outputs(model.config):
             kw["aux_outputs"] = True
-        return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
-                               ray_head_bias=hb, **kw)
+        if not getattr(model.config, "densify_stats", False):
+            return rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
+                                   ray_head_bias=hb, **kw)
+        # opt-in (an absent field: off): per-tetrahedron training statistics for densify(stats=True).  The batch's sample
+        # placement is kept on the model until fused_get_loss_dict knows the error of every ray -- a plain attribute, nothing of it
+        # enters the state dict.  Batches of the occupancy-guided sampler are not counted (render_train refuses the combination:
+        # their edges are live-length coordinates); the unculled refresh batches are.
+        kw["tet_stats"] = not kw.get("occupancy_sampler", False)
+        res = rd.render_train(o, d, gradient_scaling=bool(getattr(model.config, "use_gradient_scaling", False)), background=bg,
+                              ray_head_bias=hb, **kw)
+        pending = res.pop("tet_stats_pending", None)
+        object.__setattr__(model, "_tn_tet_stats_pending", None if pending is None else (rd, pending))
+        return res
     kw = {}
     if _wants_aux_outputs(model.config):
         kw["aux_outputs"] = True
@@ -438,10 +451,56 @@ def fused_get_loss_dict(model, outputs, batch, metrics_dict=None):
     if ref is None:
         raise RuntimeError("no reference get_loss_dict to wrap: install() / make_fused_model_class() set it")
     loss_dict = ref(model, outputs, batch, metrics_dict)
+    held = getattr(model, "_tn_tet_stats_pending", None)
+    if held is not None:
+        # config.densify_stats: the squared error of every rendered pixel, spread over the tetrahedra its ray's weights fell into
+        object.__setattr__(model, "_tn_tet_stats_pending", None)
+        rd, pending = held
+        with torch.no_grad():
+            rgb = outputs["rgb"]
+            image = batch["image"].to(rgb.device)
+            ray_value = ((rgb - image) ** 2).sum(-1).detach().reshape(-1)
+            rd.accumulate_tet_stats(model_tet_stats(model), pending, ray_value)
     mult = getattr(model.config, "distortion_loss_mult", None)
     if mult is not None and "distortion" in outputs:
         loss_dict["distortion_loss"] = float(mult) * outputs["distortion"].mean()
     return loss_dict
+
+
+def model_tet_stats(model, reset=False, num_cells=None):
+    """The model's per-tetrahedron training statistics `model._tn_tet_stats`, i64 [T, 3] (cpp.tet_stats_new), created lazily and
+    sized to the tracer's current cells (or num_cells); an array of another size (the mesh changed under it) or reset=True
+    gives fresh zeros.  A plain attribute: no state-dict key."""
+    from . import tetranerf_cpp_extension as cpp
+
+    tracer = model.get_tetrahedra_tracer()
+    T = tracer.tetrahedra_cells.numel() // 4 if num_cells is None else int(num_cells)
+    stats = getattr(model, "_tn_tet_stats", None)
+    if reset or stats is None or stats.size(0) != T or stats.device != tracer.tetrahedra_cells.device:
+        stats = cpp.tet_stats_new(T, tracer.tetrahedra_cells.device)
+        object.__setattr__(model, "_tn_tet_stats", stats)
+    return stats
+
+
+def densify_selection(stats, mask=None, score="error", min_hits=None, max_new=None):
+    """The statistics' part of densify's selection, in plain torch (any device): bool [T].
+        eligible = (hits >= min_hits) & mask            (min_hits None: 1 -- a tetrahedron no sample fell into has no evidence)
+        max_new: of the eligible, the max_new with the highest render.tet_stats_scores(stats, score); equal scores go to the
+        LOWER id (a stable descending sort keeps ids ascending among equals)."""
+    from . import render
+
+    hits = stats[:, 0]
+    eligible = hits >= int(1 if min_hits is None else min_hits)
+    if mask is not None:
+        eligible = eligible & mask.to(eligible.device)
+    if max_new is None or int(max_new) >= eligible.numel():
+        return eligible
+    scores = render.tet_stats_scores(stats, score)
+    scores = torch.where(eligible, scores, scores.new_full((), -1.0))       # (scores are >= 0)
+    keep = torch.sort(scores, descending=True, stable=True).indices[:max(0, int(max_new))]
+    cut = torch.zeros_like(eligible)
+    cut[keep] = True
+    return eligible & cut
 
 
 def install(model_cls=None):
@@ -581,8 +640,8 @@ def _grow_moments(optimizer, old, vertex_parents, new_moments, vertex_major):
     return tuple(out)
 
 
-def densify(model, select=None, *, occupancy_threshold=None, min_width=None, max_new=None, optimizer=None, new_moments="mean",
-            retriangulate=False):
+def densify(model, select=None, *, stats=None, score="error", min_hits=None, occupancy_threshold=None, min_width=None, max_new=None,
+            optimizer=None, new_moments="mean", retriangulate=False):
     """Raise the resolution of a TetrahedraNerf's mesh where asked: the selected tetrahedra are split 1 -> 4 at their centroids
     (`tracer.split_tetrahedra`), the new vertices take the mean of their four parents' field columns, so
     the piecewise-linear field -- and with it the next frame and the next loss -- is the one of the unsplit mesh up to rounding.
@@ -592,6 +651,13 @@ def densify(model, select=None, *, occupancy_threshold=None, min_width=None, max
     `tetrahedra_occupancy` buffer) and width >= min_width (`tracer.tet_quality()`), whichever are given.  max_new: the mask is cut
     to the max_new widest tetrahedra (torch.topk).  The policy is the caller's; tetrahedra the rule refuses (flat, or so thin that
     the fp32 centroid lands on a face) stay as they are.
+    stats: per-tetrahedron training statistics i64 [T, 3] (cpp.tet_stats_accumulate), or True: the model's own, gathered under
+    `config.densify_stats`.  With select=None the mask is hits >= min_hits (None: 1) and the occupancy and width conditions
+    where given; max_new then cuts to the highest SCORES -- render.tet_stats_scores(stats, score), score one of "error",
+    "mean_error", "weight", "hits" -- with ties going to the lower id (a stable sort; densify_selection).  With `select` given
+    the mask is the caller's and only the max_new cut uses the scores.  Selection is plain torch: it runs once per hundreds of
+    iterations.  After a split or a re-triangulation the model's statistics (where it has any) are replaced by zeros of the new
+    size -- children start from zero -- and the result has "stats_reset": True.
     optimizer: the optimiser that holds `tetrahedra_field` (and `tetrahedra_vertices`, where that is optimised): its state moves
     through optim.grow_parameter -- step kept, the moments of a new vertex the mean of its parents' (new_moments="mean") or 0
     ("zero").  Without it the caller re-creates its optimiser.
@@ -616,11 +682,20 @@ def densify(model, select=None, *, occupancy_threshold=None, min_width=None, max
     field, vertices = model.tetrahedra_field, model.tetrahedra_vertices
     occupancy = getattr(model, "tetrahedra_occupancy", None)
     T = tracer.tetrahedra_cells.numel() // 4
+    if stats is True:
+        stats = getattr(model, "_tn_tet_stats", None)
+        if stats is None:
+            raise ValueError("densify: stats=True needs the model's own statistics (config.densify_stats and at least one training step)")
+    if stats is not None and (stats.dim() != 2 or tuple(stats.shape) != (T, 3) or stats.dtype != torch.int64):
+        raise ValueError("densify: stats must be i64 [T, 3] over the model's current cells")
+    if stats is None and min_hits is not None:
+        raise ValueError("densify: min_hits needs stats")
+    has_stats = stats is not None or getattr(model, "_tn_tet_stats", None) is not None
     with torch.no_grad():
-        width = tracer.tet_quality()["width"] if (select is None and min_width is not None) or max_new is not None else None
+        width = tracer.tet_quality()["width"] if (select is None and min_width is not None) or (max_new is not None and stats is None) else None
         if select is None:
-            if occupancy_threshold is None and min_width is None:
-                raise ValueError("densify: give `select`, or occupancy_threshold and / or min_width")
+            if occupancy_threshold is None and min_width is None and stats is None:
+                raise ValueError("densify: give `select`, stats, or occupancy_threshold and / or min_width")
             mask = torch.ones(T, dtype=torch.bool, device=tracer.device)
             if occupancy_threshold is not None:
                 if occupancy is None:
@@ -632,7 +707,9 @@ def densify(model, select=None, *, occupancy_threshold=None, min_width=None, max
             mask = select.to(tracer.device).reshape(-1) != 0
             if mask.numel() != T:
                 raise ValueError("densify: select must have one entry per tetrahedron")
-        if max_new is not None and T:
+        if stats is not None:
+            mask = densify_selection(stats.to(tracer.device), mask, score, min_hits if select is None else 0, max_new)
+        elif max_new is not None and T:
             keep = torch.topk(torch.where(mask, width, width.new_full((), -1.0)), min(int(max_new), T)).indices
             cut = torch.zeros_like(mask)
             cut[keep] = True
@@ -643,6 +720,8 @@ def densify(model, select=None, *, occupancy_threshold=None, min_width=None, max
         K = int(out["num_new"])
         result = {"counters": out["counters"], "num_new": K, "num_vertices": vertices.shape[0] + K, "num_cells": T + 3 * K,
                   "retriangulated": False}
+        if has_stats:
+            result["stats_reset"] = False
         if K == 0:
             return result
         parents = out["vertex_parents"]
@@ -680,4 +759,7 @@ def densify(model, select=None, *, occupancy_threshold=None, min_width=None, max
         if getattr(tracer, "_tn_vertex_snapshot", None) is not None:
             tracer._tn_vertex_snapshot = new_vertices.detach().clone()
         tracer._tn_vertex_key = (new_vertices._version, new_vertices.data_ptr())
+        if has_stats and getattr(model, "_tn_tet_stats", None) is not None:
+            model_tet_stats(model, reset=True, num_cells=result["num_cells"])
+            result["stats_reset"] = True
         return result

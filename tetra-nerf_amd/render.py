@@ -353,6 +353,70 @@ def occupancy_update_statement(occupancy: torch.Tensor, cells: torch.Tensor, sig
     return torch.maximum(decayed, top)
 
 
+def tet_stats_statement(stats, cells, weights, ray_value=None, ray_index=None, count=None):
+    """Statement of the per-tetrahedron training statistics (tn_tet_stats_accumulate computes it in place, byte for byte), in
+    numpy integers.  Returns stats + the batch as a NEW int64 [T,3] array; `stats` is not changed.
+    cells [rows,S]: the matched tetrahedron of every sample (int32 with -1 or uint32 with 0xFFFFFFFF = unmatched); weights f32
+    [rows,S]: the COMPOSITE'S OWN weights of these samples (cpp.composite(..., out_weights): an input, because the host's expf is
+    not the device's); row q belongs to ray ray_index[q] (None: q) of ray_value f32 [rays] (None: every value 1); only rows
+    q < count are read (None: all).
+        w^ = w >= 0 ? min(w, 1) : 0;   v^ = v >= 0 ? min(v, 256) : 0                       (NaN, negative, -0 -> 0)
+        for every sample with 0 <= cell < T:   stats[cell] += (1, rint(w^ * 2^32), rint(fl32(w^ * v^) * 2^32))
+    rint rounds half to even; w^ * 2^32 is exact in fp32; w^ * v^ is ONE fp32 multiply.  Integer sums: the order of the samples
+    cannot matter."""
+    import numpy as np
+
+    def host(x, dtype=None):
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        return x if dtype is None else x.astype(dtype)
+
+    out = host(stats, np.int64).copy()
+    T = out.shape[0]
+    c = host(cells)
+    c = c.reshape(-1, c.shape[-1]) if c.ndim >= 2 else c.reshape(1, -1)
+    if c.dtype.kind == "u":
+        c = c.astype(np.int64)
+    else:                                     # a signed id names the same 32 bits: -1 is 0xFFFFFFFF, never < T
+        c = c.astype(np.int64) & 0xFFFFFFFF if c.dtype.itemsize == 4 else c.astype(np.int64)
+    w = host(weights, np.float32).reshape(c.shape)
+    rows = c.shape[0] if count is None else min(c.shape[0], int(host(count).reshape(-1)[0]))
+    c, w = c[:rows], w[:rows]
+    ray = np.arange(rows, dtype=np.int64) if ray_index is None else host(ray_index).reshape(-1)[:rows].astype(np.int64) & 0xFFFFFFFF
+    v = np.ones(rows, np.float32) if ray_value is None else host(ray_value, np.float32).reshape(-1)[ray]
+    with np.errstate(invalid="ignore"):
+        wh = np.where(w >= 0, np.minimum(w, np.float32(1)), np.float32(0)).astype(np.float32)
+        vh = np.where(v >= 0, np.minimum(v, np.float32(256)), np.float32(0)).astype(np.float32)
+    scale = np.float32(2.0 ** 32)
+    qw = np.rint(wh * scale).astype(np.int64)
+    qe = np.rint((wh * vh[:, None]).astype(np.float32) * scale).astype(np.int64)
+    ok = (c >= 0) & (c < T)
+    np.add.at(out[:, 0], c[ok], 1)
+    np.add.at(out[:, 1], c[ok], qw[ok])
+    np.add.at(out[:, 2], c[ok], qe[ok])
+    return out
+
+
+def tet_stats_scores(stats: torch.Tensor, kind: str = "error") -> torch.Tensor:
+    """Per-tetrahedron scores f32 [T] of the statistics i64 [T,3] (plain torch, float64 inside):
+        "error"       sum of w^ v^        (stats[:,2] / 2^32)
+        "mean_error"  sum of w^ v^ / sum of w^, 0 where the sum of weights is 0
+        "weight"      sum of w^           (stats[:,1] / 2^32)
+        "hits"        the number of samples matched to the tetrahedron"""
+    st = stats.to(torch.float64)
+    scale = 2.0 ** -32
+    if kind == "error":
+        out = st[:, 2] * scale
+    elif kind == "mean_error":
+        out = torch.where(stats[:, 1] != 0, st[:, 2] / st[:, 1].clamp_min(1.0), torch.zeros_like(st[:, 2]))
+    elif kind == "weight":
+        out = st[:, 1] * scale
+    elif kind == "hits":
+        out = st[:, 0]
+    else:
+        raise ValueError(f'tet_stats_scores: kind must be "error", "mean_error", "weight" or "hits", got {kind!r}')
+    return out.to(torch.float32)
+
+
 def cull_mask_statement(cells: torch.Tensor, occupancy: torch.Tensor, threshold: float) -> torch.Tensor:
     """bool mask, shape of `cells`: True = the sample is CULLED, i.e. its cell is a valid id < T and occupancy[cell] < threshold.
     Unmatched samples stay live (they are evaluated on zero features, as without a field), a NaN occupancy is live (the
@@ -1365,7 +1429,7 @@ class TetraRenderer:
                      adjoint_mode: Optional[str] = None, dw_mode: Optional[str] = None,
                      occupancy: Optional[torch.Tensor] = None, occupancy_decay: Optional[float] = None,
                      occupancy_threshold: Optional[float] = None, occupancy_sampler: bool = False,
-                     aux_outputs: bool = False) -> Dict[str, torch.Tensor]:
+                     aux_outputs: bool = False, tet_stats: bool = False) -> Dict[str, torch.Tensor]:
         """One training forward (TetrahedraNerf.get_outputs in training mode, model.py:520-662): stratified coarse samples
         (uniform or biased), optional PDF fine pass on the detached coarse weights (nerfstudio's PDFSampler detaches them),
         gather + MLP + heads, optional GradientScaler, weights and renderers (training mode: no clamp) -- differentiable
@@ -1478,7 +1542,19 @@ class TetraRenderer:
         alone run.  The edges stay constants of the gradient.  GradientScaler, culled training, position gradients and the
         three arithmetic switches need no change: the composite node sits behind them and sees full-size [r,S] tensors.
         occupancy_sampler=True is refused with aux_outputs: the composite's edges are then live-length coordinates, and a
-        depth or a spread measured in them is another quantity."""
+        depth or a spread measured in them is another quantity.
+
+        tet_stats (opt-in, fused path; off: nothing else changes, not a launch, not an allocation): the result also has
+        "tet_stats_pending", what accumulate_tet_stats needs once the caller knows the error of every ray (the loss is formed
+        outside this call, hence the two steps): the final pass's "cell_indices" [r,S], "sigma" [r,S] (detached, contiguous;
+        after culling, before GradientScaler), "edges" [r,S+1], "ray_index" i32 [r] (row -> ray of the call) and "count" (the
+        device-side number of real rows of the sync-free form, whose padded duplicates must not be counted; None in the
+        compacting form); None when no ray hits.  Refused with fused=False (the accumulation is a kernel; its statement is
+        tet_stats_statement) and with occupancy_sampler=True (the edges are live-length coordinates there, as for aux_outputs)."""
+        if tet_stats and not fused:
+            raise RuntimeError("tet_stats is a kernel of the fused path (fused=True); its statement is tet_stats_statement")
+        if tet_stats and occupancy_sampler:
+            raise RuntimeError("tet_stats cannot be combined with occupancy_sampler: the composite's edges are live-length coordinates there")
         occ, modes = self._train_args(fused, position_gradients, mlp_mode, adjoint_mode, dw_mode, occupancy, occupancy_decay,
                                       occupancy_threshold, occupancy_sampler, aux_outputs)
         cpp, S = self.cpp, self.S
@@ -1505,6 +1581,8 @@ class TetraRenderer:
         bg = self._bg(background)
         frame = self._frame(R, bg, dev, ray_mask, aux_outputs)
         if idx.numel() == 0:
+            if tet_stats:
+                frame["tet_stats_pending"] = None
             return frame
         lists = trace_rows(out)
         ridx = padded if sync_free else idx.to(torch.int32)
@@ -1547,6 +1625,10 @@ class TetraRenderer:
         if occupancy_decay is not None:
             with torch.no_grad():
                 cpp.occupancy_update(occupancy, traced["cell_indices"], sigma.detach().contiguous(), occupancy_decay)
+        pending = None
+        if tet_stats:
+            pending = {"cell_indices": traced["cell_indices"], "sigma": sigma.detach().contiguous(), "edges": edges,
+                       "ray_index": ridx, "count": count if sync_free else None}
         if gradient_scaling and torch.is_grad_enabled():
             if to_distance is not None:     # distances of the edges, over the ray's own [near, far]
                 with torch.no_grad():
@@ -1555,7 +1637,21 @@ class TetraRenderer:
         rows = self._composite_rows(sigma, col, edges, bg, "node" if record else "kernels" if fused else "statement", aux_outputs)
         if to_distance is not None:
             rows["depth"] = _median_to_distance(rows["depth"], to_distance)
-        return _scatter_padded(frame, rows, order, valid[:, None]) if sync_free else _scatter_compacted(frame, rows, idx)
+        res = _scatter_padded(frame, rows, order, valid[:, None]) if sync_free else _scatter_compacted(frame, rows, idx)
+        if tet_stats:
+            res["tet_stats_pending"] = pending
+        return res
+
+    def accumulate_tet_stats(self, stats: torch.Tensor, pending: Optional[dict], ray_value: Optional[torch.Tensor]) -> torch.Tensor:
+        """Second step of render_train(tet_stats=True): add the batch to `stats` i64 [T,3] in place (cpp.tet_stats_accumulate,
+        under no_grad; statement: tet_stats_statement).  pending: the result's "tet_stats_pending" (None -- no ray hit --
+        adds nothing); ray_value f32 [R] over ALL rays of the call (e.g. the squared error of every rendered pixel; None: 1)."""
+        if pending is None:
+            return stats
+        with torch.no_grad():
+            rv = None if ray_value is None else ray_value.detach().to(torch.float32).reshape(-1).contiguous()
+            return self.cpp.tet_stats_accumulate(stats, pending["cell_indices"], pending["sigma"], pending["edges"], ray_value=rv,
+                                                 ray_index=pending["ray_index"], count=pending["count"])
 
     def _coarse_weights_statement(self, traced, edges, occ):
         """The coarse weights of a pass in PyTorch (model.py:577-582): gather, mlp_base + density head, get_weights; occ =

@@ -1080,6 +1080,57 @@ def occupancy_update(occupancy, cells, sigma, decay, samples_per_ray=None, count
     return occupancy
 
 
+# ---- per-tetrahedron training statistics (no reference counterpart: the reference never changes its mesh)
+
+TET_STATS_MAX_SAMPLES = 8192   # samples per ray tn_tet_stats_accumulate supports (a row's weights live in the wave's LDS)
+
+
+def tet_stats_new(num_cells, device):
+    """Zeroed statistics i64 [num_cells, 3] for tet_stats_accumulate: per tetrahedron (hits, sum of weights, sum of weight x
+    ray value), the last two in fixed point with 32 fractional bits (render.tet_stats_scores turns them into floats)."""
+    return torch.zeros((int(num_cells), 3), dtype=torch.int64, device=device)
+
+
+def tet_stats_accumulate(stats, cells, sigma, edges, ray_value=None, ray_index=None, count=None):
+    """IN PLACE accumulation of per-tetrahedron training statistics (tn_tet_stats_accumulate; statement:
+    render.tet_stats_statement, byte for byte).  stats i64 [T, 3]; cells i32 [rows, S] = the matched tetrahedron of every sample
+    (find_visited_cells' "cell_indices", -1 = unmatched); sigma f32 [rows, S] and edges f32 [rows, S + 1] = what the composite
+    of these rows takes -- the kernel forms the composite's own weights w from them and adds, for every sample with a cell < T,
+        stats[cell] += (1, rint(w^ * 2^32), rint(fl32(w^ * v^) * 2^32)),   w^ = clamp(w, 0, 1), v^ = clamp(v, 0, 256), NaN -> 0
+    with v = ray_value[ray_index[row]] (ray_value f32 [rays], None: 1; ray_index i32 [rows], None: the row itself; its entries
+    must be valid indices of ray_value).  count (i32 [1] on the device): only the first count[0] rows are read -- the padded
+    rows of compact_hits(want_padded=True) repeat a real ray and must not be counted.  Integer sums: independent of any order,
+    identical from run to run.  Caller's stream, no host synchronisation.  Returns `stats`."""
+    _check_cells(cells)
+    dev = cells.device
+    _check_input(stats, "stats")
+    _check(stats.dtype == torch.int64 and stats.dim() == 2 and stats.size(1) == 3 and stats.device == dev,
+           "stats must be i64 [num_cells, 3] on the samples' device (tet_stats_new)")
+    _check(stats.size(0) < 2 ** 32, "stats: too many tetrahedra")
+    _check(cells.dim() == 2, "cells must be i32 [rows, samples_per_ray]")
+    rows, S = cells.shape
+    for x, name, shape in ((sigma, "sigma", (rows, S)), (edges, "edges", (rows, S + 1))):
+        _check_input(x, name)
+        _check(x.dtype == torch.float32 and tuple(x.shape) == shape and x.device == dev,
+               f"{name} must be f32 {list(shape)} on the samples' device")
+    if ray_value is not None:
+        _check_input(ray_value, "ray_value")
+        _check(ray_value.dtype == torch.float32 and ray_value.dim() == 1 and ray_value.device == dev,
+               "ray_value must be f32 [rays] on the samples' device")
+        _check(ray_index is not None or ray_value.numel() >= rows, "ray_value must hold one value per row (or pass ray_index)")
+    if ray_index is not None:
+        _check_input(ray_index, "ray_index")
+        _check(ray_index.dtype == torch.int32 and ray_index.numel() == rows and ray_index.device == dev,
+               "ray_index must be i32 [rows] on the samples' device")
+        _check(ray_value is not None, "ray_index names entries of ray_value: pass ray_value")
+    if count is not None:
+        _check(count.dtype == torch.int32 and count.numel() >= 1 and count.device == dev, "count must be an i32 tensor on the samples' device")
+    with _on(dev):
+        _lib.check(_lib.load().tn_tet_stats_accumulate(stats.size(0), rows, S, _ptr(cells), _ptr(sigma), _ptr(edges), _ptr(ray_value),
+                                                       _ptr(ray_index), _ptr(count), _ptr(stats), _stream(dev)))
+    return stats
+
+
 def remap_tet_values(old_cells, new_cells, values, num_vertices, return_star_max=False):
     """Per-tetrahedron values (>= 0: the occupancy field) carried from `old_cells` to `new_cells` over the same vertices, without
     point location (tn_remap_tet_values; statement: geometry.remap_tet_values_statement):
