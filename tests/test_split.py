@@ -129,7 +129,12 @@ STRUCTURED = ("cube_all", "random_300_30pct", "grid_4_all", "grid_6_all", "near_
 @pytest.mark.parametrize("name", STRUCTURED)
 def test_split_mesh_is_conforming_and_keeps_orientations(scenes, oracle, name):
     xyz, cells, select = sc.case(scenes, name)
-    s = sc.statement(scenes, name)
+    check_structure(oracle, xyz, cells, sc.statement(scenes, name), name)
+
+
+def check_structure(oracle, xyz, cells, s, name):
+    """the checks of the test above on one split: (xyz, cells) is the input, s the statement's answer (also used on the generation
+    meshes of tests/lifecycle_lib.py, whose input is itself the output of a split)"""
     V, T, K = len(xyz), len(cells), s["num_new"]
     assert K > 0 and s["cells"].shape == (T + 3 * K, 4) and s["vertices"].shape == (V + K, 3)
     faces, face_tets = oracle.build_faces(s["cells"])                         # raises on a face in three tetrahedra
