@@ -26,9 +26,9 @@
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "tn_build.h"
+#include "tn_mesh_ops.h"
 
 namespace tn {
 
@@ -37,7 +37,6 @@ namespace {
 constexpr int BT = 256;
 constexpr int MAX_WIDE_LEVELS = 16;
 inline unsigned grid_for(size_t n) { return (unsigned)((n + BT - 1) / BT); }
-__device__ __forceinline__ size_t gid() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -329,10 +328,8 @@ void sort_pairs(Temp &tmp, const uint64_t *kin, uint64_t *kout, const uint32_t *
     TN_HIP(rocprim::radix_sort_pairs(p, bytes, kin, kout, vin, vout, n, 0u, end_bit, s));
 }
 void exclusive_scan(Temp &tmp, const uint32_t *in, uint32_t *out, size_t n, hipStream_t s) {
-    size_t bytes = 0;
-    TN_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s));
-    void *p = tmp.need(bytes);
-    TN_HIP(rocprim::exclusive_scan(p, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s));
+    const size_t bytes = scan_bytes<const uint32_t *>(n, s);
+    scan(tmp.need(bytes), bytes, in, out, n, s);
 }
 template <typename T>
 T read_back(const T *dev, hipStream_t s) {

@@ -10,15 +10,14 @@
 //                     floats order like their bits: k_star_width's trick with the other sign); a value of +0 launches nothing.
 //   k_remap           lane per new tetrahedron: the largest star_max of its four vertices.
 //
-// All three are grid-stride loops on at most DELAUNAY_BLOCKS blocks.  Counters are reduced per block (shuffle, then LDS) to one
-// atomic per block and counter, and none where the block's sum is 0 (k_refit_records, k_clamp_vertices).  No read-back, no
+// All three are grid-stride loops on at most DELAUNAY_BLOCKS blocks (tn_mesh_ops.h).  Counters are reduced per block to one
+// atomic per block and counter, and none where the block's sum is 0 (block_count, tn_mesh_ops.h).  No read-back, no
 // allocation; everything is enqueued on the caller's stream.  The transfer's cells come from the caller, not from a loaded
 // tracer: a vertex id that is not below num_vertices is passed over by both of its kernels.
-#include <algorithm>
-
 #include <hip/hip_runtime.h>
 
 #include "tn_build.h"
+#include "tn_mesh_ops.h"
 #include "tn_delaunay_core.h"
 
 namespace tn {
@@ -27,33 +26,12 @@ namespace {
 
 constexpr int BT = 256;
 constexpr unsigned DELAUNAY_BLOCKS = 1024;   // grid cap of the three kernels (TetrahedraTracer.DELAUNAY_GRID_LANES = DELAUNAY_BLOCKS * BT)
-inline unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>((n + BT - 1) / BT, DELAUNAY_BLOCKS); }
-__device__ __forceinline__ size_t gid() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ size_t stride() { return (size_t)gridDim.x * BT; }
-
-// sums of n[0..3] over the block -> one atomicAdd per non-zero sum
-__device__ __forceinline__ void block_count4(uint32_t n[4], uint32_t *out) {
-    __shared__ uint32_t part[BT / 64][4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) n[c] += (uint32_t)__shfl_xor((int)n[c], off);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) part[threadIdx.x >> 6][c] = n[c];
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        uint32_t r = 0;
-        for (int w = 0; w < BT / 64; ++w) r += part[w][threadIdx.x];
-        if (r) atomicAdd(out + threadIdx.x, r);
-    }
-}
 
 __global__ __launch_bounds__(BT) void k_delaunay_faces(size_t F, const uint32_t *__restrict__ face_tets,
                                                        const uint32_t *__restrict__ cells, const float *__restrict__ xyz,
                                                        int8_t *__restrict__ face_state, uint32_t *tet_violations, uint32_t *counters) {
     uint32_t n[4] = {0, 0, 0, 0};
-    for (size_t f = gid(); f < F; f += stride()) {
+    for (size_t f = gid(); f < F; f += stride<BT>()) {
         const uint32_t t0 = face_tets[2 * f], t1 = face_tets[2 * f + 1];
         int state = delaunay::HULL;
         if (t1 != TN_EMPTY) {
@@ -81,12 +59,12 @@ __global__ __launch_bounds__(BT) void k_delaunay_faces(size_t F, const uint32_t 
         }
         if (face_state) face_state[f] = (int8_t)state;
     }
-    block_count4(n, counters);
+    block_count<BT>(n, counters);
 }
 
 __global__ __launch_bounds__(BT) void k_star_max(size_t T, uint32_t V, const uint32_t *__restrict__ cells,
                                                  const uint32_t *__restrict__ values, uint32_t *star_max) {
-    for (size_t i = gid(); i < T; i += stride()) {
+    for (size_t i = gid(); i < T; i += stride<BT>()) {
         const uint32_t bits = values[i];
         if (bits == 0) continue;                       // the preset already holds +0
 #pragma unroll
@@ -99,7 +77,7 @@ __global__ __launch_bounds__(BT) void k_star_max(size_t T, uint32_t V, const uin
 
 __global__ __launch_bounds__(BT) void k_remap(size_t T, uint32_t V, const uint32_t *__restrict__ cells,
                                               const uint32_t *__restrict__ star_max, uint32_t *__restrict__ values) {
-    for (size_t i = gid(); i < T; i += stride()) {
+    for (size_t i = gid(); i < T; i += stride<BT>()) {
         uint32_t m = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -117,8 +95,8 @@ void launch_delaunay_check(size_t T, size_t F, const uint32_t *cells, const uint
     TN_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), s));
     if (tet_violations && T) TN_HIP(hipMemsetAsync(tet_violations, 0, 4 * ((T + 3) / 4), s));
     if (F)
-        hipLaunchKernelGGL(k_delaunay_faces, dim3(grid_for(F)), dim3(BT), 0, s, F, face_tets, cells, xyz, face_state,
-                           reinterpret_cast<uint32_t *>(tet_violations), counters);
+        hipLaunchKernelGGL(k_delaunay_faces, dim3(grid_for<BT, DELAUNAY_BLOCKS>(F)), dim3(BT), 0, s, F, face_tets, cells, xyz,
+                           face_state, reinterpret_cast<uint32_t *>(tet_violations), counters);
     TN_HIP(hipGetLastError());
 }
 
@@ -126,10 +104,10 @@ void launch_remap_tet_values(size_t V, size_t T_old, const uint32_t *old_cells, 
                              const uint32_t *new_cells, float *new_values, float *star_max, hipStream_t s) {
     if (V) TN_HIP(hipMemsetAsync(star_max, 0, V * sizeof(float), s));
     if (T_old)
-        hipLaunchKernelGGL(k_star_max, dim3(grid_for(T_old)), dim3(BT), 0, s, T_old, (uint32_t)V, old_cells,
+        hipLaunchKernelGGL(k_star_max, dim3(grid_for<BT, DELAUNAY_BLOCKS>(T_old)), dim3(BT), 0, s, T_old, (uint32_t)V, old_cells,
                            reinterpret_cast<const uint32_t *>(old_values), reinterpret_cast<uint32_t *>(star_max));
     if (T_new)
-        hipLaunchKernelGGL(k_remap, dim3(grid_for(T_new)), dim3(BT), 0, s, T_new, (uint32_t)V, new_cells,
+        hipLaunchKernelGGL(k_remap, dim3(grid_for<BT, DELAUNAY_BLOCKS>(T_new)), dim3(BT), 0, s, T_new, (uint32_t)V, new_cells,
                            reinterpret_cast<const uint32_t *>(star_max), reinterpret_cast<uint32_t *>(new_values));
     TN_HIP(hipGetLastError());
 }

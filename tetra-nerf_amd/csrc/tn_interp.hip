@@ -24,6 +24,7 @@
 
 #include "tn_device.h"
 #include "tn_kernels.h"
+#include "tn_mesh_ops.h"
 
 namespace tn {
 
@@ -279,18 +280,6 @@ __global__ __launch_bounds__(256) void k_interp_bwd(uint32_t n, uint32_t Fd, con
     }
 }
 
-// stream-ordered temporary, released when the scope is left (also when a launch check throws)
-struct AsyncBuf {
-    float *p = nullptr;
-    hipStream_t s;
-    AsyncBuf(size_t floats, hipStream_t stream) : s(stream) {
-        if (floats) TN_HIP(hipMallocAsync((void **)&p, floats * sizeof(float), stream));
-    }
-    ~AsyncBuf() { if (p) (void)hipFreeAsync(p, s); }
-    AsyncBuf(const AsyncBuf &) = delete;
-    AsyncBuf &operator=(const AsyncBuf &) = delete;
-};
-
 // fieldT: the field vertex-major [V, Fd]
 template <int D>
 void run_fwd_vm(uint32_t n, uint32_t Fd, const uint32_t *vi, const float *bc, const float *fieldT, float *result,
@@ -322,9 +311,9 @@ void run_bwd_vm(uint32_t n, uint32_t Fd, const uint32_t *vi, const float *bc, co
 template <int D>
 void run_fwd(uint32_t V, uint32_t n, uint32_t Fd, const uint32_t *vi, const float *bc, const float *field,
              float *result, hipStream_t stream) {
-    AsyncBuf fieldT((size_t)V * Fd, stream);
-    launch_transpose(field, fieldT.p, Fd, V, stream);
-    run_fwd_vm<D>(n, Fd, vi, bc, fieldT.p, result, stream);
+    AsyncBytes fieldT((size_t)V * Fd * sizeof(float), stream);
+    launch_transpose(field, fieldT.at<float>(), Fd, V, stream);
+    run_fwd_vm<D>(n, Fd, vi, bc, fieldT.at<float>(), result, stream);
 }
 
 // rows_major: grad_in is [n, Fd] (what autograd hands over for a contiguous [..., Fd] gradient);
@@ -332,17 +321,17 @@ void run_fwd(uint32_t V, uint32_t n, uint32_t Fd, const uint32_t *vi, const floa
 template <int D>
 void run_bwd(uint32_t V, uint32_t n, uint32_t Fd, const uint32_t *vi, const float *bc, const float *grad_in,
              bool rows_major, float *field_grad, hipStream_t stream) {
-    AsyncBuf gradT((size_t)V * Fd, stream);
+    AsyncBytes gradT((size_t)V * Fd * sizeof(float), stream);
     TN_HIP(hipMemsetAsync(gradT.p, 0, (size_t)V * Fd * sizeof(float), stream));
     if (n) {
-        AsyncBuf rows(rows_major ? 0 : (size_t)n * Fd, stream);
+        AsyncBytes rows(rows_major ? 0 : (size_t)n * Fd * sizeof(float), stream);
         if (!rows_major) {
-            launch_transpose(grad_in, rows.p, Fd, n, stream);
-            grad_in = rows.p;
+            launch_transpose(grad_in, rows.at<float>(), Fd, n, stream);
+            grad_in = rows.at<float>();
         }
-        run_bwd_vm<D>(n, Fd, vi, bc, grad_in, gradT.p, stream);
+        run_bwd_vm<D>(n, Fd, vi, bc, grad_in, gradT.at<float>(), stream);
     }
-    launch_transpose(gradT.p, field_grad, V, Fd, stream);
+    launch_transpose(gradT.at<float>(), field_grad, V, Fd, stream);
 }
 
 // ---- the adjoint WITHOUT float atomics (opt-in: bit-reproducible field gradients) -------------------------------------
@@ -420,8 +409,8 @@ void run_bwd_det(uint32_t V, uint32_t n, uint32_t Fd, const uint32_t *vi, const 
     size_t bytes = 0;
     TN_HIP(rocprim::radix_sort_pairs(nullptr, bytes, vi, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, np, 0u, 32u, stream));
     const size_t npa = (np + 63) & ~(size_t)63, nb = (2 * (size_t)V + 63) & ~(size_t)63;
-    AsyncBuf all(3 * npa + nb + (bytes + 3) / 4 + 64, stream);
-    uint32_t *ks = reinterpret_cast<uint32_t *>(all.p), *vs = ks + npa, *io = vs + npa;
+    AsyncBytes all((3 * npa + nb + (bytes + 3) / 4 + 64) * sizeof(uint32_t), stream);
+    uint32_t *ks = all.at<uint32_t>(), *vs = ks + npa, *io = vs + npa;
     uint32_t *st = io + npa, *en = st + V;
     void *tmp = st + nb;
     hipLaunchKernelGGL(k_iota, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream, (uint32_t)np, io);

@@ -17,17 +17,18 @@
 //   k_iso_triangles  lane per tetrahedron: the table rows, the orientation swap and the slot_id lookups give `triangles` and
 //                    `triangle_tets` at tri_offsets[t] + row.
 //
-// Every kernel is a grid-stride loop on at most ISO_BLOCKS blocks.  No float atomics, no atomics at all: every output element has
-// one writer, and the sort is stable, so nothing depends on scheduling.  Scratch is ONE stream-ordered allocation per entry
-// (tn_interp.hip does the same for its sort).  Every store is bounded by the counts the caller passed; ids read from a key are
-// checked against V.  Nothing is read back here: the caller reads the totals between the two entries.
+// Every kernel is a grid-stride loop on at most ISO_BLOCKS blocks (tn_mesh_ops.h).  No float atomics, no atomics at all: every
+// output element has one writer, and the sort is stable, so nothing depends on scheduling.  Scratch is ONE stream-ordered
+// allocation per entry (AsyncBytes, tn_mesh_ops.h; tn_interp.hip does the same for its sort).  Every store is bounded by the
+// counts the caller passed; ids read from a key are checked against V.  Nothing is read back here: the caller reads the totals
+// between the two entries.
 #include <algorithm>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include "tn_build.h"
+#include "tn_mesh_ops.h"
 #include "tn_isosurface_core.h"
 
 namespace tn {
@@ -36,9 +37,6 @@ namespace {
 
 constexpr int BT = 256;
 constexpr unsigned ISO_BLOCKS = 1024;   // grid cap of every kernel here (TetrahedraTracer.ISOSURFACE_GRID_LANES = ISO_BLOCKS * BT)
-inline unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>((n + BT - 1) / BT, ISO_BLOCKS); }
-__device__ __forceinline__ size_t gid() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ size_t stride() { return (size_t)gridDim.x * BT; }
 
 // the case of tetrahedron t; c = its cell row (read only when the mask lets it through)
 __device__ __forceinline__ iso::TetCase tet_case(size_t t, uint32_t V, const uint32_t *__restrict__ cells,
@@ -60,7 +58,7 @@ __global__ __launch_bounds__(BT) void k_iso_count(size_t T, uint32_t V, const ui
                                                   const float *__restrict__ values, float level,
                                                   const uint8_t *__restrict__ tet_mask, uint32_t *__restrict__ tri_count,
                                                   uint32_t *__restrict__ ref_count) {
-    for (size_t t = gid(); t <= T; t += stride()) {
+    for (size_t t = gid(); t <= T; t += stride<BT>()) {
         uint32_t c[4];
         const iso::TetCase k = t < T ? tet_case(t, V, cells, values, level, tet_mask, c) : iso::TetCase{0u, 0u, 0u, 0u};
         tri_count[t] = k.ntri;
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(BT) void k_iso_count(size_t T, uint32_t V, const ui
 }
 
 __global__ __launch_bounds__(BT) void k_iso_fill(size_t num_refs, uint64_t *__restrict__ keys, uint32_t *__restrict__ slots) {
-    for (size_t i = gid(); i < num_refs; i += stride()) {
+    for (size_t i = gid(); i < num_refs; i += stride<BT>()) {
         keys[i] = ~0ull;
         slots[i] = (uint32_t)i;
     }
@@ -79,7 +77,7 @@ __global__ __launch_bounds__(BT) void k_iso_keys(size_t T, uint32_t V, const uin
                                                  const float *__restrict__ values, float level,
                                                  const uint8_t *__restrict__ tet_mask, const uint32_t *__restrict__ ref_offsets,
                                                  size_t num_refs, uint64_t *__restrict__ keys) {
-    for (size_t t = gid(); t < T; t += stride()) {
+    for (size_t t = gid(); t < T; t += stride<BT>()) {
         uint32_t c[4];
         const iso::TetCase k = tet_case(t, V, cells, values, level, tet_mask, c);
         if (k.nref == 0) continue;
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(BT) void k_iso_keys(size_t T, uint32_t V, const uin
 // flags[i], i in [0, num_refs]: 1 where sorted position i starts a run of equal keys; flags[num_refs] = 0
 __global__ __launch_bounds__(BT) void k_iso_heads(size_t num_refs, const uint64_t *__restrict__ sorted_keys,
                                                   uint32_t *__restrict__ flags) {
-    for (size_t i = gid(); i <= num_refs; i += stride())
+    for (size_t i = gid(); i <= num_refs; i += stride<BT>())
         flags[i] = i < num_refs && (i == 0 || sorted_keys[i] != sorted_keys[i - 1]);
 }
 
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(BT) void k_iso_vertices(size_t num_refs, uint32_t V
                                                      uint32_t *__restrict__ slot_id, uint32_t *__restrict__ edge_vertices,
                                                      float *__restrict__ edge_t, float *__restrict__ positions,
                                                      uint32_t *__restrict__ num_out_vertices) {
-    for (size_t i = gid(); i < num_refs; i += stride()) {
+    for (size_t i = gid(); i < num_refs; i += stride<BT>()) {
         const uint32_t before = below[i], upto = below[i + 1];
         const uint32_t id = upto - 1u;                     // upto >= 1: position 0 is a head
         const uint32_t slot = sorted_slots[i];
@@ -139,7 +137,7 @@ __global__ __launch_bounds__(BT) void k_iso_triangles(size_t T, uint32_t V, cons
                                                       const uint32_t *__restrict__ ref_offsets, size_t num_triangles, size_t num_refs,
                                                       const uint32_t *__restrict__ slot_id, uint32_t *__restrict__ triangles,
                                                       uint32_t *__restrict__ triangle_tets) {
-    for (size_t t = gid(); t < T; t += stride()) {
+    for (size_t t = gid(); t < T; t += stride<BT>()) {
         uint32_t c[4];
         const iso::TetCase k = tet_case(t, V, cells, values, level, tet_mask, c);
         if (k.ntri == 0) continue;
@@ -163,27 +161,6 @@ __global__ __launch_bounds__(BT) void k_iso_triangles(size_t T, uint32_t V, cons
     }
 }
 
-// stream-ordered temporary, released when the scope is left (also when a launch check throws)
-struct AsyncBytes {
-    char *p = nullptr;
-    hipStream_t s;
-    AsyncBytes(size_t bytes, hipStream_t stream) : s(stream) {
-        if (bytes) TN_HIP(hipMallocAsync((void **)&p, bytes, stream));
-    }
-    ~AsyncBytes() { if (p) (void)hipFreeAsync(p, s); }
-    AsyncBytes(const AsyncBytes &) = delete;
-    AsyncBytes &operator=(const AsyncBytes &) = delete;
-};
-
-inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-size_t scan_bytes(size_t n, hipStream_t s) {
-    size_t bytes = 0;
-    TN_HIP(rocprim::exclusive_scan(nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), s));
-    return bytes;
-}
-void scan(void *tmp, size_t bytes, uint32_t *in, uint32_t *out, size_t n, hipStream_t s) {
-    TN_HIP(rocprim::exclusive_scan(tmp, bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), s));
-}
 unsigned bit_width(uint64_t v) { unsigned b = 0; while (v) { ++b; v >>= 1; } return b; }
 
 }  // namespace
@@ -197,10 +174,10 @@ void launch_isosurface_count(size_t V, size_t T, const uint32_t *cells, const fl
     }
     const size_t n = T + 1, tmp_bytes = scan_bytes(n, s), count_bytes = align256(n * sizeof(uint32_t));
     AsyncBytes all(2 * count_bytes + tmp_bytes, s);   // triangle counts | crossing-edge counts | rocprim's scratch
-    uint32_t *tri_count = reinterpret_cast<uint32_t *>(all.p), *ref_count = reinterpret_cast<uint32_t *>(all.p + count_bytes);
+    uint32_t *tri_count = all.at<uint32_t>(), *ref_count = all.at<uint32_t>(count_bytes);
     void *tmp = all.p + 2 * count_bytes;
-    hipLaunchKernelGGL(k_iso_count, dim3(grid_for(n)), dim3(BT), 0, s, T, (uint32_t)V, cells, values, level, tet_mask, tri_count,
-                       ref_count);
+    hipLaunchKernelGGL(k_iso_count, dim3(grid_for<BT, ISO_BLOCKS>(n)), dim3(BT), 0, s, T, (uint32_t)V, cells, values, level, tet_mask,
+                       tri_count, ref_count);
     TN_HIP(hipGetLastError());
     scan(tmp, tmp_bytes, tri_count, tri_offsets, n, s);
     scan(tmp, tmp_bytes, ref_count, ref_offsets, n, s);
@@ -224,25 +201,25 @@ void launch_isosurface_emit(size_t V, size_t T, const float *xyz, const uint32_t
     const size_t key_bytes = align256(nr * sizeof(uint64_t)), word_bytes = align256((nr + 1) * sizeof(uint32_t));
     // keys | sorted keys | slots | sorted slots | head flags | their scan | slot -> welded id | rocprim's scratch
     AsyncBytes all(2 * key_bytes + 5 * word_bytes + tmp_bytes, s);
-    uint64_t *keys = reinterpret_cast<uint64_t *>(all.p), *sorted_keys = reinterpret_cast<uint64_t *>(all.p + key_bytes);
+    uint64_t *keys = all.at<uint64_t>(), *sorted_keys = all.at<uint64_t>(key_bytes);
     uint32_t *words[5];
-    for (int k = 0; k < 5; ++k) words[k] = reinterpret_cast<uint32_t *>(all.p + 2 * key_bytes + k * word_bytes);
+    for (int k = 0; k < 5; ++k) words[k] = all.at<uint32_t>(2 * key_bytes + k * word_bytes);
     uint32_t *slots = words[0], *sorted_slots = words[1], *flags = words[2], *below = words[3], *slot_id = words[4];
     void *tmp = all.p + 2 * key_bytes + 5 * word_bytes;
 
-    hipLaunchKernelGGL(k_iso_fill, dim3(grid_for(nr)), dim3(BT), 0, s, nr, keys, slots);
-    hipLaunchKernelGGL(k_iso_keys, dim3(grid_for(T)), dim3(BT), 0, s, T, (uint32_t)V, cells, values, level, tet_mask, ref_offsets, nr,
-                       keys);
+    hipLaunchKernelGGL(k_iso_fill, dim3(grid_for<BT, ISO_BLOCKS>(nr)), dim3(BT), 0, s, nr, keys, slots);
+    hipLaunchKernelGGL(k_iso_keys, dim3(grid_for<BT, ISO_BLOCKS>(T)), dim3(BT), 0, s, T, (uint32_t)V, cells, values, level, tet_mask,
+                       ref_offsets, nr, keys);
     TN_HIP(hipGetLastError());
     TN_HIP(rocprim::radix_sort_pairs(tmp, sort_bytes, keys, sorted_keys, slots, sorted_slots, nr, 0u, end_bit, s));
-    hipLaunchKernelGGL(k_iso_heads, dim3(grid_for(nr + 1)), dim3(BT), 0, s, nr, sorted_keys, flags);
+    hipLaunchKernelGGL(k_iso_heads, dim3(grid_for<BT, ISO_BLOCKS>(nr + 1)), dim3(BT), 0, s, nr, sorted_keys, flags);
     TN_HIP(hipGetLastError());
     scan(tmp, tmp_bytes, flags, below, nr + 1, s);
-    hipLaunchKernelGGL(k_iso_vertices, dim3(grid_for(nr)), dim3(BT), 0, s, nr, (uint32_t)V, sorted_keys, sorted_slots, below, xyz, values,
-                       level, slot_id, edge_vertices, edge_t, positions, num_out_vertices);
+    hipLaunchKernelGGL(k_iso_vertices, dim3(grid_for<BT, ISO_BLOCKS>(nr)), dim3(BT), 0, s, nr, (uint32_t)V, sorted_keys, sorted_slots,
+                       below, xyz, values, level, slot_id, edge_vertices, edge_t, positions, num_out_vertices);
     if (num_triangles)
-        hipLaunchKernelGGL(k_iso_triangles, dim3(grid_for(T)), dim3(BT), 0, s, T, (uint32_t)V, xyz, cells, values, level, tet_mask,
-                           tri_offsets, ref_offsets, num_triangles, nr, slot_id, triangles, triangle_tets);
+        hipLaunchKernelGGL(k_iso_triangles, dim3(grid_for<BT, ISO_BLOCKS>(T)), dim3(BT), 0, s, T, (uint32_t)V, xyz, cells, values,
+                           level, tet_mask, tri_offsets, ref_offsets, num_triangles, nr, slot_id, triangles, triangle_tets);
     TN_HIP(hipGetLastError());
 }
 

@@ -11,14 +11,13 @@
 //                          place -- the lane that reads an element is the one that writes it.
 //   k_iso_refine_vertices  lane per vertex: edge_t and positions of the bracket as it stands.
 //
-// Every kernel is a grid-stride loop on at most ISO_BLOCKS blocks of BT, a lane per element, one writer per element, no atomics,
-// no scratch, nothing read back.  Every index is bounded by the count the caller passed; ids are checked against V before `values`
-// or `xyz` is read.
-#include <algorithm>
-
+// Every kernel is a grid-stride loop on at most ISO_BLOCKS blocks of BT (tn_mesh_ops.h), a lane per element, one writer per
+// element, no atomics, no scratch, nothing read back.  Every index is bounded by the count the caller passed; ids are checked
+// against V before `values` or `xyz` is read.
 #include <hip/hip_runtime.h>
 
 #include "tn_build.h"
+#include "tn_mesh_ops.h"
 #include "tn_isosurface_core.h"
 
 namespace tn {
@@ -28,9 +27,6 @@ namespace {
 constexpr int BT = 256;
 constexpr unsigned ISO_BLOCKS = 1024;   // the grid cap of tn_isosurface.hip
 constexpr int C = iso::REFINE_CANDIDATES;
-inline unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>((n + BT - 1) / BT, ISO_BLOCKS); }
-__device__ __forceinline__ size_t gid() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ size_t stride() { return (size_t)gridDim.x * BT; }
 
 __device__ __forceinline__ iso::Bracket load_bracket(const float4 *__restrict__ brackets, size_t i) {
     const float4 b = brackets[i];
@@ -43,7 +39,7 @@ __device__ __forceinline__ void store_bracket(float4 *__restrict__ brackets, siz
 __global__ __launch_bounds__(BT) void k_iso_refine_begin(size_t N, uint32_t V, const uint2 *__restrict__ edge_vertices,
                                                          const float *__restrict__ values, float level,
                                                          float4 *__restrict__ brackets, uint8_t *__restrict__ flags) {
-    for (size_t i = gid(); i < N; i += stride()) {
+    for (size_t i = gid(); i < N; i += stride<BT>()) {
         const uint2 e = edge_vertices[i];
         iso::Bracket br;
         flags[i] = iso::refine_begin(e.x, e.y, V, values, level, br);
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(BT) void k_iso_refine_points(size_t N, const uint2 
                                                           const float4 *__restrict__ brackets, const uint8_t *__restrict__ flags,
                                                           uint4 *__restrict__ vertex_indices, float *__restrict__ barycentric) {
     const size_t n = N * C;
-    for (size_t i = gid(); i < n; i += stride()) {
+    for (size_t i = gid(); i < n; i += stride<BT>()) {
         const size_t v = i / C;
         const int j = (int)(i - v * C) + 1;
         uint2 e = edge_vertices[v];
@@ -70,7 +66,7 @@ __global__ __launch_bounds__(BT) void k_iso_refine_points(size_t N, const uint2 
 
 __global__ __launch_bounds__(BT) void k_iso_refine_select(size_t N, float level, const float *__restrict__ densities,
                                                           float4 *__restrict__ brackets, uint8_t *__restrict__ flags) {
-    for (size_t i = gid(); i < N; i += stride()) {
+    for (size_t i = gid(); i < N; i += stride<BT>()) {
         const uint8_t flag = flags[i];
         if (flag) continue;                 // frozen: the bracket and the flag stay
         float s[C];
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(BT) void k_iso_refine_vertices(size_t N, uint32_t V
                                                             const uint2 *__restrict__ edge_vertices,
                                                             const float4 *__restrict__ brackets, float level,
                                                             float *__restrict__ edge_t, float *__restrict__ positions) {
-    for (size_t i = gid(); i < N; i += stride()) {
+    for (size_t i = gid(); i < N; i += stride<BT>()) {
         const uint2 e = edge_vertices[i];
         float t = 0.f, p[3] = {0.f, 0.f, 0.f};
         if (e.x < V && e.y < V) {
@@ -107,7 +103,7 @@ __global__ __launch_bounds__(BT) void k_iso_refine_vertices(size_t N, uint32_t V
 void launch_isosurface_refine_begin(size_t V, size_t N, const uint32_t *edge_vertices, const float *values, float level,
                                     float *brackets, uint8_t *flags, hipStream_t s) {
     if (N == 0) return;
-    hipLaunchKernelGGL(k_iso_refine_begin, dim3(grid_for(N)), dim3(BT), 0, s, N, (uint32_t)V,
+    hipLaunchKernelGGL(k_iso_refine_begin, dim3(grid_for<BT, ISO_BLOCKS>(N)), dim3(BT), 0, s, N, (uint32_t)V,
                        reinterpret_cast<const uint2 *>(edge_vertices), values, level, reinterpret_cast<float4 *>(brackets), flags);
     TN_HIP(hipGetLastError());
 }
@@ -115,15 +111,16 @@ void launch_isosurface_refine_begin(size_t V, size_t N, const uint32_t *edge_ver
 void launch_isosurface_refine_points(size_t N, const uint32_t *edge_vertices, const float *brackets, const uint8_t *flags,
                                      uint32_t *vertex_indices, float *barycentric, hipStream_t s) {
     if (N == 0) return;
-    hipLaunchKernelGGL(k_iso_refine_points, dim3(grid_for(N * C)), dim3(BT), 0, s, N, reinterpret_cast<const uint2 *>(edge_vertices),
-                       reinterpret_cast<const float4 *>(brackets), flags, reinterpret_cast<uint4 *>(vertex_indices), barycentric);
+    hipLaunchKernelGGL(k_iso_refine_points, dim3(grid_for<BT, ISO_BLOCKS>(N * C)), dim3(BT), 0, s, N,
+                       reinterpret_cast<const uint2 *>(edge_vertices), reinterpret_cast<const float4 *>(brackets), flags,
+                       reinterpret_cast<uint4 *>(vertex_indices), barycentric);
     TN_HIP(hipGetLastError());
 }
 
 void launch_isosurface_refine_select(size_t N, float level, const float *densities, float *brackets, uint8_t *flags,
                                      hipStream_t s) {
     if (N == 0) return;
-    hipLaunchKernelGGL(k_iso_refine_select, dim3(grid_for(N)), dim3(BT), 0, s, N, level, densities,
+    hipLaunchKernelGGL(k_iso_refine_select, dim3(grid_for<BT, ISO_BLOCKS>(N)), dim3(BT), 0, s, N, level, densities,
                        reinterpret_cast<float4 *>(brackets), flags);
     TN_HIP(hipGetLastError());
 }
@@ -131,7 +128,7 @@ void launch_isosurface_refine_select(size_t N, float level, const float *densiti
 void launch_isosurface_refine_vertices(size_t V, size_t N, const float *xyz, const uint32_t *edge_vertices, const float *brackets,
                                        float level, float *edge_t, float *positions, hipStream_t s) {
     if (N == 0) return;
-    hipLaunchKernelGGL(k_iso_refine_vertices, dim3(grid_for(N)), dim3(BT), 0, s, N, (uint32_t)V, xyz,
+    hipLaunchKernelGGL(k_iso_refine_vertices, dim3(grid_for<BT, ISO_BLOCKS>(N)), dim3(BT), 0, s, N, (uint32_t)V, xyz,
                        reinterpret_cast<const uint2 *>(edge_vertices), reinterpret_cast<const float4 *>(brackets), level, edge_t,
                        positions);
     TN_HIP(hipGetLastError());

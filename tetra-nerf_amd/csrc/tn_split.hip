@@ -3,7 +3,8 @@
 //
 //   k_split_flags     lane per tetrahedron: select byte, cell row (16 B), four position gathers, five orientations in double;
 //                     writes the accepted flag (lane T writes the 0 the scan turns into the total) and counts the four verdicts
-//                     per lane; a block adds its four sums to `counters` once.  rocprim::exclusive_scan gives offsets[T + 1].
+//                     per lane; a block adds its four sums to `counters` once (block_count, tn_mesh_ops.h).
+//                     rocprim::exclusive_scan gives offsets[T + 1].
 //   k_split_cells     lane per tetrahedron: copies the row or, where offsets say accepted, writes the centroid, the four children,
 //                     their parents and the new vertex's parents.  The old vertices are one device-to-device copy.
 //   k_split_copy_rows lane per 16-byte chunk of the OUTPUT: out[r, 0 .. V) = values[r, 0 .. V).  The two strides differ (V and
@@ -14,16 +15,17 @@
 //                     array; out[r, V + k] is stored along k and out_vm[V + k, r] along r, both whole lines.
 //   The old part of out_vm is a copy of values_vm where the caller has it and launch_transpose(values) where it has not.
 //
-// Every kernel is a grid-stride loop on at most SPLIT_BLOCKS blocks.  The only atomics are the four counters (one add per block
-// and counter).  Scratch is ONE stream-ordered allocation (tn_split_count alone needs any).  Every store is bounded by the
-// counts the caller passed, every id is checked against V before it is used as an address.  Nothing is read back here.
+// Every kernel is a grid-stride loop on at most SPLIT_BLOCKS blocks (tn_mesh_ops.h).  The only atomics are the four counters (one
+// add per block and counter).  Scratch is ONE stream-ordered allocation (AsyncBytes; tn_split_count alone needs any).  Every store
+// is bounded by the counts the caller passed, every id is checked against V before it is used as an address.  Nothing is read back
+// here.
 #include <algorithm>
 
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
 
 #include "tn_build.h"
 #include "tn_kernels.h"
+#include "tn_mesh_ops.h"
 #include "tn_split_core.h"
 
 namespace tn {
@@ -33,15 +35,12 @@ namespace {
 constexpr int BT = 256;
 constexpr unsigned SPLIT_BLOCKS = 1024;   // grid cap of every kernel here (TetrahedraTracer.SPLIT_GRID_LANES = SPLIT_BLOCKS * BT)
 constexpr int TILE = 64;                  // new vertices and rows per block of k_split_new_columns
-inline unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>((n + BT - 1) / BT, SPLIT_BLOCKS); }
-__device__ __forceinline__ size_t gid() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ size_t stride() { return (size_t)gridDim.x * BT; }
 
 __global__ __launch_bounds__(BT) void k_split_flags(size_t T, uint32_t V, const float *__restrict__ xyz,
                                                     const uint32_t *__restrict__ cells, const uint8_t *__restrict__ select,
                                                     uint32_t *__restrict__ flags, uint32_t *__restrict__ counters) {
     uint32_t n[4] = {0u, 0u, 0u, 0u};   // asked, accepted, refused flat, refused id
-    for (size_t t = gid(); t <= T; t += stride()) {
+    for (size_t t = gid(); t <= T; t += stride<BT>()) {
         split::Verdict v = split::NOT_ASKED;
         if (t < T && select[t] != 0) {
             uint32_t c[4];
@@ -56,26 +55,14 @@ __global__ __launch_bounds__(BT) void k_split_flags(size_t T, uint32_t V, const 
         n[2] += v == split::REFUSED_FLAT;
         n[3] += v == split::REFUSED_ID;
     }
-    __shared__ uint32_t part[BT / 64][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint32_t s = n[k];
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        uint32_t s = 0;
-        for (int w = 0; w < BT / 64; ++w) s += part[w][threadIdx.x];
-        if (s) atomicAdd(&counters[threadIdx.x], s);
-    }
+    block_count<BT>(n, counters);
 }
 
 __global__ __launch_bounds__(BT) void k_split_cells(size_t T, uint32_t V, const float *__restrict__ xyz,
                                                     const uint32_t *__restrict__ cells, const uint32_t *__restrict__ offsets,
                                                     size_t num_new, float *__restrict__ xyz_out, uint32_t *__restrict__ cells_out,
                                                     uint32_t *__restrict__ cell_parent, uint32_t *__restrict__ vertex_parents) {
-    for (size_t t = gid(); t < T; t += stride()) {
+    for (size_t t = gid(); t < T; t += stride<BT>()) {
         uint32_t c[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) c[k] = cells[4 * t + k];
@@ -90,10 +77,7 @@ __global__ __launch_bounds__(BT) void k_split_cells(size_t T, uint32_t V, const 
         float cen[3] = {0.f, 0.f, 0.f};
         if (iso::ids_ok(c, V)) {   // (false only where the caller changed `cells` between the two entries)
             float p[4][3];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int a = 0; a < 3; ++a) p[j][a] = xyz[3 * (size_t)c[j] + a];
+            gather_tet(c, xyz, p);
             split::centroid(p, cen);
         }
         const uint32_t v = V + (uint32_t)k;
@@ -120,7 +104,7 @@ typedef float float4a __attribute__((ext_vector_type(4), aligned(16)));
 __global__ __launch_bounds__(BT) void k_split_copy_rows(size_t rows, size_t V, size_t K, size_t chunks,
                                                         const float *__restrict__ values, float *__restrict__ out, bool vec) {
     const size_t total = rows * chunks;
-    for (size_t idx = gid(); idx < total; idx += stride()) {
+    for (size_t idx = gid(); idx < total; idx += stride<BT>()) {
         const size_t r = idx / chunks, j = idx - r * chunks;
         const size_t d0 = r * (V + K), d1 = d0 + V, s0 = r * V;
         const size_t a = (d0 & ~(size_t)3) + 4 * j;
@@ -199,20 +183,6 @@ __global__ __launch_bounds__(BT) void k_split_new_columns(size_t rows, size_t V,
     }
 }
 
-// stream-ordered temporary, released when the scope is left (also when a launch check throws)
-struct AsyncBytes {
-    char *p = nullptr;
-    hipStream_t s;
-    AsyncBytes(size_t bytes, hipStream_t stream) : s(stream) {
-        if (bytes) TN_HIP(hipMallocAsync((void **)&p, bytes, stream));
-    }
-    ~AsyncBytes() { if (p) (void)hipFreeAsync(p, s); }
-    AsyncBytes(const AsyncBytes &) = delete;
-    AsyncBytes &operator=(const AsyncBytes &) = delete;
-};
-
-inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 }  // namespace
 
 void launch_split_count(size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint8_t *select, uint32_t *offsets,
@@ -222,23 +192,21 @@ void launch_split_count(size_t V, size_t T, const float *xyz, const uint32_t *ce
         TN_HIP(hipMemsetAsync(offsets, 0, sizeof(uint32_t), s));
         return;
     }
-    const size_t n = T + 1;
-    size_t tmp_bytes = 0;
-    TN_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n, rocprim::plus<uint32_t>(), s));
-    const size_t flag_bytes = align256(n * sizeof(uint32_t));
+    const size_t n = T + 1, tmp_bytes = scan_bytes(n, s), flag_bytes = align256(n * sizeof(uint32_t));
     AsyncBytes all(flag_bytes + tmp_bytes, s);   // accepted flags | rocprim's scratch
-    uint32_t *flags = reinterpret_cast<uint32_t *>(all.p);
-    hipLaunchKernelGGL(k_split_flags, dim3(grid_for(n)), dim3(BT), 0, s, T, (uint32_t)V, xyz, cells, select, flags, counters);
+    uint32_t *flags = all.at<uint32_t>();
+    hipLaunchKernelGGL(k_split_flags, dim3(grid_for<BT, SPLIT_BLOCKS>(n)), dim3(BT), 0, s, T, (uint32_t)V, xyz, cells, select, flags,
+                       counters);
     TN_HIP(hipGetLastError());
-    TN_HIP(rocprim::exclusive_scan(all.p + flag_bytes, tmp_bytes, flags, offsets, 0u, n, rocprim::plus<uint32_t>(), s));
+    scan(all.p + flag_bytes, tmp_bytes, flags, offsets, n, s);
 }
 
 void launch_split_emit(size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint32_t *offsets, size_t num_new,
                        float *xyz_out, uint32_t *cells_out, uint32_t *cell_parent, uint32_t *vertex_parents, hipStream_t s) {
     if (V) TN_HIP(hipMemcpyAsync(xyz_out, xyz, 3 * V * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (T == 0) return;
-    hipLaunchKernelGGL(k_split_cells, dim3(grid_for(T)), dim3(BT), 0, s, T, (uint32_t)V, xyz, cells, offsets, num_new, xyz_out,
-                       cells_out, cell_parent, vertex_parents);
+    hipLaunchKernelGGL(k_split_cells, dim3(grid_for<BT, SPLIT_BLOCKS>(T)), dim3(BT), 0, s, T, (uint32_t)V, xyz, cells, offsets,
+                       num_new, xyz_out, cells_out, cell_parent, vertex_parents);
     TN_HIP(hipGetLastError());
 }
 
@@ -249,8 +217,8 @@ void launch_split_vertex_rows(size_t rows, size_t V, size_t K, const float *valu
             TN_HIP(hipMemcpyAsync(out, values, rows * V * sizeof(float), hipMemcpyDeviceToDevice, s));
         } else {
             const size_t chunks = V / 4 + 2;
-            hipLaunchKernelGGL(k_split_copy_rows, dim3(grid_for(rows * chunks)), dim3(BT), 0, s, rows, V, K, chunks, values, out,
-                               ((uintptr_t)out & 15u) == 0);
+            hipLaunchKernelGGL(k_split_copy_rows, dim3(grid_for<BT, SPLIT_BLOCKS>(rows * chunks)), dim3(BT), 0, s, rows, V, K, chunks,
+                               values, out, ((uintptr_t)out & 15u) == 0);
         }
         if (out_vm) {   // rows [0, V) of the shadow are contiguous
             if (values_vm) TN_HIP(hipMemcpyAsync(out_vm, values_vm, rows * V * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -11,14 +11,13 @@
 //   k_verify_orient   lane per tetrahedron: orientation on xyz_old and on the clamped xyz_new; counts flipped and collapsed
 //                     tetrahedra.  The guard's own cross-check: both read 0 wherever the bound applies.
 //
-// All three are grid-stride loops on at most GUARD_BLOCKS blocks.  Counters are reduced per block (shuffle, then LDS) to one
-// atomic per block and counter, and none where the block's sum is 0 (k_refit_records: one same-address atomic per wave
-// serialises).  No read-back, no allocation; everything is enqueued on the caller's stream.
-#include <algorithm>
-
+// All three are grid-stride loops on at most GUARD_BLOCKS blocks (tn_mesh_ops.h).  Counters are reduced per block (shuffle, then
+// LDS) to one atomic per block and counter, and none where the block's sum is 0 (k_refit_records: one same-address atomic per
+// wave serialises).  No read-back, no allocation; everything is enqueued on the caller's stream.
 #include <hip/hip_runtime.h>
 
 #include "tn_build.h"
+#include "tn_mesh_ops.h"
 #include "tn_vertex_guard_core.h"
 
 namespace tn {
@@ -27,19 +26,10 @@ namespace {
 
 constexpr int BT = 256;
 constexpr unsigned GUARD_BLOCKS = 1024;   // grid cap of the three kernels (TetrahedraTracer.VERTEX_GUARD_GRID_LANES = GUARD_BLOCKS * BT)
-inline unsigned grid_for(size_t n) { return (unsigned)std::min<size_t>((n + BT - 1) / BT, GUARD_BLOCKS); }
-__device__ __forceinline__ size_t gid() { return (size_t)blockIdx.x * blockDim.x + threadIdx.x; }
-__device__ __forceinline__ size_t stride() { return (size_t)gridDim.x * BT; }
 
-__device__ __forceinline__ void gather_tet(const uint32_t *c, const float *__restrict__ xyz, float p[4][3]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) p[k][a] = xyz[3 * (size_t)c[k] + a];
-}
-
-// sum of (a, b) over the block -> one atomicAdd per non-zero sum
-__device__ __forceinline__ void block_count(uint32_t a, uint32_t b, uint32_t *out_a, uint32_t *out_b) {
+// sum of (a, b) over the block -> one atomicAdd per non-zero sum.  Not tn_mesh_ops.h's block_count<BT>: on two counters its
+// array form compiles to other instructions (LDS stores and the atomic's address), and these kernels keep theirs.
+__device__ __forceinline__ void block_count2(uint32_t a, uint32_t b, uint32_t *out_a, uint32_t *out_b) {
     __shared__ uint32_t part[BT / 64][2];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -57,7 +47,7 @@ __device__ __forceinline__ void block_count(uint32_t a, uint32_t b, uint32_t *ou
 
 __global__ __launch_bounds__(BT) void k_star_width(size_t T, const uint32_t *__restrict__ cells, const float *__restrict__ xyz,
                                                    float *__restrict__ width, int8_t *__restrict__ orient, uint32_t *star_w) {
-    for (size_t i = gid(); i < T; i += stride()) {
+    for (size_t i = gid(); i < T; i += stride<BT>()) {
         const uint32_t *c = cells + 4 * i;
         float p[4][3];
         gather_tet(c, xyz, p);
@@ -73,7 +63,7 @@ __global__ __launch_bounds__(BT) void k_star_width(size_t T, const uint32_t *__r
 __global__ __launch_bounds__(BT) void k_clamp_vertices(size_t V, const float *__restrict__ xyz_old, float *xyz_new,
                                                        const uint32_t *__restrict__ star_w, float fraction, uint32_t *counters) {
     uint32_t n_clamped = 0, n_frozen = 0;
-    for (size_t v = gid(); v < V; v += stride()) {
+    for (size_t v = gid(); v < V; v += stride<BT>()) {
         float o[3], n[3], out[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) { o[a] = xyz_old[3 * v + a]; n[a] = xyz_new[3 * v + a]; }
@@ -86,13 +76,13 @@ __global__ __launch_bounds__(BT) void k_clamp_vertices(size_t V, const float *__
         n_clamped += kind == guard::CLAMPED;
         n_frozen += kind == guard::FROZEN_MOVED;
     }
-    block_count(n_clamped, n_frozen, counters + 0, counters + 1);
+    block_count2(n_clamped, n_frozen, counters + 0, counters + 1);
 }
 
 __global__ __launch_bounds__(BT) void k_verify_orient(size_t T, const uint32_t *__restrict__ cells, const float *__restrict__ xyz_old,
                                                       const float *__restrict__ xyz_new, uint32_t *counters) {
     uint32_t n_flipped = 0, n_collapsed = 0;
-    for (size_t i = gid(); i < T; i += stride()) {
+    for (size_t i = gid(); i < T; i += stride<BT>()) {
         const uint32_t *c = cells + 4 * i;
         float p[4][3];
         gather_tet(c, xyz_old, p);
@@ -102,7 +92,7 @@ __global__ __launch_bounds__(BT) void k_verify_orient(size_t T, const uint32_t *
         n_flipped += before * after < 0;
         n_collapsed += before != 0 && after == 0;
     }
-    block_count(n_flipped, n_collapsed, counters + 2, counters + 3);
+    block_count2(n_flipped, n_collapsed, counters + 2, counters + 3);
 }
 
 }  // namespace
@@ -111,7 +101,7 @@ void launch_tet_quality(size_t V, size_t T, const uint32_t *cells, const float *
                         hipStream_t s) {
     if (star_width && V) TN_HIP(hipMemsetD32Async((hipDeviceptr_t)star_width, (int)guard::INF_BITS, V, s));
     if (T)
-        hipLaunchKernelGGL(k_star_width, dim3(grid_for(T)), dim3(BT), 0, s, T, cells, xyz, width, orient,
+        hipLaunchKernelGGL(k_star_width, dim3(grid_for<BT, GUARD_BLOCKS>(T)), dim3(BT), 0, s, T, cells, xyz, width, orient,
                            reinterpret_cast<uint32_t *>(star_width));
     TN_HIP(hipGetLastError());
 }
@@ -121,10 +111,10 @@ void launch_limit_vertex_step(size_t V, size_t T, const uint32_t *cells, const f
     TN_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), s));
     launch_tet_quality(V, T, cells, xyz_old, nullptr, nullptr, star_width, s);
     if (V)
-        hipLaunchKernelGGL(k_clamp_vertices, dim3(grid_for(V)), dim3(BT), 0, s, V, xyz_old, xyz_new,
+        hipLaunchKernelGGL(k_clamp_vertices, dim3(grid_for<BT, GUARD_BLOCKS>(V)), dim3(BT), 0, s, V, xyz_old, xyz_new,
                            reinterpret_cast<const uint32_t *>(star_width), fraction, counters);
     if (verify && T)
-        hipLaunchKernelGGL(k_verify_orient, dim3(grid_for(T)), dim3(BT), 0, s, T, cells, xyz_old, xyz_new, counters);
+        hipLaunchKernelGGL(k_verify_orient, dim3(grid_for<BT, GUARD_BLOCKS>(T)), dim3(BT), 0, s, T, cells, xyz_old, xyz_new, counters);
     TN_HIP(hipGetLastError());
 }
 

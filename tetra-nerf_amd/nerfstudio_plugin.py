@@ -230,23 +230,58 @@ def _renderer_for(model, tracer):
     return rd
 
 
+def _accumulate(model, name, counters):
+    """`counters` added to `model.<name>`, an int64 tensor on their device, created by the first call (and again on another
+    device); without a model nothing is kept"""
+    if model is None:
+        return
+    total = getattr(model, name, None)
+    if total is None or total.device != counters.device:
+        total = torch.zeros(4, dtype=torch.int64, device=counters.device)
+        setattr(model, name, total)
+    total += counters
+
+
+def _adopt_mesh(model, tracer, cells, *, vertices=None, occupancy=None):
+    """The model takes the mesh its tracer has just loaded, in the order of DESIGN.md section 4.18.1: (1) `tetrahedra_vertices`
+    (where `vertices` is given; the tracer is re-pointed at it, the storage it borrows), `tetrahedra_cells` and
+    `tetrahedra_occupancy` (where `occupancy` is given) REPLACED under their names, each of its kind (`_set_tensor`), so a state
+    dict keeps its keys; (2) `config.num_tetrahedra_vertices` / `num_tetrahedra_cells` where the config has them; (3) the vertex
+    snapshot refreshed iff the tracer keeps one, the vertex key taken again; (4) the statistics, where the model has any, zeros of
+    the new size.  model None: (3) alone.  Returns the tracer's vertex table."""
+    if model is not None:
+        if vertices is not None:
+            vertices = tracer.tetrahedra_vertices = _set_tensor(model, "tetrahedra_vertices", vertices, model.tetrahedra_vertices)
+        _set_tensor(model, "tetrahedra_cells", cells)
+        if occupancy is not None:
+            _set_tensor(model, "tetrahedra_occupancy", occupancy)
+        cfg = getattr(model, "config", None)
+        if vertices is not None and hasattr(cfg, "num_tetrahedra_vertices"):
+            cfg.num_tetrahedra_vertices = vertices.shape[0]
+        if hasattr(cfg, "num_tetrahedra_cells"):
+            cfg.num_tetrahedra_cells = cells.numel() // 4
+    v = tracer.tetrahedra_vertices
+    if getattr(tracer, "_tn_vertex_snapshot", None) is not None:
+        tracer._tn_vertex_snapshot = v.detach().clone()
+    tracer._tn_vertex_key = (v._version, v.data_ptr())
+    if model is not None and getattr(model, "_tn_tet_stats", None) is not None:     # statistics of cells that no longer exist
+        model_tet_stats(model, reset=True, num_cells=cells.numel() // 4)
+    return v
+
+
 def _monitor_delaunay(tracer, model, above, keep_snapshot):
     """One look at the Delaunay monitor (`config.delaunay_check_every`), and a re-triangulation where
     `config.retriangulate_above` asks for one.  The counters of `tracer.delaunay_check()` on the vertices the tracer follows
     (interior faces, violated, uncertain, violated with an inverted first tetrahedron) accumulate in
     `model._tn_delaunay_counters`, an int64 tensor on the device.  With a threshold the first two are read back -- the ONE host
     synchronisation of the monitor -- and when violated / interior exceeds it `tracer.retriangulate` gives the vertices new cells
-    (blocking: Qhull on the CPU, then a load): the model's `tetrahedra_cells` buffer and, where it has one, its
-    `tetrahedra_occupancy` buffer (carried over conservatively: `remap_tet_values`) are REPLACED by tensors of the new size under
-    their names, so a state dict keeps its keys, and `config.num_tetrahedra_cells`, which sizes both at construction, follows.
-    What is keyed by vertex -- the field, its optimiser state -- does not change.  Returns True after a re-triangulation."""
+    (blocking: Qhull on the CPU, then a load) and the model adopts them (`_adopt_mesh`): `tetrahedra_cells` and, where it has one,
+    its `tetrahedra_occupancy` (carried over conservatively: `remap_tet_values`) are replaced, `_tn_retriangulations` counts the
+    re-triangulation.  What is keyed by vertex -- the field, its optimiser state -- does not change.  keep_snapshot (the caller's
+    vertex_step_fraction is set) decides nothing any more: `_follow_vertices` keeps a snapshot exactly then, and `_adopt_mesh`
+    refreshes the one the tracer keeps.  Returns True after a re-triangulation."""
     counters = tracer.delaunay_check()["counters"]
-    total = getattr(model, "_tn_delaunay_counters", None) if model is not None else None
-    if total is None or total.device != counters.device:
-        total = torch.zeros(4, dtype=torch.int64, device=counters.device)
-        if model is not None:
-            model._tn_delaunay_counters = total
-    total += counters
+    _accumulate(model, "_tn_delaunay_counters", counters)
     if above is None:
         return False
     interior, violated = counters[:2].tolist()
@@ -254,19 +289,9 @@ def _monitor_delaunay(tracer, model, above, keep_snapshot):
         return False
     occupancy = getattr(model, "tetrahedra_occupancy", None) if model is not None else None
     out = tracer.retriangulate(tracer.tetrahedra_vertices, () if occupancy is None else (occupancy.detach(),))
+    _adopt_mesh(model, tracer, out["cells"], occupancy=None if occupancy is None else out["tet_values"][0])
     if model is not None:
-        model.tetrahedra_cells = out["cells"]
-        if occupancy is not None:
-            model.tetrahedra_occupancy = out["tet_values"][0]
-        if hasattr(getattr(model, "config", None), "num_tetrahedra_cells"):
-            model.config.num_tetrahedra_cells = int(out["num_tetrahedra"])
         model._tn_retriangulations = getattr(model, "_tn_retriangulations", 0) + 1
-        if getattr(model, "_tn_tet_stats", None) is not None:     # statistics of cells that no longer exist
-            model_tet_stats(model, reset=True, num_cells=int(out["num_tetrahedra"]))
-    v = tracer.tetrahedra_vertices
-    if keep_snapshot:
-        tracer._tn_vertex_snapshot = v.detach().clone()
-    tracer._tn_vertex_key = (v._version, v.data_ptr())
     return True
 
 
@@ -303,12 +328,7 @@ def _follow_vertices(tracer, model=None, fraction=None, delaunay_check_every=Non
     elif getattr(tracer, "_tn_vertex_key", None) != key:
         if snapshot is not None and snapshot.shape == v.shape:
             counters, _ = tracer.limit_vertex_step(snapshot, v.data, float(fraction))
-            total = getattr(model, "_tn_vertex_step_counters", None) if model is not None else None
-            if total is None or total.device != counters.device:
-                total = torch.zeros(4, dtype=torch.int64, device=counters.device)
-                if model is not None:
-                    model._tn_vertex_step_counters = total
-            total += counters
+            _accumulate(model, "_tn_vertex_step_counters", counters)
         else:
             snapshot = None          # first sight of a tracer someone else loaded: nothing valid to limit against
         tracer.update_vertices(v)
@@ -664,11 +684,12 @@ def densify(model, select=None, *, stats=None, score="error", min_hits=None, occ
     retriangulate: afterwards `tracer.retriangulate` gives the grown vertex table Delaunay cells; the field is per vertex and
     survives, the occupancy goes through remap_tet_values.  This trades the exact preservation for a Delaunay mesh.
 
-    REPLACED under their names, so a state dict keeps its keys: `tetrahedra_vertices`, `tetrahedra_cells`, `tetrahedra_field` (a
-    new nn.Parameter: the old one leaves the field cache, the new one is registered iff the old was, with its vertex-major shadow
-    already installed), `tetrahedra_occupancy` where present, and `config.num_tetrahedra_vertices` / `config.num_tetrahedra_cells`.
-    What `_follow_vertices` remembers of the vertex table is reset.  BLOCKS on the read-back of the number of accepted tetrahedra
-    and on the load.  With nothing accepted nothing is touched.
+    The model adopts the split mesh, and after a re-triangulation that one (`_adopt_mesh`: `tetrahedra_vertices`,
+    `tetrahedra_cells`, `tetrahedra_occupancy` where present and the config sizes replaced, what `_follow_vertices` remembers
+    of the vertex table taken again, the statistics zeroed).  `tetrahedra_field` is REPLACED under its name as well (a new
+    nn.Parameter: the old one leaves the field cache, the new one is registered iff the old was, with its vertex-major shadow
+    already installed).  BLOCKS on the read-back of the number of accepted tetrahedra and on the load.  With nothing accepted
+    nothing is touched.
     Returns {"counters": int32 [4] on the device (asked, accepted, refused flat or inverted, refused for an id), "num_new",
     "num_vertices", "num_cells", "retriangulated"}."""
     from . import optim as tn_optim
@@ -725,14 +746,12 @@ def densify(model, select=None, *, stats=None, score="error", min_hits=None, occ
         if K == 0:
             return result
         parents = out["vertex_parents"]
-        new_field, new_vm = cpp.split_vertex_rows(field.detach(), parents, "mean", values_vm=field_vm, want_vertex_major=True)
         field_moments = _grow_moments(optimizer, field, parents, new_moments, False)
         vertex_moments = _grow_moments(optimizer, vertices, parents, new_moments, True)
-        new_vertices = _set_tensor(model, "tetrahedra_vertices", out["vertices"], vertices)
-        tracer.tetrahedra_vertices = new_vertices                              # the same storage the tracer borrows
-        model.tetrahedra_cells = out["cells"]
-        if occupancy is not None:
-            model.tetrahedra_occupancy = out["tet_values"][0]
+        new_vertices = _adopt_mesh(model, tracer, out["cells"], vertices=out["vertices"],
+                                   occupancy=None if occupancy is None else out["tet_values"][0])
+        # the split's own: the field's new columns, its registration and shadow, the optimiser state of both tensors
+        new_field, new_vm = cpp.split_vertex_rows(field.detach(), parents, "mean", values_vm=field_vm, want_vertex_major=True)
         new_field = _set_tensor(model, "tetrahedra_field", new_field, field)
         cpp.unregister_field(field)
         if registered:
@@ -745,21 +764,9 @@ def densify(model, select=None, *, stats=None, score="error", min_hits=None, occ
                 tn_optim.grow_parameter(optimizer, vertices, new_vertices, *vertex_moments)
         if retriangulate:
             occ = getattr(model, "tetrahedra_occupancy", None)
-            again = tracer.retriangulate(tracer.tetrahedra_vertices.detach(), () if occ is None else (occ.detach(),))
-            tracer.tetrahedra_vertices = new_vertices
-            model.tetrahedra_cells = again["cells"]
-            if occ is not None:
-                model.tetrahedra_occupancy = again["tet_values"][0]
+            again = tracer.retriangulate(new_vertices, () if occ is None else (occ.detach(),))    # (the load borrows the Parameter)
+            _adopt_mesh(model, tracer, again["cells"], occupancy=None if occ is None else again["tet_values"][0])
             result.update(num_cells=int(again["num_tetrahedra"]), retriangulated=True)
-        cfg = getattr(model, "config", None)
-        if hasattr(cfg, "num_tetrahedra_vertices"):
-            cfg.num_tetrahedra_vertices = result["num_vertices"]
-        if hasattr(cfg, "num_tetrahedra_cells"):
-            cfg.num_tetrahedra_cells = result["num_cells"]
-        if getattr(tracer, "_tn_vertex_snapshot", None) is not None:
-            tracer._tn_vertex_snapshot = new_vertices.detach().clone()
-        tracer._tn_vertex_key = (new_vertices._version, new_vertices.data_ptr())
-        if has_stats and getattr(model, "_tn_tet_stats", None) is not None:
-            model_tet_stats(model, reset=True, num_cells=result["num_cells"])
-            result["stats_reset"] = True
+        if has_stats:
+            result["stats_reset"] = getattr(model, "_tn_tet_stats", None) is not None
         return result

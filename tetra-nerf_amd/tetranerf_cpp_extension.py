@@ -193,6 +193,35 @@ class TetrahedraTracer:
         _check(x.dim() == 2 and x.size(0) == self.tetrahedra_vertices.numel() // 3,
                f"{name} must have shape [V, 3] with the V of the loaded mesh")
 
+    def _xyz_or_loaded(self, xyz):
+        """`xyz`, or the loaded vertices where it is None; checked against the loaded mesh"""
+        if xyz is None:
+            xyz = self.tetrahedra_vertices
+            _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
+        self._check_loaded_vertices(xyz, "xyz")
+        return xyz
+
+    def _check_tet_values(self, tet_values, flat):
+        """`tet_values` as a tuple of arrays over the loaded cells on the tracer's device: [T, ...], or float32 [T] where flat"""
+        tet_values, T = tuple(tet_values), self.tetrahedra_cells.numel() // 4
+        for t in tet_values:
+            _check_input(t, "tet_values")
+            ok = t.dim() >= 1 and t.size(0) == T and t.device == self._device
+            _check(ok and (not flat or (t.dtype == torch.float32 and t.dim() == 1)),
+                   f"tet_values must be {'float32 [T]' if flat else '[T, ...]'} arrays over the loaded cells, on the tracer's device")
+        return tet_values
+
+    def _check_rays(self, ray_origins, ray_directions, max_ray_triangles):
+        """(R, M) of a trace: M = max_ray_triangles a power of 2, both ray arrays float32 [..., 3] on the device, as many of each"""
+        M = int(max_ray_triangles)
+        if M <= 0 or (M & (M - 1)) != 0:
+            raise RuntimeError("max_ray_triangles must be a power of 2.")
+        self._check_float_dim3(ray_origins, "ray_origins")
+        self._check_float_dim3(ray_directions, "ray_directions")
+        R = ray_origins.numel() // 3
+        _check(ray_directions.numel() // 3 == R, "ray_origins and ray_directions must have the same number of rays")
+        return R, M
+
     def tet_quality(self, xyz=None):
         """Width and orientation of every loaded tetrahedron on `xyz` (None: the loaded vertices), and the star width of every
         vertex (no reference counterpart; tn_tet_quality, geometry.tet_width_orient / star_width).  xyz: float32 [V, 3] on the
@@ -200,10 +229,7 @@ class TetrahedraTracer:
         tetrahedron over all directions, "orient": int8 [T] -- sign of its signed volume, "star_width": f32 [V] -- the smallest
         width around the vertex, +inf where no tetrahedron names it}.  No synchronisation."""
         with torch.no_grad():
-            if xyz is None:
-                xyz = self.tetrahedra_vertices
-                _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
-            self._check_loaded_vertices(xyz, "xyz")
+            xyz = self._xyz_or_loaded(xyz)
             V, T, dev = xyz.size(0), self.tetrahedra_cells.numel() // 4, self._device
             width = _empty((T,), dtype=torch.float32, device=dev)
             orient = _empty((T,), dtype=torch.int8, device=dev)
@@ -247,10 +273,7 @@ class TetrahedraTracer:
         face_tables()) or None; "tet_violations": uint8 [T], the violated faces of each tetrahedron, or None}.
         Nothing is read back: look at the counters when you would synchronise anyway.  The tracer is not touched."""
         with torch.no_grad():
-            if xyz is None:
-                xyz = self.tetrahedra_vertices
-                _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
-            self._check_loaded_vertices(xyz, "xyz")
+            xyz = self._xyz_or_loaded(xyz)
             V, T, dev = xyz.size(0), self.tetrahedra_cells.numel() // 4, self._device
             counters = _empty((4,), dtype=torch.int32, device=dev)
             state = _empty((int(self._lib.tn_num_faces(self._h)),), dtype=torch.int8, device=dev) if face_state else None
@@ -270,11 +293,7 @@ class TetrahedraTracer:
         with torch.no_grad():
             self._check_loaded_vertices(xyz, "xyz")
             old_cells, V = self.tetrahedra_cells, xyz.size(0)
-            tet_values = tuple(tet_values)
-            for t in tet_values:
-                _check_input(t, "tet_values")
-                _check(t.dtype == torch.float32 and t.dim() == 1 and t.numel() == old_cells.numel() // 4 and t.device == self._device,
-                       "tet_values must be float32 [T] arrays over the loaded cells, on the tracer's device")
+            tet_values = self._check_tet_values(tet_values, flat=True)
             cells = triangulate(xyz).to(torch.int32).contiguous()         # raises on a Qhull failure: nothing touched so far
             carried = [remap_tet_values(old_cells, cells, t, V) for t in tet_values]
             self.load_tetrahedra(xyz, cells, refittable=self._refittable)
@@ -290,10 +309,7 @@ class TetrahedraTracer:
         refine (None: the extraction alone, nothing else runs): a dict with "rounds" (0..8) and either "field" f32 [64, V] and
         "weights" (optionally "mode") -- isosurface_refine on the network whose vertex densities `values` are -- or "density_fn",
         the callback of isosurface_refine_with; the vertices then move along their edges onto that density's level set."""
-        if xyz is None:
-            xyz = self.tetrahedra_vertices
-            _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
-        self._check_loaded_vertices(xyz, "xyz")
+        xyz = self._xyz_or_loaded(xyz)
         surface = isosurface(xyz.detach(), self.tetrahedra_cells.reshape(-1, 4), values, level, tet_mask)
         if refine is None:
             return surface
@@ -322,15 +338,12 @@ class TetrahedraTracer:
             _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
             xyz, cells = xyz.detach().reshape(-1, 3), cells.reshape(-1, 4)
             V, T = xyz.size(0), cells.size(0)
-            vertex_rows, tet_values = tuple(vertex_rows), tuple(tet_values)
+            vertex_rows = tuple(vertex_rows)
             for v in vertex_rows:
                 _check_input(v, "vertex_rows")
                 _check(v.dtype == torch.float32 and v.dim() == 2 and v.size(1) == V and v.device == self._device,
                        "vertex_rows must be float32 [rows, V] arrays over the loaded vertices, on the tracer's device")
-            for t in tet_values:
-                _check_input(t, "tet_values")
-                _check(t.dim() >= 1 and t.size(0) == T and t.device == self._device,
-                       "tet_values must be [T, ...] arrays over the loaded cells, on the tracer's device")
+            tet_values = self._check_tet_values(tet_values, flat=False)
             out = split_tetrahedra(xyz, cells, select)
             if out["num_new"] == 0:
                 out.update(vertices=self.tetrahedra_vertices, cells=self.tetrahedra_cells, vertex_rows=list(vertex_rows),
@@ -352,14 +365,8 @@ class TetrahedraTracer:
         bin_rays (no reference counterpart; per call; for INCOHERENT batches): the library walks the rays in a locality
         order of its own (TN_TRACE_BIN_RAYS; the key is ray_order.ray_keys) and writes every row at the caller's index:
         the same five arrays, bit for bit.  Small batches on the BVH path and chunked calls ignore it (ray_order())."""
-        M = int(max_ray_triangles)
-        if M <= 0 or (M & (M - 1)) != 0:
-            raise RuntimeError("max_ray_triangles must be a power of 2.")
         with torch.no_grad():
-            self._check_float_dim3(ray_origins, "ray_origins")
-            self._check_float_dim3(ray_directions, "ray_directions")
-            R = ray_origins.numel() // 3
-            _check(ray_directions.numel() // 3 == R, "ray_origins and ray_directions must have the same number of rays")
+            R, M = self._check_rays(ray_origins, ray_directions, max_ray_triangles)
             out = _trace_rows(R, M, self._device)
             _lib.check(self._lib.tn_trace_rays_ex(
                 self._h, R, M, _ptr(ray_origins), _ptr(ray_directions), *map(_ptr, out.values()),
@@ -368,14 +375,8 @@ class TetrahedraTracer:
 
     def trace_rays_triangles(self, ray_origins, ray_directions, max_ray_triangles):
         """PyTetrahedraTracer::trace_rays_triangles (py_binding.cpp:78-113): the sorted all-hits list."""
-        M = int(max_ray_triangles)
-        if M <= 0 or (M & (M - 1)) != 0:
-            raise RuntimeError("max_ray_triangles must be a power of 2.")
         with torch.no_grad():
-            self._check_float_dim3(ray_origins, "ray_origins")
-            self._check_float_dim3(ray_directions, "ray_directions")
-            R = ray_origins.numel() // 3
-            _check(ray_directions.numel() // 3 == R, "ray_origins and ray_directions must have the same number of rays")
+            R, M = self._check_rays(ray_origins, ray_directions, max_ray_triangles)
             dev = self._device
             num = _empty((R,), dtype=torch.int32, device=dev)
             vis = _empty((R, M), dtype=torch.int32, device=dev)
