@@ -263,6 +263,42 @@ int tn_split_emit(size_t num_vertices, size_t num_cells, const float *xyz, const
 int tn_split_vertex_rows(size_t rows, size_t num_vertices, size_t num_new, const float *values, const float *values_vm,
                          const uint32_t *vertex_parents, uint32_t new_mode, float *out, float *out_vm, void *stream);
 
+/* Vertex pruning (no reference counterpart: the reference's mesh is its input point cloud for the whole run).  Vertices whose
+ * every tetrahedron is dead, and which lie on no hull face, are removed; the per-vertex arrays are compacted; the kept points get
+ * their cells from the caller's triangulation (csrc/tn_prune.hip, the rule once in csrc/tn_prune_core.h, DESIGN.md section 4.21;
+ * every output is bit-equal to geometry.prune_vertices_statement / geometry.prune_vertex_rows_statement).
+ *   cells u32 [T,4], dead u8 [T] (non-zero = dead), faces u32 [F,3] and face_tets u32 [F,2] (the face table of those cells),
+ *   vertex_select u8 [V] (nullable: every vertex is asked), all on the current device.
+ *   A vertex is NAMED if a row of cells contains it, LIVE if a tetrahedron that is not dead names it (a row with an id >= V counts
+ *   as live for its in-range ids), HULL if it is a vertex of a face with face_tets[f,1] == 0xFFFFFFFF; ids >= V in either table
+ *   are skipped.  An asked vertex is kept because live, else kept because hull, else kept because no tetrahedron names it, else
+ *   removed; a vertex that is not asked is kept.
+ * tn_prune_count / tn_prune_count_tables: offsets u32 [V+1] = exclusive sums of the keep flags, V' last (reading it back is the
+ *   caller's one synchronisation); counters u32 [5], zeroed by the call: asked, removed, kept live, kept hull, kept unreferenced.
+ *   tn_prune_count reads the loaded mesh's own device cells and face tables (num_vertices must be the loaded V);
+ *   tn_prune_count_tables reads the arrays given, on `device`.
+ * tn_prune_emit: given offsets and num_kept = V' (a host value): new_id u32 [V] (offsets[v] for a kept vertex, 0xFFFFFFFF for a
+ *   removed one), kept_ids u32 [num_kept] (the old id of each new vertex, ascending), xyz_out f32 [num_kept,3] = xyz[kept_ids].
+ *   Every store is bounded by the num_kept passed.
+ * tn_prune_vertex_rows: a per-vertex array compacted: out f32 [rows,num_kept] with out[r,j] = values[r,kept_ids[j]] (0 where
+ *   kept_ids[j] >= V).  out_vm f32 [num_kept,rows] (nullable) is the transposition of out, bit-equal to tn_transpose_f32 of it,
+ *   written in the same pass.  values_vm f32 [V,rows] (nullable) is the caller's transposition of values (the vertex-major shadow
+ *   of the field): where given, the kept columns are read from it as rows.  Carries the [64,V] field and both moments of its
+ *   optimiser.
+ * None but tn_prune_count needs a tracer.  All launch on `stream` and read nothing back; the only atomics are the five counters
+ * (one add per block); the count entries take their scratch as one stream-ordered allocation.  V == 0 or num_kept == 0 gives
+ * empties.  Errors (nothing is touched): a null pointer beside a non-zero count; num_vertices >= 2^32 - 1; num_cells >= 2^30;
+ * num_kept > num_vertices; rows == 0; tn_prune_count without a loaded mesh or with another num_vertices. */
+int tn_prune_count(tn_tracer_t tracer, size_t num_vertices, const uint8_t *dead, const uint8_t *vertex_select, uint32_t *offsets,
+                   uint32_t *counters, void *stream);
+int tn_prune_count_tables(int device, size_t num_vertices, size_t num_cells, const uint32_t *cells, size_t num_faces,
+                          const uint32_t *faces, const uint32_t *face_tets, const uint8_t *dead, const uint8_t *vertex_select,
+                          uint32_t *offsets, uint32_t *counters, void *stream);
+int tn_prune_emit(size_t num_vertices, const float *xyz, const uint32_t *offsets, size_t num_kept, uint32_t *new_id,
+                  uint32_t *kept_ids, float *xyz_out, void *stream);
+int tn_prune_vertex_rows(size_t rows, size_t num_vertices, size_t num_kept, const float *values, const float *values_vm,
+                         const uint32_t *kept_ids, float *out, float *out_vm, void *stream);
+
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);
 

@@ -812,6 +812,66 @@ int tn_split_vertex_rows(size_t rows, size_t V, size_t K, const float *values, c
     });
 }
 
+namespace {
+// the size and pointer checks both count entries share (nothing is touched when one fails)
+void check_prune_count(const char *who, size_t V, size_t T, size_t F, const void *cells, const void *faces, const void *face_tets,
+                       const void *dead, const void *offsets, const void *counters) {
+    const std::string w(who);
+    if (V >= 0xFFFFFFFFull) throw tn::Error(w + ": too many vertices (uint32 ids)");
+    if (T >= tn::split::MAX_CELLS) throw tn::Error(w + ": num_cells must be below 2^30");
+    if (F >= 0xFFFFFFFFull) throw tn::Error(w + ": too many faces");
+    if (!offsets || !counters || (T && (!cells || !dead)) || (F && (!faces || !face_tets)))
+        throw tn::Error(w + ": a null pointer beside a non-zero count");
+}
+}  // namespace
+
+int tn_prune_count(tn_tracer_t tracer, size_t V, const uint8_t *dead, const uint8_t *vertex_select, uint32_t *offsets,
+                   uint32_t *counters, void *stream_) {
+    return guarded([&] {
+        tn_tracer *t = checked(tracer);
+        std::lock_guard<std::mutex> lock(t->mu);
+        check_guard_mesh(t, "tn_prune_count", V);
+        const tn::DeviceMesh &m = t->mesh.view;
+        check_prune_count("tn_prune_count", V, m.T, m.F, m.cells, m.faces, m.face_tets, dead, offsets, counters);
+        DeviceGuard g(t->device);
+        tn::launch_prune_count(V, m.T, m.cells, m.F, m.faces, m.face_tets, dead, vertex_select, offsets, counters, (hipStream_t)stream_);
+    });
+}
+
+int tn_prune_count_tables(int device, size_t V, size_t T, const uint32_t *cells, size_t F, const uint32_t *faces,
+                          const uint32_t *face_tets, const uint8_t *dead, const uint8_t *vertex_select, uint32_t *offsets,
+                          uint32_t *counters, void *stream_) {
+    return guarded([&] {
+        check_prune_count("tn_prune_count_tables", V, T, F, cells, faces, face_tets, dead, offsets, counters);
+        DeviceGuard g(device);
+        tn::launch_prune_count(V, T, cells, F, faces, face_tets, dead, vertex_select, offsets, counters, (hipStream_t)stream_);
+    });
+}
+
+int tn_prune_emit(size_t V, const float *xyz, const uint32_t *offsets, size_t num_kept, uint32_t *new_id, uint32_t *kept_ids,
+                  float *xyz_out, void *stream_) {
+    return guarded([&] {
+        if (V >= 0xFFFFFFFFull) throw tn::Error("tn_prune_emit: too many vertices (uint32 ids)");
+        if (num_kept > V) throw tn::Error("tn_prune_emit: num_kept exceeds num_vertices");
+        if ((V && (!xyz || !offsets || !new_id)) || (num_kept && (!kept_ids || !xyz_out)))
+            throw tn::Error("tn_prune_emit: a null pointer beside a non-zero count");
+        tn::launch_prune_emit(V, xyz, offsets, num_kept, new_id, kept_ids, xyz_out, (hipStream_t)stream_);
+    });
+}
+
+int tn_prune_vertex_rows(size_t rows, size_t V, size_t num_kept, const float *values, const float *values_vm, const uint32_t *kept_ids,
+                         float *out, float *out_vm, void *stream_) {
+    return guarded([&] {
+        if (rows == 0) throw tn::Error("tn_prune_vertex_rows: rows must not be 0");
+        if (rows >= 0xFFFFFFFFull) throw tn::Error("tn_prune_vertex_rows: too many rows");
+        if (V >= 0xFFFFFFFFull) throw tn::Error("tn_prune_vertex_rows: too many vertices (uint32 ids)");
+        if (num_kept > V) throw tn::Error("tn_prune_vertex_rows: num_kept exceeds num_vertices");
+        if (num_kept && (!kept_ids || !out || (!values && !values_vm)))
+            throw tn::Error("tn_prune_vertex_rows: a null pointer beside a non-zero count");
+        tn::launch_prune_vertex_rows(rows, V, num_kept, values, values_vm, kept_ids, out, out_vm, (hipStream_t)stream_);
+    });
+}
+
 size_t tn_num_faces(tn_tracer_t tracer) { return tracer && tracer->mesh.loaded ? tracer->mesh.view.F : 0; }
 
 int tn_get_faces(tn_tracer_t tracer, uint32_t *faces_host, uint32_t *face_tets_host) {

@@ -129,4 +129,19 @@ void launch_split_emit(size_t V, size_t T, const float *xyz, const uint32_t *cel
 void launch_split_vertex_rows(size_t rows, size_t V, size_t K, const float *values, const float *values_vm,
                               const uint32_t *vertex_parents, uint32_t new_mode, float *out, float *out_vm, hipStream_t s);
 
+// Vertex pruning (tn_prune.hip; the rule: tn_prune_core.h; no reference counterpart).  An asked vertex is removed iff some
+// tetrahedron names it, every tetrahedron that names it is dead, and it is on no hull face.  All three enqueue on `s` and return:
+// no read-back.  launch_prune_count: offsets u32 [V + 1] = exclusive sums of the keep flags, V' last; counters u32 [5] zeroed and
+// then = asked, removed, kept live, kept hull, kept unreferenced; one stream-ordered allocation.  launch_prune_emit: the caller
+// read V' back and passes it as num_kept, which bounds every store; new_id u32 [V], kept_ids u32 [num_kept], xyz_out f32
+// [num_kept, 3].  launch_prune_vertex_rows: out f32 [rows, V'] = values[:, kept_ids] (an id >= V gives 0), out_vm f32 [V', rows]
+// (nullable) its transposition; values_vm f32 [V, rows] (nullable) = the transposition of values, then read in its place.  The
+// entries (tn_api_tracer.hip) have checked the arguments.
+void launch_prune_count(size_t V, size_t T, const uint32_t *cells, size_t F, const uint32_t *faces, const uint32_t *face_tets,
+                        const uint8_t *dead, const uint8_t *select, uint32_t *offsets, uint32_t *counters, hipStream_t s);
+void launch_prune_emit(size_t V, const float *xyz, const uint32_t *offsets, size_t num_kept, uint32_t *new_id, uint32_t *kept_ids,
+                       float *xyz_out, hipStream_t s);
+void launch_prune_vertex_rows(size_t rows, size_t V, size_t num_kept, const float *values, const float *values_vm,
+                              const uint32_t *kept_ids, float *out, float *out_vm, hipStream_t s);
+
 }  // namespace tn

@@ -658,3 +658,73 @@ def split_vertex_rows_statement(values, vertex_parents, new="mean"):
         a, b, c, d = (values[:, vp[ok, j]] for j in range(4))
         fresh[:, ok] = _mean4_f32(a, b, c, d)
     return np.concatenate([values, fresh], 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Vertex pruning (csrc/tn_prune_core.h, csrc/tn_prune.hip), stated in numpy: asked vertices whose every
+# tetrahedron is dead, and which lie on no hull face, are removed, and every per-vertex array is compacted.  No arithmetic: every
+# array is, bit for bit, what the kernels give.
+
+PRUNE_COUNTER_NAMES = ("asked", "removed", "kept_live", "kept_hull", "kept_unreferenced")
+
+
+def prune_vertices_statement(xyz, cells, dead, faces, face_tets, vertex_select=None):
+    """What tn_prune_count(_tables) + tn_prune_emit compute.  xyz float32 [V, 3], cells integer [T, 4] (any tetrahedron soup),
+    dead [T] (non-zero = dead), faces integer [F, 3] and face_tets integer [F, 2] (a face table of the cells: oracle.build_faces,
+    TetrahedraTracer.face_tables), vertex_select [V] or None (non-zero = asked; None: every vertex): numpy arrays, or torch
+    tensors (copied to the host).  int32 ids are read as the uint32 they stand for (-1 = 0xFFFFFFFF).
+
+    named[v]: some row of cells contains v.  live[v]: a row that is not dead, or that has an id >= V, contains v.  hull[v]: v is a
+    vertex of a face with face_tets[f, 1] == 0xFFFFFFFF.  Ids >= V are skipped in every table.  An asked vertex is kept because
+    live, else because hull, else because it is not named, else removed; a vertex that is not asked is kept.
+
+    Returns a dict of numpy arrays: "vertices" float32 [V', 3] = xyz[kept_ids], "new_id" int32 [V] (the new id, -1 where
+    removed), "kept_ids" int32 [V'] (ascending), "offsets" uint32 [V + 1] (exclusive sums of the keep flags), "counters" uint32
+    [5] = asked, removed, kept live, kept hull, kept unreferenced (PRUNE_COUNTER_NAMES); and the ints "num_kept" = V',
+    "num_removed"."""
+    xyz = np.ascontiguousarray(_to_numpy(xyz), np.float32).reshape(-1, 3)
+    c = _as_index(_to_numpy(cells)).reshape(-1, 4)
+    is_dead = _to_numpy(dead).reshape(-1) != 0
+    f = _as_index(_to_numpy(faces)).reshape(-1, 3)
+    ft = _as_index(_to_numpy(face_tets)).reshape(-1, 2)
+    V, T = len(xyz), len(c)
+    if len(is_dead) != T:
+        raise ValueError("dead must have one entry per row of cells")
+    if len(f) != len(ft):
+        raise ValueError("faces and face_tets must have one row per face")
+    asked = np.ones(V, bool) if vertex_select is None else _to_numpy(vertex_select).reshape(-1) != 0
+    if len(asked) != V:
+        raise ValueError("vertex_select must have one entry per vertex")
+
+    def mark(ids):
+        m = np.zeros(V, bool)
+        ids = ids.reshape(-1)
+        m[ids[ids < V]] = True
+        return m
+
+    named = mark(c)
+    live = mark(c[~is_dead | (c >= V).any(1)])
+    hull = mark(f[ft[:, 1] == EMPTY])
+    removed = asked & ~live & ~hull & named
+    keep = ~removed
+    offsets = np.concatenate([[0], np.cumsum(keep)]).astype(np.uint32)
+    kept_ids = np.nonzero(keep)[0]
+    new_id = np.full(V, -1, np.int64)
+    new_id[kept_ids] = np.arange(len(kept_ids))
+    counters = np.array([asked.sum(), removed.sum(), (asked & live).sum(), (asked & ~live & hull).sum(),
+                         (asked & ~live & ~hull & ~named).sum()], np.uint32)
+    return {"vertices": np.ascontiguousarray(xyz[kept_ids]), "new_id": new_id.astype(np.int32), "kept_ids": kept_ids.astype(np.int32),
+            "offsets": offsets, "counters": counters, "num_kept": len(kept_ids), "num_removed": int(removed.sum())}
+
+
+def prune_vertex_rows_statement(values, kept_ids):
+    """What tn_prune_vertex_rows computes.  values float32 [rows, V], kept_ids integer [V'] -> float32 [rows, V']:
+    out[r, j] = values[r, kept_ids[j]], 0 where kept_ids[j] >= V."""
+    values = np.ascontiguousarray(_to_numpy(values), np.float32)
+    if values.ndim != 2 or values.shape[0] == 0:
+        raise ValueError("values must be [rows, V] with rows > 0")
+    ids = _as_index(_to_numpy(kept_ids)).reshape(-1)
+    ok = ids < values.shape[1]
+    out = np.zeros((values.shape[0], len(ids)), np.float32)
+    out[:, ok] = values[:, ids[ok]]
+    return out

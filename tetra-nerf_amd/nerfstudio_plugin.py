@@ -770,3 +770,110 @@ def densify(model, select=None, *, stats=None, score="error", min_hits=None, occ
         if has_stats:
             result["stats_reset"] = getattr(model, "_tn_tet_stats", None) is not None
         return result
+
+
+def _prune_moments(optimizer, old, kept_ids, vertex_major):
+    """(exp_avg, exp_avg_sq) of `old` compacted to the kept vertices, or (None, None) where the optimiser holds none for it.
+    vertex_major: the moments are [V, ...] (the vertex table's) and are carried in plain torch; else [rows, V] (the field's)."""
+    from . import tetranerf_cpp_extension as cpp
+
+    state = optimizer.state.get(old) if optimizer is not None else None
+    if not state or "exp_avg" not in state:
+        return None, None
+    if vertex_major:
+        return tuple(state[k][kept_ids.long()].contiguous() for k in ("exp_avg", "exp_avg_sq"))
+    return tuple(cpp.prune_vertex_rows(state[k], kept_ids) for k in ("exp_avg", "exp_avg_sq"))
+
+
+def prune(model, dead=None, *, stats=None, max_hits=0, occupancy_below=None, vertex_select=None, max_removed=None, optimizer=None):
+    """Lower the resolution of a TetrahedraNerf's mesh where nothing is left: the vertices that only dead tetrahedra name, and that
+    lie on no hull face, are removed and the rest get their Delaunay cells (`tracer.remove_vertices`).
+    The field, its optimiser's moments and the vertex table are compacted; the occupancy goes through remap_tet_values.  An
+    explicit call, like densify, not a config switch.
+
+    dead: bool / uint8 [T] over the model's cells, or None: then the AND of the conditions given -- hits <= max_hits from
+    `stats` (i64 [T, 3], cpp.tet_stats_accumulate, or True: the model's own) and occupancy < occupancy_below (needs the
+    `tetrahedra_occupancy` buffer); ValueError if none is.  vertex_select: bool / uint8 [V], only these vertices are asked.
+    max_removed: of the removable vertices, the max_removed with the LOWEST ids are removed (a second count with a cut
+    vertex_select).  optimizer: the optimiser that holds `tetrahedra_field` (and `tetrahedra_vertices`, where that is
+    optimised): its state moves through optim.grow_parameter -- step kept, the moments of every kept vertex kept bit for bit.
+    Without it the caller re-creates its optimiser.
+
+    The model adopts the pruned mesh (`_adopt_mesh`: `tetrahedra_vertices`, `tetrahedra_cells`, `tetrahedra_occupancy` where
+    present and the config sizes replaced, what `_follow_vertices` remembers of the vertex table taken again, the statistics
+    zeroed).  `tetrahedra_field` is REPLACED under its name (a new nn.Parameter: the old one leaves the field cache, the new one is
+    registered iff the old was, with its vertex-major shadow already installed).  BLOCKS on the read-back of V' (twice with
+    max_removed), the triangulation and the load.  With nothing removed nothing is touched.
+    Returns {"counters": int32 [5] on the device (asked, removed, kept live, kept hull, kept unreferenced), "num_removed",
+    "num_vertices", "num_cells"} and "stats_reset" where the model has statistics."""
+    from . import optim as tn_optim
+    from . import tetranerf_cpp_extension as cpp
+
+    tracer = model.get_tetrahedra_tracer()
+    if not getattr(tracer, "supports_prune", False):
+        raise RuntimeError("prune needs a tracer with remove_vertices (tetranerf_cpp_extension.TetrahedraTracer)")
+    field, vertices = model.tetrahedra_field, model.tetrahedra_vertices
+    occupancy = getattr(model, "tetrahedra_occupancy", None)
+    T, V, dev = tracer.tetrahedra_cells.numel() // 4, vertices.shape[0], tracer.device
+    if stats is True:
+        stats = getattr(model, "_tn_tet_stats", None)
+        if stats is None:
+            raise ValueError("prune: stats=True needs the model's own statistics (config.densify_stats and at least one training step)")
+    if stats is not None and (stats.dim() != 2 or tuple(stats.shape) != (T, 3) or stats.dtype != torch.int64):
+        raise ValueError("prune: stats must be i64 [T, 3] over the model's current cells")
+    has_stats = stats is not None or getattr(model, "_tn_tet_stats", None) is not None
+    with torch.no_grad():
+        if dead is None:
+            if stats is None and occupancy_below is None:
+                raise ValueError("prune: give `dead`, stats, or occupancy_below")
+            mask = torch.ones(T, dtype=torch.bool, device=dev)
+            if stats is not None:
+                mask &= stats[:, 0].to(dev) <= int(max_hits)
+            if occupancy_below is not None:
+                if occupancy is None:
+                    raise ValueError("prune: occupancy_below needs the model's tetrahedra_occupancy buffer")
+                mask &= occupancy.detach() < float(occupancy_below)
+        else:
+            mask = dead.to(dev).reshape(-1) != 0
+            if mask.numel() != T:
+                raise ValueError("prune: dead must have one entry per tetrahedron")
+        mask = mask.contiguous()
+        select = None
+        if vertex_select is not None:
+            select = (vertex_select.to(dev).reshape(-1) != 0).contiguous()
+            if select.numel() != V:
+                raise ValueError("prune: vertex_select must have one entry per vertex")
+        if max_removed is not None:
+            offsets, _ = tracer.prune_count(mask, select)
+            removable = torch.nonzero(offsets[1:] == offsets[:-1]).reshape(-1)[:max(0, int(max_removed))]
+            cut = torch.zeros(V, dtype=torch.bool, device=dev)
+            cut[removable] = True
+            select = cut
+        registered = cpp.field_is_registered(field)
+        field_vm = cpp.field_vertex_major(field) if registered else None        # (before the load below forgets it)
+        out = tracer.remove_vertices(mask, select, tet_values=() if occupancy is None else (occupancy.detach(),))
+        R = int(out["num_removed"])
+        result = {"counters": out["counters"], "num_removed": R, "num_vertices": V - R, "num_cells": int(out["num_tetrahedra"])}
+        if has_stats:
+            result["stats_reset"] = False
+        if R == 0:
+            return result
+        kept = out["kept_ids"]
+        field_moments = _prune_moments(optimizer, field, kept, False)
+        vertex_moments = _prune_moments(optimizer, vertices, kept, True)
+        new_vertices = _adopt_mesh(model, tracer, out["cells"], vertices=out["vertices"],
+                                   occupancy=None if occupancy is None else out["tet_values"][0])
+        new_field, new_vm = cpp.prune_vertex_rows(field.detach(), kept, values_vm=field_vm, want_vertex_major=True)
+        new_field = _set_tensor(model, "tetrahedra_field", new_field, field)
+        cpp.unregister_field(field)
+        if registered:
+            cpp.register_field(new_field)
+            cpp.install_field_shadow(new_field, new_vm)
+        if optimizer is not None:
+            if field_moments[0] is not None or any(p is field for g in optimizer.param_groups for p in g["params"]):
+                tn_optim.grow_parameter(optimizer, field, new_field, *field_moments)
+            if any(p is vertices for g in optimizer.param_groups for p in g["params"]):
+                tn_optim.grow_parameter(optimizer, vertices, new_vertices, *vertex_moments)
+        if has_stats:
+            result["stats_reset"] = getattr(model, "_tn_tet_stats", None) is not None
+        return result

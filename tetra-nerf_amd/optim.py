@@ -249,10 +249,10 @@ class FusedRAdam(torch.optim.Optimizer):
 
 
 def grow_parameter(optimizer, old, new, exp_avg=None, exp_avg_sq=None):
-    """Replace the parameter `old` of `optimizer` by `new` -- the same quantity on a mesh with more vertices (cpp.split_vertex_rows)
-    -- in its parameter group, and move its state: `step` is kept (the bias corrections and the rectification go on where they
-    were), `exp_avg` / `exp_avg_sq` are the tensors given (the old moments carried by split_vertex_rows) or zeros of the new
-    shape.  A parameter that has not been stepped yet has no state, and gets none.  Works on torch.optim.RAdam and on FusedRAdam,
+    """Replace the parameter `old` of `optimizer` by `new` -- the same quantity on a mesh with other vertices, more after a split
+    (cpp.split_vertex_rows), fewer after a prune (cpp.prune_vertex_rows); any shape -- in its parameter group, and move its
+    state: `step` is kept (the bias corrections and the rectification go on where they were), `exp_avg` / `exp_avg_sq` are the
+    tensors given (the old moments carried to the new vertices) or zeros of the new shape.  A parameter that has not been stepped yet has no state, and gets none.  Works on torch.optim.RAdam and on FusedRAdam,
     whose state layouts are the same: the state_dict of either still loads into the other.  Raises ValueError if `old` is not a
     parameter of the optimiser, or a moment has not the new parameter's shape, dtype and device.  Returns `new`."""
     group = next((g for g in optimizer.param_groups if any(p is old for p in g["params"])), None)

@@ -355,6 +355,67 @@ class TetrahedraTracer:
             self.load_tetrahedra(out["vertices"], out["cells"], refittable=self._refittable)
             return out
 
+    supports_prune = True
+    PRUNE_GRID_LANES = 1024 * 256            # lanes of the prune's kernels at their grid cap (tn_prune.hip: PRUNE_BLOCKS * BT)
+
+    def prune_count(self, dead, vertex_select=None):
+        """The first half of remove_vertices, alone: tn_prune_count on the tracer's own cells and face tables (prune_vertices'
+        rule).  dead: uint8 / bool [T]; vertex_select: uint8 / bool [V] or None.  Returns (offsets i32 [V + 1] -- vertex v is
+        removed iff offsets[v + 1] == offsets[v], V' = offsets[V] --, counters i32 [5]: asked, removed, kept live, kept hull,
+        kept unreferenced), both on the device.  No synchronisation; the tracer is not touched."""
+        with torch.no_grad():
+            xyz = self.tetrahedra_vertices
+            _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
+            V, T, dev = xyz.numel() // 3, self.tetrahedra_cells.numel() // 4, self._device
+            _check_prune_masks(dead, vertex_select, T, V, dev)
+            with _on(dev):
+                offsets = _empty((V + 1,), dtype=torch.int32, device=dev)
+                counters = _empty((5,), dtype=torch.int32, device=dev)
+                _lib.check(self._lib.tn_prune_count(self._h, V, _ptr(dead), _ptr(vertex_select), _ptr(offsets), _ptr(counters),
+                                                    _stream(dev)))
+            return offsets, counters
+
+    def remove_vertices(self, dead, vertex_select=None, vertex_rows=(), tet_values=()):
+        """Remove the vertices of the LOADED mesh that only dead tetrahedra name and that lie on no hull face, and load the
+        Delaunay cells of the rest: tn_prune_count on the tracer's own cells and face tables, tn_prune_emit (prune_vertices'
+        rule), cells = triangulate(kept points) -- Qhull, on the CPU --, every array of `vertex_rows` (f32 [rows, V]: the field,
+        its optimiser's moments) carried by prune_vertex_rows, every array of `tet_values` (float32 [T] of values >= 0 on the
+        loaded cells: the occupancy) carried by remap_tet_values(old cells, kept_ids[new cells]), then load_tetrahedra(kept
+        points, new cells, refittable=what this tracer was loaded with).  dead: uint8 / bool [T]; vertex_select: uint8 / bool [V]
+        or None.  Every hull-face vertex is kept, so the convex hull -- and with it the traced domain -- is unchanged wherever
+        the loaded cells triangulate the convex hull of their points, as the reference's meshes do; it is not once moved
+        vertices have bent the hull.
+        Returns {"vertices": f32 [V', 3], "cells": i32 [T', 4] (both borrowed by the tracer from now on), "new_id", "kept_ids",
+        "counters", "num_removed", "vertex_rows", "tet_values" (the carried arrays in the order given), "num_tetrahedra": T'}.
+        With nothing removed the tracer is not touched and the inputs come back as they are; if the triangulation fails the
+        tracer stays as it was.  BLOCKS on the read-back of V', the triangulation and the load.  The field cache is
+        invalidated, as by every load."""
+        with torch.no_grad():
+            xyz, cells = self.tetrahedra_vertices, self.tetrahedra_cells
+            _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
+            xyz, old_cells = xyz.detach().reshape(-1, 3), cells.reshape(-1, 4)
+            V, T, dev = xyz.size(0), old_cells.size(0), self._device
+            vertex_rows = tuple(vertex_rows)
+            for v in vertex_rows:
+                _check_input(v, "vertex_rows")
+                _check(v.dtype == torch.float32 and v.dim() == 2 and v.size(1) == V and v.device == dev,
+                       "vertex_rows must be float32 [rows, V] arrays over the loaded vertices, on the tracer's device")
+            tet_values = self._check_tet_values(tet_values, flat=True)
+            offsets, counters = self.prune_count(dead, vertex_select)
+            with _on(dev):
+                out = _prune_emit(xyz, offsets, counters)
+            if out["num_removed"] == 0:
+                out.update(vertices=self.tetrahedra_vertices, cells=self.tetrahedra_cells, vertex_rows=list(vertex_rows),
+                           tet_values=list(tet_values), num_tetrahedra=T)
+                return out
+            new_cells = triangulate(out["vertices"]).to(torch.int32).contiguous()   # raises on a Qhull failure: nothing touched so far
+            in_old_ids = out["kept_ids"][new_cells.long()].contiguous()
+            out["vertex_rows"] = [prune_vertex_rows(v.detach(), out["kept_ids"]) for v in vertex_rows]
+            out["tet_values"] = [remap_tet_values(old_cells, in_old_ids, t.detach(), V) for t in tet_values]
+            self.load_tetrahedra(out["vertices"], new_cells, refittable=self._refittable)
+            out.update(cells=new_cells, num_tetrahedra=new_cells.size(0))
+            return out
+
     supports_compact_rows = True
     supports_bin_rays = True
 
@@ -1347,6 +1408,92 @@ def split_vertex_rows(values, vertex_parents, new="mean", values_vm=None, want_v
         out_vm = _empty((V + K, rows), dtype=torch.float32, device=dev) if want_vertex_major else None
         _lib.check(_lib.load().tn_split_vertex_rows(rows, V, K, _ptr(values), _ptr(values_vm), _ptr(vertex_parents), SPLIT_NEW_MODES[new],
                                                     _ptr(out), _ptr(out_vm), _stream(dev)))
+    return (out, out_vm) if want_vertex_major else out
+
+
+def _check_prune_masks(dead, vertex_select, T, V, dev):
+    _check_input(dead, "dead")
+    _check(dead.dtype in (torch.uint8, torch.bool) and dead.numel() == T and dead.device == dev,
+           "dead must be uint8 or bool [num_cells] on the device of the mesh")
+    if vertex_select is not None:
+        _check_input(vertex_select, "vertex_select")
+        _check(vertex_select.dtype in (torch.uint8, torch.bool) and vertex_select.numel() == V and vertex_select.device == dev,
+               "vertex_select must be uint8 or bool [num_vertices] on the device of the mesh")
+
+
+def _prune_emit(xyz, offsets, counters):
+    """The read-back of V' and tn_prune_emit: prune_vertices' dict (the inputs themselves where nothing is removed)"""
+    V, dev = xyz.size(0), xyz.device
+    Vp = int(offsets[V].item())                                                 # the read-back
+    out = {"offsets": offsets, "counters": counters, "num_kept": Vp, "num_removed": V - Vp}
+    if Vp == V:
+        ids = torch.arange(V, dtype=torch.int32, device=dev)
+        out.update(vertices=xyz, new_id=ids, kept_ids=ids)
+        return out
+    vertices = _empty((Vp, 3), dtype=torch.float32, device=dev)
+    new_id = _empty((V,), dtype=torch.int32, device=dev)
+    kept_ids = _empty((Vp,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().tn_prune_emit(V, _ptr(xyz), _ptr(offsets), Vp, _ptr(new_id), _ptr(kept_ids), _ptr(vertices), _stream(dev)))
+    out.update(vertices=vertices, new_id=new_id, kept_ids=kept_ids)
+    return out
+
+
+def prune_vertices(xyz, cells, dead, faces, face_tets, vertex_select=None):
+    """Remove the vertices that only dead tetrahedra name and that lie on no hull face (no reference counterpart: the reference's
+    mesh is its input point cloud for the whole run; tn_prune_count_tables + tn_prune_emit; statement:
+    geometry.prune_vertices_statement, bit for bit; the rule: DESIGN.md section 4.21).  xyz f32 [V, 3], cells i32 [T, 4] (any
+    tetrahedron soup), dead uint8 / bool [T] (non-zero = dead), faces i32 [F, 3] and face_tets i32 [F, 2] (the cells' face table,
+    -1 = no second tetrahedron: a hull face), vertex_select uint8 / bool [V] or None (only these vertices are asked), all on one
+    device.  An asked vertex is kept because a tetrahedron that is not dead (or that has an id outside [0, V)) names it, else
+    because it is on a hull face, else because no tetrahedron names it; otherwise it is removed.
+    Returns {"vertices": f32 [V', 3] = xyz[kept_ids], "new_id": i32 [V] (-1 where removed), "kept_ids": i32 [V'] (ascending:
+    prune_vertex_rows carries a per-vertex array), "offsets": i32 [V + 1], "counters": i32 [5] on the device -- asked, removed,
+    kept live, kept hull, kept unreferenced --, "num_kept": V', "num_removed"}.  The cells of the kept points are the caller's
+    (triangulate; TetrahedraTracer.remove_vertices).  BLOCKS on one small read-back: V' between the two entries (it sizes the
+    outputs).  With nothing removed the second entry is not called: "vertices" is the input itself."""
+    for x, name in ((xyz, "xyz"), (cells, "cells"), (faces, "faces"), (face_tets, "face_tets")):
+        _check_input(x, name)
+    dev = xyz.device
+    _check(xyz.dtype == torch.float32 and xyz.dim() == 2 and xyz.size(1) == 3, "xyz must be f32 [V, 3]")
+    _check(cells.dtype == torch.int32 and cells.dim() == 2 and cells.size(1) == 4 and cells.device == dev,
+           "cells must be int32 [num_cells, 4] on the device of xyz")
+    _check(faces.dtype == torch.int32 and faces.dim() == 2 and faces.size(1) == 3 and faces.device == dev,
+           "faces must be int32 [num_faces, 3] on the device of xyz")
+    _check(face_tets.dtype == torch.int32 and tuple(face_tets.shape) == (faces.size(0), 2) and face_tets.device == dev,
+           "face_tets must be int32 [num_faces, 2] on the device of xyz")
+    V, T, F = xyz.size(0), cells.size(0), faces.size(0)
+    _check_prune_masks(dead, vertex_select, T, V, dev)
+    with torch.no_grad(), _on(dev):
+        offsets = _empty((V + 1,), dtype=torch.int32, device=dev)
+        counters = _empty((5,), dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().tn_prune_count_tables(dev.index or 0, V, T, _ptr(cells), F, _ptr(faces), _ptr(face_tets), _ptr(dead),
+                                                     _ptr(vertex_select), _ptr(offsets), _ptr(counters), _stream(dev)))
+        return _prune_emit(xyz, offsets, counters)
+
+
+def prune_vertex_rows(values, kept_ids, values_vm=None, want_vertex_major=False):
+    """A per-vertex array compacted to the kept vertices of a prune (tn_prune_vertex_rows; statement:
+    geometry.prune_vertex_rows_statement, bit for bit).  values f32 [rows, V] (the [64, V] field, a moment of its optimiser),
+    kept_ids i32 [V'] (prune_vertices') -> f32 [rows, V'] = values[:, kept_ids].  values_vm f32 [V, rows] (optional): the caller's
+    vertex-major shadow of `values` (field_vertex_major); the kept columns are then read from it as whole rows.
+    want_vertex_major: also return the shadow f32 [V', rows] of the result, written in the same pass and bit-equal to its
+    transposition: (out, out_vm).  Caller's stream, no host synchronisation."""
+    for x, name in ((values, "values"), (kept_ids, "kept_ids")):
+        _check_input(x, name)
+    dev = values.device
+    _check(values.dtype == torch.float32 and values.dim() == 2 and values.size(0) > 0, "values must be f32 [rows, V] with rows > 0")
+    _check(kept_ids.dtype == torch.int32 and kept_ids.dim() == 1 and kept_ids.device == dev, "kept_ids must be int32 [V'] on the device of values")
+    rows, V, Vp = values.size(0), values.size(1), kept_ids.size(0)
+    _check(Vp <= V, "kept_ids must not be longer than the rows of values")
+    if values_vm is not None:
+        _check_input(values_vm, "values_vm")
+        _check(values_vm.dtype == torch.float32 and tuple(values_vm.shape) == (V, rows) and values_vm.device == dev,
+               "values_vm must be f32 [V, rows] on the device of values")
+    with torch.no_grad(), _on(dev):
+        out = _empty((rows, Vp), dtype=torch.float32, device=dev)
+        out_vm = _empty((Vp, rows), dtype=torch.float32, device=dev) if want_vertex_major else None
+        _lib.check(_lib.load().tn_prune_vertex_rows(rows, V, Vp, _ptr(values), _ptr(values_vm), _ptr(kept_ids), _ptr(out), _ptr(out_vm),
+                                                    _stream(dev)))
     return (out, out_vm) if want_vertex_major else out
 
 
