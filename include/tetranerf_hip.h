@@ -299,6 +299,49 @@ int tn_prune_emit(size_t num_vertices, const float *xyz, const uint32_t *offsets
 int tn_prune_vertex_rows(size_t rows, size_t num_vertices, size_t num_kept, const float *values, const float *values_vm,
                          const uint32_t *kept_ids, float *out, float *out_vm, void *stream);
 
+/* Edge split (no reference counterpart: the reference's mesh is its input point cloud for the whole run).  Selected edges are
+ * bisected at their midpoints together with every tetrahedron around them: the standard refinement, which halves the edge and the
+ * volumes, needs no hanging node and keeps the hull and every other face of the ring (csrc/tn_edge_split.hip, the rule once in
+ * csrc/tn_edge_split_core.h; every output is bit-equal to geometry.split_edges_statement).
+ *   xyz f32 [V,3], cells u32 [T,4], select u8 [T] (non-zero = asked), faces u32 [F,3] and face_tets u32 [F,2] (the face table of
+ *   those cells; a hull face has face_tets[f,1] == 0xFFFFFFFF), all on the current device.
+ *   An EDGE is the sorted id pair (lo, hi), key = lo << 32 | hi; its squared length is (dx dx + dy dy) + dz dz of d = p[hi] - p[lo]
+ *   in fp32, one rounding per operation, no fused multiply-add.  Edge e beats f iff it is longer, or as long with the smaller key.
+ *   An asked tetrahedron whose ids are < V and whose stored orientation s (as tn_tet_quality evaluates it, 0 also for NaN) is not 0
+ *   nominates its best edge; the CANDIDATES are the distinct nominated edges.  The ring of a candidate is every row that holds
+ *   both its ids; the winner of a row is the best candidate among its six edges.  A candidate is refused, in this precedence, for
+ *   an id >= V in a ring row; for lying on a hull face; because some ring row's winner is another edge; because a ring row has
+ *   orientation 0 or one of its two children has not the row's orientation.  Otherwise it is ACCEPTED: accepted edges share no row.
+ *   Accepted edges are ranked j in ascending key order; the new vertex V + j is ((p_lo + p_hi) + (p_lo + p_hi)) * 0.25f per
+ *   coordinate and vertex_parents[j] = (lo, hi, lo, hi), so tn_split_vertex_rows carries the per-vertex arrays.  A bisected row t,
+ *   with k = the bisected rows below it: child 0 (the slot holding hi replaced) overwrites row t, child 1 (the slot holding lo
+ *   replaced) is row T + k; the other slots keep their stored order.
+ * tn_edge_split_count / tn_edge_split_count_tables: tet_offsets u32 [T+1] = exclusive sums of the bisected flags; tet_edge u32 [T]
+ *   = the rank j of the row's accepted edge, 0xFFFFFFFF for a row that is not bisected; bisected u8 [T]; edge_vertices u32 [T,2],
+ *   of which the first K_v rows are written; counters u32 [10], zeroed by the call: asked, asked refused for an id, asked refused
+ *   flat, candidates, candidates refused id / hull / lost / flat, accepted edges K_v, bisected tetrahedra K_t (reading them back is
+ *   the caller's one synchronisation).  tn_edge_split_count reads the loaded mesh's own device cells and face tables (num_vertices
+ *   must be the loaded V; xyz may be any positions of those vertices); tn_edge_split_count_tables reads the arrays given, on
+ *   `device`.
+ * tn_edge_split_emit: given those arrays and num_new = K_v, num_rows = K_t (host values): xyz_out f32 [V+num_new,3], cells_out u32
+ *   [T+num_rows,4], cell_parent u32 [T+num_rows] (the row itself below T, the parent for an appended row), vertex_parents u32
+ *   [num_new,4].  Every store is bounded by the two counts passed: a caller who changed the inputs between the two entries gets a
+ *   wrong mesh, never a write outside its buffers.
+ * Only tn_edge_split_count needs a tracer.  All launch on `stream` and read nothing back; the atomics are the ten counters (one add
+ *   per block) and or-ed flag words, so no result depends on an order; the count entries take their scratch as one stream-ordered
+ *   allocation.  T == 0 gives empties.  Errors (nothing is touched): a null pointer beside a non-zero count; num_new or num_rows >
+ *   num_cells; num_vertices + num_new >= 2^32 - 1; num_cells + num_rows >= 2^30; num_faces >= 2^32 - 1; tn_edge_split_count without
+ *   a loaded mesh or with another num_vertices. */
+int tn_edge_split_count_tables(int device, size_t num_vertices, size_t num_cells, const float *xyz, const uint32_t *cells,
+                               const uint8_t *select, size_t num_faces, const uint32_t *faces, const uint32_t *face_tets,
+                               uint32_t *tet_offsets, uint32_t *tet_edge, uint8_t *bisected, uint32_t *edge_vertices,
+                               uint32_t *counters, void *stream);
+int tn_edge_split_count(tn_tracer_t tracer, size_t num_vertices, const float *xyz, const uint8_t *select, uint32_t *tet_offsets,
+                        uint32_t *tet_edge, uint8_t *bisected, uint32_t *edge_vertices, uint32_t *counters, void *stream);
+int tn_edge_split_emit(size_t num_vertices, size_t num_cells, const float *xyz, const uint32_t *cells, const uint32_t *tet_offsets,
+                       const uint32_t *tet_edge, const uint32_t *edge_vertices, size_t num_new, size_t num_rows, float *xyz_out,
+                       uint32_t *cells_out, uint32_t *cell_parent, uint32_t *vertex_parents, void *stream);
+
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);
 

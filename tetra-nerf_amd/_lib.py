@@ -41,6 +41,7 @@ SYMBOLS = (
     "tn_split_count", "tn_split_emit", "tn_split_vertex_rows",   # the 1 -> 4 tetrahedron split: the reference never changes its mesh
     "tn_tet_stats_accumulate",                     # per-tetrahedron training statistics: what a densification policy selects by
     "tn_prune_count", "tn_prune_count_tables", "tn_prune_emit", "tn_prune_vertex_rows",   # vertex pruning: the reference never changes its mesh
+    "tn_edge_split_count", "tn_edge_split_count_tables", "tn_edge_split_emit",   # edge bisection with the whole ring: likewise
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -89,6 +90,9 @@ def load():
     lib.tn_prune_count_tables.argtypes = [i32, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_prune_emit.argtypes = [sz, vp, vp, sz, vp, vp, vp, vp]
     lib.tn_prune_vertex_rows.argtypes = [sz, sz, sz, vp, vp, vp, vp, vp, vp]
+    lib.tn_edge_split_count_tables.argtypes = [i32, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.tn_edge_split_count.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.tn_edge_split_emit.argtypes = [sz, sz, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     lib.tn_tet_stats_accumulate.argtypes = [u32, sz, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_refit_table_bytes.restype = sz
     lib.tn_refit_table_bytes.argtypes = [vp]

@@ -12,6 +12,7 @@
 #include "tn_isosurface_core.h"
 #include "tn_kernels.h"
 #include "tn_split_core.h"
+#include "tn_edge_split_core.h"
 
 using tn::check_loaded;
 using tn::check_pow2_M;
@@ -869,6 +870,64 @@ int tn_prune_vertex_rows(size_t rows, size_t V, size_t num_kept, const float *va
         if (num_kept && (!kept_ids || !out || (!values && !values_vm)))
             throw tn::Error("tn_prune_vertex_rows: a null pointer beside a non-zero count");
         tn::launch_prune_vertex_rows(rows, V, num_kept, values, values_vm, kept_ids, out, out_vm, (hipStream_t)stream_);
+    });
+}
+
+namespace {
+// the checks both count entries of the edge split share (nothing is touched when one fails)
+void check_edge_split_count(const char *who, size_t V, size_t T, size_t F, const void *xyz, const void *cells, const void *select,
+                            const void *faces, const void *face_tets, const void *tet_offsets, const void *tet_edge,
+                            const void *bisected, const void *edge_vertices, const void *counters) {
+    const std::string w(who);
+    if (V >= 0xFFFFFFFFull) throw tn::Error(w + ": too many vertices (uint32 ids)");
+    if (T >= tn::esplit::MAX_CELLS) throw tn::Error(w + ": num_cells must be below 2^30");
+    if (F >= 0xFFFFFFFFull) throw tn::Error(w + ": too many faces");
+    if (!tet_offsets || !counters || (T && (!cells || !select || !tet_edge || !bisected || !edge_vertices)) || (T && V && !xyz) ||
+        (F && (!faces || !face_tets)))
+        throw tn::Error(w + ": a null pointer beside a non-zero count");
+}
+}  // namespace
+
+int tn_edge_split_count_tables(int device, size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint8_t *select,
+                               size_t F, const uint32_t *faces, const uint32_t *face_tets, uint32_t *tet_offsets, uint32_t *tet_edge,
+                               uint8_t *bisected, uint32_t *edge_vertices, uint32_t *counters, void *stream_) {
+    return guarded([&] {
+        check_edge_split_count("tn_edge_split_count_tables", V, T, F, xyz, cells, select, faces, face_tets, tet_offsets, tet_edge,
+                               bisected, edge_vertices, counters);
+        DeviceGuard g(device);
+        tn::launch_edge_split_count(V, T, xyz, cells, select, F, faces, face_tets, tet_offsets, tet_edge, bisected, edge_vertices,
+                                    counters, (hipStream_t)stream_);
+    });
+}
+
+int tn_edge_split_count(tn_tracer_t tracer, size_t V, const float *xyz, const uint8_t *select, uint32_t *tet_offsets,
+                        uint32_t *tet_edge, uint8_t *bisected, uint32_t *edge_vertices, uint32_t *counters, void *stream_) {
+    return guarded([&] {
+        tn_tracer *t = checked(tracer);
+        std::lock_guard<std::mutex> lock(t->mu);
+        check_guard_mesh(t, "tn_edge_split_count", V);
+        const tn::DeviceMesh &m = t->mesh.view;
+        check_edge_split_count("tn_edge_split_count", V, m.T, m.F, xyz, m.cells, select, m.faces, m.face_tets, tet_offsets, tet_edge,
+                               bisected, edge_vertices, counters);
+        DeviceGuard g(t->device);
+        tn::launch_edge_split_count(V, m.T, xyz, m.cells, select, m.F, m.faces, m.face_tets, tet_offsets, tet_edge, bisected,
+                                    edge_vertices, counters, (hipStream_t)stream_);
+    });
+}
+
+int tn_edge_split_emit(size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint32_t *tet_offsets,
+                       const uint32_t *tet_edge, const uint32_t *edge_vertices, size_t num_new, size_t num_rows, float *xyz_out,
+                       uint32_t *cells_out, uint32_t *cell_parent, uint32_t *vertex_parents, void *stream_) {
+    return guarded([&] {
+        const std::string w("tn_edge_split_emit");
+        if (num_new > T || num_rows > T) throw tn::Error(w + ": num_new or num_rows exceeds num_cells (a tetrahedron is bisected at most once)");
+        if (V >= 0xFFFFFFFFull || V + num_new >= 0xFFFFFFFFull) throw tn::Error(w + ": too many vertices (uint32 ids)");
+        if (T >= tn::esplit::MAX_CELLS || T + num_rows >= tn::esplit::MAX_CELLS) throw tn::Error(w + ": num_cells + num_rows must be below 2^30");
+        if ((T && (!cells || !tet_offsets || !tet_edge || !cells_out || !cell_parent)) || (V && (!xyz || !xyz_out)) ||
+            (num_new && (!edge_vertices || !xyz_out || !vertex_parents)) || (num_rows && !edge_vertices))
+            throw tn::Error(w + ": a null pointer beside a non-zero count");
+        tn::launch_edge_split_emit(V, T, xyz, cells, tet_offsets, tet_edge, edge_vertices, num_new, num_rows, xyz_out, cells_out,
+                                   cell_parent, vertex_parents, (hipStream_t)stream_);
     });
 }
 

@@ -144,4 +144,20 @@ void launch_prune_emit(size_t V, const float *xyz, const uint32_t *offsets, size
 void launch_prune_vertex_rows(size_t rows, size_t V, size_t num_kept, const float *values, const float *values_vm,
                               const uint32_t *kept_ids, float *out, float *out_vm, hipStream_t s);
 
+// The edge split (tn_edge_split.hip; the rule: tn_edge_split_core.h; no reference counterpart).  The best edge of every asked
+// tetrahedron is a candidate; a candidate is bisected at its midpoint with every row around it unless a ring row has an id >= V,
+// it lies on a hull face, a ring row prefers another candidate, or a ring row or child is flat.  Both enqueue on `s` and return: no
+// read-back.  launch_edge_split_count: tet_offsets u32 [T + 1] = exclusive sums of the bisected flags; tet_edge u32 [T] = the rank
+// of the row's accepted edge (0xFFFFFFFF: not bisected); bisected u8 [T]; edge_vertices u32 [T, 2] of which the first K_v rows are
+// written; counters u32 [10] zeroed and then filled (K_v = counters[8], K_t = counters[9]); one stream-ordered allocation.
+// launch_edge_split_emit: the caller read the two totals back and passes them as num_new and num_rows, which bound every store;
+// xyz_out f32 [V + num_new, 3], cells_out u32 [T + num_rows, 4], cell_parent u32 [T + num_rows], vertex_parents u32 [num_new, 4].
+// The entries (tn_api_tracer.hip) have checked the arguments.
+void launch_edge_split_count(size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint8_t *select, size_t F,
+                             const uint32_t *faces, const uint32_t *face_tets, uint32_t *tet_offsets, uint32_t *tet_edge,
+                             uint8_t *bisected, uint32_t *edge_vertices, uint32_t *counters, hipStream_t s);
+void launch_edge_split_emit(size_t V, size_t T, const float *xyz, const uint32_t *cells, const uint32_t *tet_offsets,
+                            const uint32_t *tet_edge, const uint32_t *edge_vertices, size_t num_new, size_t num_rows, float *xyz_out,
+                            uint32_t *cells_out, uint32_t *cell_parent, uint32_t *vertex_parents, hipStream_t s);
+
 }  // namespace tn

@@ -661,6 +661,176 @@ def split_vertex_rows_statement(values, vertex_parents, new="mean"):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The edge split (csrc/tn_edge_split_core.h, csrc/tn_edge_split.hip), stated in numpy and vectorised:
+# selected edges are bisected at their midpoints together with every tetrahedron around them.  Every array is, bit for bit, what
+# the kernels give.
+
+EDGE_SPLIT_COUNTER_NAMES = ("asked", "asked_refused_id", "asked_refused_flat", "candidates", "refused_id", "refused_hull",
+                            "refused_lost", "refused_flat", "accepted", "bisected")
+_EDGE_CORNERS = np.array(((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)))   # iso::EDGE_CORNERS
+_ES_ID, _ES_HULL, _ES_LOST, _ES_FLAT = 1, 2, 4, 8
+
+
+def _len2_f32(lo, hi):
+    """(dx dx + dy dy) + dz dz of d = hi - lo on float32 [n, 3]: esplit::len2"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = hi - lo
+        return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+
+
+def _beats(len_e, key_e, len_f, key_f):
+    with np.errstate(invalid="ignore"):
+        return (len_e > len_f) | ((len_e == len_f) & (key_e < key_f))
+
+
+def _row_edges(c, p):
+    """(key uint64 [n, 6], len2 float32 [n, 6], slot_lo [n, 6], slot_hi [n, 6]) of rows c int64 [n, 4] with positions p f32 [n, 4, 3]"""
+    n = len(c)
+    a, b = _EDGE_CORNERS[:, 0], _EDGE_CORNERS[:, 1]
+    a_low = c[:, a] < c[:, b]
+    slot_lo, slot_hi = np.where(a_low, a[None], b[None]), np.where(a_low, b[None], a[None])
+    r = np.arange(n)[:, None]
+    key = (c[r, slot_lo].astype(np.uint64) << np.uint64(32)) | c[r, slot_hi].astype(np.uint64)
+    len2 = np.zeros((n, 6), np.float32)
+    if p is not None:
+        for e in range(6):
+            len2[:, e] = _len2_f32(p[np.arange(n), slot_lo[:, e]], p[np.arange(n), slot_hi[:, e]])
+    return key, len2, slot_lo, slot_hi
+
+
+def split_edges_statement(xyz, cells, select, faces, face_tets):
+    """What tn_edge_split_count(_tables) + tn_edge_split_emit compute.  xyz float32 [V, 3], cells integer [T, 4] (any tetrahedron
+    soup), select [T] (non-zero = asked), faces integer [F, 3] and face_tets integer [F, 2] (the face table of the cells:
+    oracle.build_faces, TetrahedraTracer.face_tables; a hull face has no second tetrahedron, -1): numpy arrays, or torch tensors
+    (copied to the host).
+
+    An edge is the sorted id pair (lo, hi), key = lo << 32 | hi, its squared length (dx dx + dy dy) + dz dz of d = p[hi] - p[lo] in
+    float32.  Edge e beats f iff len2(e) > len2(f), or they are equal and key(e) < key(f); the best of a list is the first, replaced
+    by every later one that beats it.  An asked tetrahedron whose ids are < V and whose stored orientation s is not 0 nominates the
+    best of its six edges, in the order (0,1), (0,2), (0,3), (1,2), (1,3), (2,3) of its slots; the candidates are the distinct
+    nominated keys.  The winner of ANY row is the best candidate among its six edges.  A candidate is refused, in this precedence,
+    because a row that holds it has an id >= V; because it is an edge of a hull face; because the winner of a row that holds it is
+    another edge; because a row that holds it has orientation 0, or one of the row's two children has not the row's orientation
+    (child 0: the slot of hi replaced by the midpoint ((p_lo + p_hi) + (p_lo + p_hi)) * 0.25f, child 1: the slot of lo).  The
+    accepted edges are ranked j in ascending key order, the new vertex is V + j; a bisected row t with k bisected rows below it
+    keeps child 0 and appends child 1 as row T + k.
+
+    Returns a dict of numpy arrays: "vertices" float32 [V + K_v, 3], "cells" int32 [T + K_t, 4], "cell_parent" int32 [T + K_t],
+    "vertex_parents" int32 [K_v, 4] = (lo, hi, lo, hi), "edge_vertices" int32 [K_v, 2], "bisected" uint8 [T], "tet_edge" int32 [T]
+    (the rank of the row's accepted edge, -1 where it is not bisected), "tet_offsets" uint32 [T + 1], "counters" uint32 [10]
+    (EDGE_SPLIT_COUNTER_NAMES); and the ints "num_new" = K_v, "num_rows" = K_t, "num_cells" = T + K_t."""
+    xyz = np.ascontiguousarray(_to_numpy(xyz), np.float32).reshape(-1, 3)
+    c = _as_index(_to_numpy(cells)).reshape(-1, 4)
+    asked = _to_numpy(select).reshape(-1) != 0
+    f = _as_index(_to_numpy(faces)).reshape(-1, 3)
+    ft = _as_index(_to_numpy(face_tets)).reshape(-1, 2)
+    V, T = len(xyz), len(c)
+    if len(asked) != T:
+        raise ValueError("select must have one entry per row of cells")
+    if len(f) != len(ft):
+        raise ValueError("faces and face_tets must have one row per face")
+    ids_ok = (c < V).all(1)
+    good = np.nonzero(ids_ok)[0]
+    cg = c[good]
+    p = xyz[cg]                                                               # float32 [n, 4, 3]
+    n, rows = len(good), np.arange(len(good))
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = _sign64(_vol6(p.astype(np.float64)))
+    key, len2, slot_lo, slot_hi = _row_edges(cg, p)
+
+    # candidates: the best edge of every asked, well-formed row that is not flat
+    best = np.zeros(n, np.int64)
+    for e in range(1, 6):
+        better = _beats(len2[:, e], key[:, e], len2[rows, best], key[rows, best])
+        best = np.where(better, e, best)
+    nominates = asked[good] & (s != 0)
+    cand = np.unique(key[rows, best][nominates])                              # ascending uint64 [C]
+    C = len(cand)
+    flags = np.zeros(C, np.uint32)
+
+    def find(k):
+        at = np.searchsorted(cand, k)
+        ok = (at < C) & (cand[np.minimum(at, max(C - 1, 0))] == k) if C else np.zeros(k.shape, bool)
+        return np.where(ok, at, -1)
+
+    # every well-formed row: its winner, what it says of the candidates it holds
+    winner = np.full(T, -1, np.int64)
+    if C:
+        found = find(key)                                                     # [n, 6]
+        w = np.full(n, -1, np.int64)                                          # the winning tet edge
+        for e in range(6):
+            has = found[:, e] >= 0
+            wc = np.maximum(w, 0)
+            better = has & ((w < 0) | _beats(len2[:, e], key[:, e], len2[rows, wc], key[rows, wc]))
+            w = np.where(better, e, w)
+        has_w = w >= 0
+        wc = np.maximum(w, 0)
+        lo_p, hi_p = p[rows, slot_lo[rows, wc]], p[rows, slot_hi[rows, wc]]
+        mid = _mean4_f32(lo_p, hi_p, lo_p, hi_p)
+        flat = s == 0
+        with np.errstate(invalid="ignore", over="ignore"):
+            for replaced in (slot_hi[rows, wc], slot_lo[rows, wc]):
+                q = p.copy()
+                q[rows, replaced] = mid
+                flat = flat | (_sign64(_vol6(q.astype(np.float64))) != s)
+        win_cand = np.where(has_w, found[rows, wc], -1)
+        for e in range(6):
+            has = found[:, e] >= 0
+            lost = has & (found[:, e] != win_cand)
+            np.bitwise_or.at(flags, found[lost, e], np.uint32(_ES_LOST))
+        np.bitwise_or.at(flags, win_cand[has_w & flat], np.uint32(_ES_FLAT))
+        winner[good] = win_cand
+        # rows with an id >= V: every candidate among their edges is refused for the id
+        bad = c[~ids_ok]
+        if len(bad):
+            bkey, _, _, _ = _row_edges(bad, None)
+            at = find(bkey)
+            np.bitwise_or.at(flags, at[at >= 0], np.uint32(_ES_ID))
+        # hull faces
+        hull = f[ft[:, 1] == EMPTY]
+        for k in range(3):
+            u, v = hull[:, k], hull[:, (k + 1) % 3]
+            hk = (np.minimum(u, v).astype(np.uint64) << np.uint64(32)) | np.maximum(u, v).astype(np.uint64)
+            at = find(hk)
+            np.bitwise_or.at(flags, at[at >= 0], np.uint32(_ES_HULL))
+
+    r_id = (flags & _ES_ID) != 0
+    r_hull = ~r_id & ((flags & _ES_HULL) != 0)
+    r_lost = ~r_id & ~r_hull & ((flags & _ES_LOST) != 0)
+    r_flat = ~r_id & ~r_hull & ~r_lost & ((flags & _ES_FLAT) != 0)
+    accepted = flags == 0
+    rank = np.concatenate([[0], np.cumsum(accepted)]).astype(np.int64)
+    K_v = int(rank[-1])
+    bisected = (winner >= 0) & accepted[np.maximum(winner, 0)] if C else np.zeros(T, bool)
+    tet_edge = np.where(bisected, rank[np.maximum(winner, 0)] if C else 0, -1)
+    tet_offsets = np.concatenate([[0], np.cumsum(bisected)]).astype(np.uint32)
+    K_t = int(tet_offsets[-1])
+    if T + K_t >= SPLIT_MAX_CELLS or V + K_v >= 0xFFFFFFFF:
+        raise ValueError("num_cells + bisected rows must be below 2^30 and num_vertices + num_new below 2^32 - 1")
+    acc_keys = cand[accepted]
+    lo, hi = (acc_keys >> np.uint64(32)).astype(np.int64), (acc_keys & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    edge_vertices = np.stack([lo, hi], 1).reshape(-1, 2)
+    mid = _mean4_f32(xyz[lo], xyz[hi], xyz[lo], xyz[hi]).reshape(-1, 3)
+    vertices = np.concatenate([xyz, mid], 0).astype(np.float32)
+    parents = np.nonzero(bisected)[0]
+    j = tet_edge[parents]
+    child0, child1 = c[parents].copy(), c[parents].copy()
+    is_hi, is_lo = child0 == hi[j][:, None], child1 == lo[j][:, None]
+    child0[np.arange(len(parents)), is_hi.argmax(1)] = V + j                  # the first slot that holds the id
+    child1[np.arange(len(parents)), is_lo.argmax(1)] = V + j
+    out = np.concatenate([c, child1], 0)
+    out[parents] = child0
+    cell_parent = np.concatenate([np.arange(T, dtype=np.int64), parents])
+    counters = np.array([asked.sum(), (asked & ~ids_ok).sum(), (asked[good] & (s == 0)).sum(), C, r_id.sum(), r_hull.sum(),
+                         r_lost.sum(), r_flat.sum(), K_v, K_t], np.uint32)
+    as_i32 = lambda a, shape: np.ascontiguousarray(a.astype(np.int64).astype(np.uint32)).view(np.int32).reshape(shape)
+    return {"vertices": vertices, "cells": as_i32(out, (-1, 4)), "cell_parent": cell_parent.astype(np.int32),
+            "vertex_parents": as_i32(np.stack([lo, hi, lo, hi], 1), (-1, 4)), "edge_vertices": as_i32(edge_vertices, (-1, 2)),
+            "bisected": bisected.astype(np.uint8), "tet_edge": as_i32(np.where(tet_edge < 0, 0xFFFFFFFF, tet_edge), (-1,)),
+            "tet_offsets": tet_offsets, "counters": counters, "num_new": K_v, "num_rows": K_t, "num_cells": T + K_t}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Vertex pruning (csrc/tn_prune_core.h, csrc/tn_prune.hip; DESIGN.md section 4.21), stated in numpy: asked vertices whose every
 # tetrahedron is dead, and which lie on no hull face, are removed, and every per-vertex array is compacted.  No arithmetic: every
 # array is, bit for bit, what the kernels give.

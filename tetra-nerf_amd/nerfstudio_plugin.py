@@ -661,7 +661,7 @@ def _grow_moments(optimizer, old, vertex_parents, new_moments, vertex_major):
 
 
 def densify(model, select=None, *, stats=None, score="error", min_hits=None, occupancy_threshold=None, min_width=None, max_new=None,
-            optimizer=None, new_moments="mean", retriangulate=False):
+            optimizer=None, new_moments="mean", retriangulate=False, method="centroid"):
     """Raise the resolution of a TetrahedraNerf's mesh where asked: the selected tetrahedra are split 1 -> 4 at their centroids
     (`tracer.split_tetrahedra`), the new vertices take the mean of their four parents' field columns, so
     the piecewise-linear field -- and with it the next frame and the next loss -- is the one of the unsplit mesh up to rounding.
@@ -690,14 +690,27 @@ def densify(model, select=None, *, stats=None, score="error", min_hits=None, occ
     nn.Parameter: the old one leaves the field cache, the new one is registered iff the old was, with its vertex-major shadow
     already installed).  BLOCKS on the read-back of the number of accepted tetrahedra and on the load.  With nothing accepted
     nothing is touched.
+    method: "centroid" (the default: the 1 -> 4 split above) or "edge": the best -- longest -- edge of every selected tetrahedron
+    is bisected at its midpoint together with EVERY tetrahedron around it (`tracer.split_edges`), which
+    halves the edge and the volumes where a centroid split never shortens an edge.  The new vertex takes the mean of the edge's
+    two ends, in the centroid's own expression, so everything above holds as it stands.  One call bisects an independent set of
+    edges: edges on the hull, edges that lose a tetrahedron to a longer selected edge and edges with a flat tetrahedron around
+    them are refused, and what was left unsplit is split by calling again with the caller's own selection carried as
+    cat(select & ~result["bisected"], zeros(num_cells - T)).
     Returns {"counters": int32 [4] on the device (asked, accepted, refused flat or inverted, refused for an id), "num_new",
-    "num_vertices", "num_cells", "retriangulated"}."""
+    "num_vertices", "num_cells", "retriangulated"}; with method="edge" the counters are the ten of split_edges
+    (geometry.EDGE_SPLIT_COUNTER_NAMES), "num_new" the new vertices K_v, "num_cells" T + K_t, and "bisected" uint8 [T] marks the
+    rows that were bisected."""
     from . import optim as tn_optim
     from . import tetranerf_cpp_extension as cpp
 
     if new_moments not in ("mean", "zero"):
         raise ValueError('densify: new_moments must be "mean" or "zero"')
+    if method not in ("centroid", "edge"):
+        raise ValueError('densify: method must be "centroid" or "edge"')
     tracer = model.get_tetrahedra_tracer()
+    if method == "edge" and not getattr(tracer, "supports_edge_split", False):
+        raise RuntimeError("densify(method=\"edge\") needs a tracer with split_edges (tetranerf_cpp_extension.TetrahedraTracer)")
     if not getattr(tracer, "supports_split", False):
         raise RuntimeError("densify needs a tracer with split_tetrahedra (tetranerf_cpp_extension.TetrahedraTracer)")
     field, vertices = model.tetrahedra_field, model.tetrahedra_vertices
@@ -737,10 +750,13 @@ def densify(model, select=None, *, stats=None, score="error", min_hits=None, occ
             mask &= cut
         registered = cpp.field_is_registered(field)
         field_vm = cpp.field_vertex_major(field) if registered else None        # (before the load below forgets it)
-        out = tracer.split_tetrahedra(mask.contiguous(), tet_values=() if occupancy is None else (occupancy.detach(),))
+        split = tracer.split_edges if method == "edge" else tracer.split_tetrahedra
+        out = split(mask.contiguous(), tet_values=() if occupancy is None else (occupancy.detach(),))
         K = int(out["num_new"])
-        result = {"counters": out["counters"], "num_new": K, "num_vertices": vertices.shape[0] + K, "num_cells": T + 3 * K,
-                  "retriangulated": False}
+        result = {"counters": out["counters"], "num_new": K, "num_vertices": vertices.shape[0] + K,
+                  "num_cells": T + (int(out["num_rows"]) if method == "edge" else 3 * K), "retriangulated": False}
+        if method == "edge":
+            result["bisected"] = out["bisected"]
         if has_stats:
             result["stats_reset"] = False
         if K == 0:

@@ -355,6 +355,61 @@ class TetrahedraTracer:
             self.load_tetrahedra(out["vertices"], out["cells"], refittable=self._refittable)
             return out
 
+    supports_edge_split = True
+    EDGE_SPLIT_GRID_LANES = 1024 * 256       # lanes of the edge split's kernels at their grid cap (tn_edge_split.hip: ESPLIT_BLOCKS * BT)
+
+    def edge_split_count(self, select, xyz=None):
+        """The first half of split_edges, alone: tn_edge_split_count on the tracer's own cells and face tables (split_edges' rule).
+        select: uint8 / bool [T]; xyz (None: the loaded vertices) f32 [V, 3].  Returns the dict of device arrays "tet_offsets" i32
+        [T + 1], "tet_edge" i32 [T], "bisected" uint8 [T], "edge_vertices" i32 [T, 2] (the first K_v rows are written), "counters"
+        i32 [10].  No synchronisation; the tracer is not touched."""
+        with torch.no_grad():
+            xyz = self._xyz_or_loaded(xyz)
+            V, T, dev = xyz.size(0), self.tetrahedra_cells.numel() // 4, self._device
+            _check_input(select, "select")
+            _check(select.dtype in (torch.uint8, torch.bool) and select.numel() == T and select.device == dev,
+                   "select must be uint8 or bool [num_cells] on the tracer's device")
+            with _on(dev):
+                out = _edge_split_buffers(T, dev)
+                _lib.check(self._lib.tn_edge_split_count(self._h, V, _ptr(xyz), _ptr(select), _ptr(out["tet_offsets"]), _ptr(out["tet_edge"]),
+                                                         _ptr(out["bisected"]), _ptr(out["edge_vertices"]), _ptr(out["counters"]),
+                                                         _stream(dev)))
+            return out
+
+    def split_edges(self, select, vertex_rows=(), tet_values=()):
+        """Bisect the best edge of every selected tetrahedron of the LOADED mesh at its midpoint, together with every tetrahedron
+        around it, and load the result: `split_edges` (below) on the tracer's own cells and face tables, every array of
+        `vertex_rows` (f32 [rows, V]: the field, its optimiser's moments) carried by split_vertex_rows(new="mean") -- the new
+        vertex's parents are (lo, hi, lo, hi) --, every array of `tet_values` ([T, ...] on the loaded cells: the occupancy) carried
+        as values[cell_parent] -- the two children tile their parent, so this is exact --, then load_tetrahedra(new vertices, new
+        cells, refittable=what this tracer was loaded with).  select: uint8 / bool [T].
+        Returns split_edges' dict with "vertex_rows" and "tet_values" (the carried arrays in the order given) added; the tracer
+        borrows "vertices" and "cells" from now on.  With K_v == 0 (nothing asked, or everything refused) the tracer is not touched
+        and the inputs come back as they are.  BLOCKS on the one read-back of the counters, and on what load_tetrahedra reads
+        back.  The field cache is invalidated, as by every load."""
+        with torch.no_grad():
+            xyz, cells = self.tetrahedra_vertices, self.tetrahedra_cells
+            _check(xyz is not None, "no mesh is loaded; call load_tetrahedra first")
+            xyz, cells = xyz.detach().reshape(-1, 3), cells.reshape(-1, 4)
+            V = xyz.size(0)
+            vertex_rows = tuple(vertex_rows)
+            for v in vertex_rows:
+                _check_input(v, "vertex_rows")
+                _check(v.dtype == torch.float32 and v.dim() == 2 and v.size(1) == V and v.device == self._device,
+                       "vertex_rows must be float32 [rows, V] arrays over the loaded vertices, on the tracer's device")
+            tet_values = self._check_tet_values(tet_values, flat=False)
+            with _on(self._device):
+                out = _edge_split_emit(xyz, cells, self.edge_split_count(select, xyz))
+            if out["num_new"] == 0:
+                out.update(vertices=self.tetrahedra_vertices, cells=self.tetrahedra_cells, vertex_rows=list(vertex_rows),
+                           tet_values=list(tet_values))
+                return out
+            out["vertex_rows"] = [split_vertex_rows(v.detach(), out["vertex_parents"]) for v in vertex_rows]
+            parent = out["cell_parent"].long()
+            out["tet_values"] = [t.detach()[parent] for t in tet_values]
+            self.load_tetrahedra(out["vertices"], out["cells"], refittable=self._refittable)
+            return out
+
     supports_prune = True
     PRUNE_GRID_LANES = 1024 * 256            # lanes of the prune's kernels at their grid cap (tn_prune.hip: PRUNE_BLOCKS * BT)
 
@@ -1409,6 +1464,80 @@ def split_vertex_rows(values, vertex_parents, new="mean", values_vm=None, want_v
         _lib.check(_lib.load().tn_split_vertex_rows(rows, V, K, _ptr(values), _ptr(values_vm), _ptr(vertex_parents), SPLIT_NEW_MODES[new],
                                                     _ptr(out), _ptr(out_vm), _stream(dev)))
     return (out, out_vm) if want_vertex_major else out
+
+
+def _edge_split_buffers(T, dev):
+    """the outputs of the edge split's count entries"""
+    return {"tet_offsets": _empty((T + 1,), dtype=torch.int32, device=dev), "tet_edge": _empty((T,), dtype=torch.int32, device=dev),
+            "bisected": _empty((T,), dtype=torch.uint8, device=dev), "edge_vertices": _empty((T, 2), dtype=torch.int32, device=dev),
+            "counters": _empty((10,), dtype=torch.int32, device=dev)}
+
+
+EDGE_SPLIT_MAX_CELLS = 1 << 30               # tn_edge_split_core.h: MAX_CELLS
+
+
+def _edge_split_emit(xyz, cells, count):
+    """The read-back of the counters and tn_edge_split_emit: split_edges' dict (the inputs themselves where nothing is accepted)"""
+    V, T, dev = xyz.size(0), cells.size(0), xyz.device
+    counters = count["counters"]
+    host = counters.tolist()                                                   # the read-back
+    Kv, Kt = int(host[8]), int(host[9])
+    _check(T + Kt < EDGE_SPLIT_MAX_CELLS and V + Kv < 0xFFFFFFFF,
+           "split_edges: num_cells + bisected rows must be below 2^30 and num_vertices + num_new below 2^32 - 1")
+    out = {"counters": counters, "bisected": count["bisected"], "tet_edge": count["tet_edge"], "tet_offsets": count["tet_offsets"],
+           "edge_vertices": count["edge_vertices"][:Kv], "num_new": Kv, "num_rows": Kt, "num_cells": T + Kt}
+    if Kv == 0:
+        out.update(vertices=xyz, cells=cells, cell_parent=torch.arange(T, dtype=torch.int32, device=dev),
+                   vertex_parents=_empty((0, 4), dtype=torch.int32, device=dev))
+        return out
+    vertices = _empty((V + Kv, 3), dtype=torch.float32, device=dev)
+    new_cells = _empty((T + Kt, 4), dtype=torch.int32, device=dev)
+    cell_parent = _empty((T + Kt,), dtype=torch.int32, device=dev)
+    vertex_parents = _empty((Kv, 4), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().tn_edge_split_emit(V, T, _ptr(xyz), _ptr(cells), _ptr(count["tet_offsets"]), _ptr(count["tet_edge"]),
+                                              _ptr(count["edge_vertices"]), Kv, Kt, _ptr(vertices), _ptr(new_cells), _ptr(cell_parent),
+                                              _ptr(vertex_parents), _stream(dev)))
+    out.update(vertices=vertices, cells=new_cells, cell_parent=cell_parent, vertex_parents=vertex_parents)
+    return out
+
+
+def split_edges(xyz, cells, select, faces, face_tets):
+    """Bisect the best edge of every selected tetrahedron at its midpoint, together with every tetrahedron around it (no reference
+    counterpart: the reference's mesh is its input point cloud for the whole run; tn_edge_split_count_tables + tn_edge_split_emit;
+    statement: geometry.split_edges_statement, bit for bit; the rule: DESIGN.md section 4.22).  xyz f32 [V, 3], cells i32 [T, 4]
+    (any tetrahedron soup), select uint8 / bool [T] (non-zero = asked), faces i32 [F, 3] and face_tets i32 [F, 2] (the cells' face
+    table, -1 = no second tetrahedron: a hull face), all on one device.  An asked tetrahedron that is well-formed and not flat
+    nominates its longest edge (ties: the smaller key lo << 32 | hi); a nominated edge is bisected unless a row around it has an id
+    outside [0, V), it lies on a hull face, a row around it holds a longer nominated edge, or a row around it or one of that row's
+    two children is flat.  The bisected edges share no tetrahedron: an independent set, not a maximal one -- call again for more.
+    Returns {"vertices": f32 [V + K_v, 3] (the old rows, then the midpoints in ascending edge order), "cells": i32 [T + K_t, 4]
+    (child 0 in the parent's row, child 1 appended, in ascending parent order), "cell_parent": i32 [T + K_t] (values[cell_parent]
+    carries a per-tetrahedron array), "vertex_parents": i32 [K_v, 4] = (lo, hi, lo, hi) (split_vertex_rows carries a per-vertex
+    array), "edge_vertices": i32 [K_v, 2], "bisected": uint8 [T] (carry your own selection as cat(select & ~bisected,
+    zeros(K_t))), "tet_edge": i32 [T], "tet_offsets": i32 [T + 1], "counters": i32 [10] on the device
+    (geometry.EDGE_SPLIT_COUNTER_NAMES), "num_new": K_v, "num_rows": K_t, "num_cells": T + K_t}.
+    BLOCKS on one small read-back: the counters between the two entries (they size the outputs).  With K_v == 0 the second entry
+    is not called: "vertices" and "cells" are the inputs themselves."""
+    for x, name in ((xyz, "xyz"), (cells, "cells"), (select, "select"), (faces, "faces"), (face_tets, "face_tets")):
+        _check_input(x, name)
+    dev = xyz.device
+    _check(xyz.dtype == torch.float32 and xyz.dim() == 2 and xyz.size(1) == 3, "xyz must be f32 [V, 3]")
+    _check(cells.dtype == torch.int32 and cells.dim() == 2 and cells.size(1) == 4 and cells.device == dev,
+           "cells must be int32 [num_cells, 4] on the device of xyz")
+    V, T, F = xyz.size(0), cells.size(0), faces.size(0)
+    _check(select.dtype in (torch.uint8, torch.bool) and select.numel() == T and select.device == dev,
+           "select must be uint8 or bool [num_cells] on the device of xyz")
+    _check(faces.dtype == torch.int32 and faces.dim() == 2 and faces.size(1) == 3 and faces.device == dev,
+           "faces must be int32 [num_faces, 3] on the device of xyz")
+    _check(face_tets.dtype == torch.int32 and tuple(face_tets.shape) == (F, 2) and face_tets.device == dev,
+           "face_tets must be int32 [num_faces, 2] on the device of xyz")
+    with torch.no_grad(), _on(dev):
+        count = _edge_split_buffers(T, dev)
+        _lib.check(_lib.load().tn_edge_split_count_tables(dev.index or 0, V, T, _ptr(xyz), _ptr(cells), _ptr(select), F, _ptr(faces),
+                                                          _ptr(face_tets), _ptr(count["tet_offsets"]), _ptr(count["tet_edge"]),
+                                                          _ptr(count["bisected"]), _ptr(count["edge_vertices"]), _ptr(count["counters"]),
+                                                          _stream(dev)))
+        return _edge_split_emit(xyz, cells, count)
 
 
 def _check_prune_masks(dead, vertex_select, T, V, dev):
