@@ -342,6 +342,51 @@ int tn_edge_split_emit(size_t num_vertices, size_t num_cells, const float *xyz, 
                        const uint32_t *tet_edge, const uint32_t *edge_vertices, size_t num_new, size_t num_rows, float *xyz_out,
                        uint32_t *cells_out, uint32_t *cell_parent, uint32_t *vertex_parents, void *stream);
 
+/* Delaunay repair by bistellar flips (no reference counterpart).  A CERTAINLY violated interior face -- tn_delaunay_check's own
+ * verdict -- is removed by a 2-3 flip (its two tetrahedra become three around the new edge de) or by a 3-2 flip (three tetrahedra
+ * around a reflex edge become two).  No vertex is added or moved, so every per-vertex array stays as it is (csrc/tn_flip.hip, the
+ * rule once in csrc/tn_flip_core.h; every output is bit-equal to geometry.flip_faces_statement).
+ *   xyz f32 [V,3], cells u32 [T,4], faces u32 [F,3] and face_tets u32 [F,2] (the face table of those cells; a hull face has
+ *   face_tets[f,1] == 0xFFFFFFFF), all on the current device.
+ *   For an interior face f: (a, b, c) = faces[f], t0, t1 = face_tets[f], d / e = the id of row t0 / t1 that the face does not name.
+ *   A violated face is refused, in this precedence: ID (a row index >= T or an id >= V, decided before any read of xyz: such a face
+ *   has no verdict); INVALID (the orientation of (a,b,c,d) or (a,b,c,e) is uncertain, or both have one sign); UNCERTAIN (one of
+ *   o_k = orientation of (x_k, y_k, d, e), (x_k, y_k) = (a,b), (b,c), (c,a), is uncertain); UNFLIPPABLE (o_k is good iff it has the
+ *   sign of (a,b,c,e); three good: 2-3; two good: 3-2, if one row t2 is the neighbour of t0 and of t1 across their faces opposite
+ *   the third id and holds x_k, y_k, d, e of the bad k; anything else); LOST (a row it needs is claimed by a candidate with a smaller
+ *   face id).  Otherwise it is accepted; accepted flips share no row: an independent set, not a maximal one -- call again for more.
+ *   Children: (x_k, y_k, d, e) for every good k ascending.  Child 0 takes the place of t0, child 1 that of t1, the place of t2 is
+ *   deleted (the new position of old row t is tet_offsets[t]), child 2 of a 2-3 flip is row (T - K32) + its rank among the accepted
+ *   2-3 flips in ascending face id.
+ * tn_flip_count / tn_flip_count_tables: tet_offsets u32 [T+1] = exclusive sums of "row t is not a deleted t2"; tet_flip u32 [T] =
+ *   the accepted face that takes the row, 0xFFFFFFFF for an untouched one; flipped u8 [T]; face_flip u32 [F,3] = (code, t2, rank):
+ *   (0, 0xFFFFFFFF, 0xFFFFFFFF) for a face that is not accepted, (1, 0xFFFFFFFF, rank) for a 2-3 flip, (2 + bad k, t2, 0xFFFFFFFF)
+ *   for a 3-2 flip; counters u32 [10], zeroed by the call: interior faces, violated, verdict uncertain, refused id / invalid /
+ *   uncertain / unflippable / lost, accepted 2-3 flips K23, accepted 3-2 flips K32 (reading them back is the caller's one
+ *   synchronisation).  tn_flip_count reads the loaded mesh's own device cells and face tables (num_vertices must be the loaded V;
+ *   xyz may be any positions of those vertices, NULL = the loaded ones); tn_flip_count_tables reads the arrays given, on `device`.
+ * tn_flip_emit: given those arrays and num_23 = K23, num_32 = K32 (host values): cells_out u32 [T+num_23-num_32,4], cell_sources
+ *   u32 [T+num_23-num_32,3] = the old rows whose union holds the new row, (t, 0xFFFFFFFF, 0xFFFFFFFF) for a copied one.  Every store
+ *   is bounded by the two counts passed: a caller who changed the inputs between the two entries gets a wrong mesh, never a write
+ *   outside its buffers.
+ * Only tn_flip_count needs a tracer.  All launch on `stream` and read nothing back; the atomics are the ten counters (one add per
+ *   block) and the claims (atomicMin), so no result depends on an order; the count entries take their scratch as one stream-ordered
+ *   allocation.  T == 0 gives empties.  Errors (nothing is touched): a null pointer beside a non-zero count; num_cells or num_cells
+ *   + num_23 >= 2^30; num_faces >= 2^32 - 1; num_23 or num_32 > num_faces; 2 num_23 + 3 num_32 > num_cells; tn_flip_count without
+ *   a loaded mesh or with another num_vertices. */
+int tn_flip_count_tables(int device, size_t num_vertices, size_t num_cells, const float *xyz, const uint32_t *cells, size_t num_faces,
+                         const uint32_t *faces, const uint32_t *face_tets, uint32_t *tet_offsets, uint32_t *tet_flip,
+                         uint8_t *flipped, uint32_t *face_flip, uint32_t *counters, void *stream);
+int tn_flip_count(tn_tracer_t tracer, size_t num_vertices, const float *xyz, uint32_t *tet_offsets, uint32_t *tet_flip,
+                  uint8_t *flipped, uint32_t *face_flip, uint32_t *counters, void *stream);
+int tn_flip_emit(size_t num_cells, const uint32_t *cells, size_t num_faces, const uint32_t *faces, const uint32_t *face_tets,
+                 const uint32_t *tet_offsets, const uint32_t *tet_flip, const uint32_t *face_flip, size_t num_23, size_t num_32,
+                 uint32_t *cells_out, uint32_t *cell_sources, void *stream);
+/* tn_flip_emit on the loaded mesh's own device cells and face tables: the second half of tn_flip_count (the tracer is not
+ * touched; load the new cells to make it follow).  Error: no loaded mesh, and those of tn_flip_emit. */
+int tn_flip_emit_loaded(tn_tracer_t tracer, const uint32_t *tet_offsets, const uint32_t *tet_flip, const uint32_t *face_flip,
+                        size_t num_23, size_t num_32, uint32_t *cells_out, uint32_t *cell_sources, void *stream);
+
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);
 

@@ -42,6 +42,7 @@ SYMBOLS = (
     "tn_tet_stats_accumulate",                     # per-tetrahedron training statistics: what a densification policy selects by
     "tn_prune_count", "tn_prune_count_tables", "tn_prune_emit", "tn_prune_vertex_rows",   # vertex pruning: the reference never changes its mesh
     "tn_edge_split_count", "tn_edge_split_count_tables", "tn_edge_split_emit",   # edge bisection with the whole ring: likewise
+    "tn_flip_count", "tn_flip_count_tables", "tn_flip_emit", "tn_flip_emit_loaded",   # Delaunay repair by 2-3 and 3-2 flips: likewise
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -93,6 +94,10 @@ def load():
     lib.tn_edge_split_count_tables.argtypes = [i32, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_edge_split_count.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_edge_split_emit.argtypes = [sz, sz, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    lib.tn_flip_count_tables.argtypes = [i32, sz, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.tn_flip_count.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.tn_flip_emit.argtypes = [sz, vp, sz, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
+    lib.tn_flip_emit_loaded.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
     lib.tn_tet_stats_accumulate.argtypes = [u32, sz, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_refit_table_bytes.restype = sz
     lib.tn_refit_table_bytes.argtypes = [vp]

@@ -13,6 +13,7 @@
 #include "tn_kernels.h"
 #include "tn_split_core.h"
 #include "tn_edge_split_core.h"
+#include "tn_flip_core.h"
 
 using tn::check_loaded;
 using tn::check_pow2_M;
@@ -928,6 +929,88 @@ int tn_edge_split_emit(size_t V, size_t T, const float *xyz, const uint32_t *cel
             throw tn::Error(w + ": a null pointer beside a non-zero count");
         tn::launch_edge_split_emit(V, T, xyz, cells, tet_offsets, tet_edge, edge_vertices, num_new, num_rows, xyz_out, cells_out,
                                    cell_parent, vertex_parents, (hipStream_t)stream_);
+    });
+}
+
+namespace {
+// the checks both count entries of the flip share (nothing is touched when one fails)
+void check_flip_count(const char *who, size_t V, size_t T, size_t F, const void *xyz, const void *cells, const void *faces,
+                      const void *face_tets, const void *tet_offsets, const void *tet_flip, const void *flipped, const void *face_flip,
+                      const void *counters) {
+    const std::string w(who);
+    if (V >= 0xFFFFFFFFull) throw tn::Error(w + ": too many vertices (uint32 ids)");
+    if (T >= tn::flip::MAX_CELLS) throw tn::Error(w + ": num_cells must be below 2^30");
+    if (F >= 0xFFFFFFFFull) throw tn::Error(w + ": too many faces");
+    if (!tet_offsets || !counters || (T && (!cells || !tet_flip || !flipped)) || (T && F && V && !xyz) ||
+        (F && (!faces || !face_tets || !face_flip)))
+        throw tn::Error(w + ": a null pointer beside a non-zero count");
+}
+}  // namespace
+
+int tn_flip_count_tables(int device, size_t V, size_t T, const float *xyz, const uint32_t *cells, size_t F, const uint32_t *faces,
+                         const uint32_t *face_tets, uint32_t *tet_offsets, uint32_t *tet_flip, uint8_t *flipped, uint32_t *face_flip,
+                         uint32_t *counters, void *stream_) {
+    return guarded([&] {
+        check_flip_count("tn_flip_count_tables", V, T, F, xyz, cells, faces, face_tets, tet_offsets, tet_flip, flipped, face_flip, counters);
+        DeviceGuard g(device);
+        tn::launch_flip_count(V, T, xyz, cells, F, faces, face_tets, tet_offsets, tet_flip, flipped, face_flip, counters,
+                              (hipStream_t)stream_);
+    });
+}
+
+int tn_flip_count(tn_tracer_t tracer, size_t V, const float *xyz, uint32_t *tet_offsets, uint32_t *tet_flip, uint8_t *flipped,
+                  uint32_t *face_flip, uint32_t *counters, void *stream_) {
+    return guarded([&] {
+        tn_tracer *t = checked(tracer);
+        std::lock_guard<std::mutex> lock(t->mu);
+        check_guard_mesh(t, "tn_flip_count", V);
+        const tn::DeviceMesh &m = t->mesh.view;
+        const float *positions = xyz ? xyz : m.xyz;   // null: the loaded vertices
+        check_flip_count("tn_flip_count", V, m.T, m.F, positions, m.cells, m.faces, m.face_tets, tet_offsets, tet_flip, flipped, face_flip,
+                         counters);
+        DeviceGuard g(t->device);
+        tn::launch_flip_count(V, m.T, positions, m.cells, m.F, m.faces, m.face_tets, tet_offsets, tet_flip, flipped, face_flip, counters,
+                              (hipStream_t)stream_);
+    });
+}
+
+namespace {
+// the checks and the launch both emit entries of the flip share (nothing is touched when a check fails)
+void checked_flip_emit(const char *who, size_t T, const uint32_t *cells, size_t F, const uint32_t *faces, const uint32_t *face_tets,
+                       const uint32_t *tet_offsets, const uint32_t *tet_flip, const uint32_t *face_flip, size_t num_23, size_t num_32,
+                       uint32_t *cells_out, uint32_t *cell_sources, void *stream_) {
+    const std::string w(who);
+    if (num_23 > F || num_32 > F) throw tn::Error(w + ": num_23 or num_32 exceeds num_faces (a face is flipped at most once)");
+    if (2 * num_23 + 3 * num_32 > T) throw tn::Error(w + ": the flips need more rows than num_cells (accepted flips share no row)");
+    if (T >= tn::flip::MAX_CELLS || T + num_23 >= tn::flip::MAX_CELLS) throw tn::Error(w + ": num_cells + num_23 must be below 2^30");
+    if (F >= 0xFFFFFFFFull) throw tn::Error(w + ": too many faces");
+    if ((T && (!cells || !tet_offsets || !tet_flip)) || (T + num_23 > num_32 && (!cells_out || !cell_sources)) ||
+        (F && (!faces || !face_tets || !face_flip)))
+        throw tn::Error(w + ": a null pointer beside a non-zero count");
+    tn::launch_flip_emit(T, cells, F, faces, face_tets, tet_offsets, tet_flip, face_flip, num_23, num_32, cells_out, cell_sources,
+                         (hipStream_t)stream_);
+}
+}  // namespace
+
+int tn_flip_emit(size_t T, const uint32_t *cells, size_t F, const uint32_t *faces, const uint32_t *face_tets,
+                 const uint32_t *tet_offsets, const uint32_t *tet_flip, const uint32_t *face_flip, size_t num_23, size_t num_32,
+                 uint32_t *cells_out, uint32_t *cell_sources, void *stream_) {
+    return guarded([&] {
+        checked_flip_emit("tn_flip_emit", T, cells, F, faces, face_tets, tet_offsets, tet_flip, face_flip, num_23, num_32, cells_out,
+                          cell_sources, stream_);
+    });
+}
+
+int tn_flip_emit_loaded(tn_tracer_t tracer, const uint32_t *tet_offsets, const uint32_t *tet_flip, const uint32_t *face_flip,
+                        size_t num_23, size_t num_32, uint32_t *cells_out, uint32_t *cell_sources, void *stream_) {
+    return guarded([&] {
+        tn_tracer *t = checked(tracer);
+        std::lock_guard<std::mutex> lock(t->mu);
+        if (!t->mesh.loaded) throw tn::Error("tn_flip_emit_loaded: no mesh is loaded; call load_tetrahedra first");
+        const tn::DeviceMesh &m = t->mesh.view;
+        DeviceGuard g(t->device);
+        checked_flip_emit("tn_flip_emit_loaded", m.T, m.cells, m.F, m.faces, m.face_tets, tet_offsets, tet_flip, face_flip, num_23, num_32,
+                          cells_out, cell_sources, stream_);
     });
 }
 

@@ -160,4 +160,20 @@ void launch_edge_split_emit(size_t V, size_t T, const float *xyz, const uint32_t
                             const uint32_t *tet_edge, const uint32_t *edge_vertices, size_t num_new, size_t num_rows, float *xyz_out,
                             uint32_t *cells_out, uint32_t *cell_parent, uint32_t *vertex_parents, hipStream_t s);
 
+// The Delaunay repair by flips (tn_flip.hip; the rule: tn_flip_core.h; no reference counterpart).  A certainly violated interior
+// face is a candidate; it is flipped 2-3 or 3-2 unless a row it reads has a bad id, its two apices are not certainly on opposite
+// sides, an orientation around the new edge is uncertain, the configuration is unflippable, or a row it needs goes to a candidate
+// with a smaller face id.  Both enqueue on `s` and return: no read-back.  launch_flip_count: tet_offsets u32 [T + 1] = exclusive sums
+// of "row t is kept" (all rows but the deleted third rows of 3-2 flips); tet_flip u32 [T] = the accepted face that takes the row
+// (0xFFFFFFFF: untouched); flipped u8 [T]; face_flip u32 [F, 3] = (code, t2, rank); counters u32 [10] zeroed and then filled (K23 =
+// counters[8], K32 = counters[9]); one stream-ordered allocation.  launch_flip_emit: the caller read the two totals back and passes
+// them as num_23 and num_32, which bound every store; cells_out u32 [T + num_23 - num_32, 4], cell_sources u32 [same, 3].  The
+// entries (tn_api_tracer.hip) have checked the arguments.
+void launch_flip_count(size_t V, size_t T, const float *xyz, const uint32_t *cells, size_t F, const uint32_t *faces,
+                       const uint32_t *face_tets, uint32_t *tet_offsets, uint32_t *tet_flip, uint8_t *flipped, uint32_t *face_flip,
+                       uint32_t *counters, hipStream_t s);
+void launch_flip_emit(size_t T, const uint32_t *cells, size_t F, const uint32_t *faces, const uint32_t *face_tets,
+                      const uint32_t *tet_offsets, const uint32_t *tet_flip, const uint32_t *face_flip, size_t num_23, size_t num_32,
+                      uint32_t *cells_out, uint32_t *cell_sources, hipStream_t s);
+
 }  // namespace tn

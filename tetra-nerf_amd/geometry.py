@@ -831,6 +831,218 @@ def split_edges_statement(xyz, cells, select, faces, face_tets):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The Delaunay repair by bistellar flips (csrc/tn_flip_core.h, csrc/tn_flip.hip; DESIGN.md section 4.23), stated in numpy and
+# vectorised: a certainly violated interior face is removed by a 2-3 or a 3-2 flip.  The signs are those of orient_det /
+# insphere_det above with their stage-A bounds; every array is, bit for bit, what the kernels give.
+
+FLIP_COUNTER_NAMES = ("interior", "violated", "verdict_uncertain", "refused_id", "refused_invalid", "refused_uncertain",
+                      "refused_unflippable", "refused_lost", "accepted_23", "accepted_32")
+FLIP_NONE, FLIP_23, FLIP_32 = 0, 1, 2                      # face_flip's codes: FLIP_32 + the bad k
+(FLIP_K_HULL, FLIP_K_REGULAR, FLIP_K_VERDICT_UNCERTAIN, FLIP_K_ID, FLIP_K_INVALID, FLIP_K_UNCERTAIN,
+ FLIP_K_UNFLIPPABLE) = 8, 9, 10, 11, 12, 13, 14           # flip::Kind: what a face that is no flippable candidate is
+
+
+def _orient_sign(q0, q1, q2, q3):
+    """+1 / -1 where the sign of orient_det of the rows (q0, q1, q2, q3) float64 [n, 3] is certain, 0 where it is not"""
+    det, perm = orient_det(np.stack([q0, q1, q2, q3], 1))
+    return np.where(abs(det) > ORIENT_BOUND * perm, np.where(det > 0, 1, -1), 0)
+
+
+def _apex_slot(c, f):
+    """the first slot of each row c [n, 4] whose id is not one of f [n, 3]; -1 where every slot is"""
+    free = (c[:, :, None] != f[:, None, :]).all(-1)
+    return np.where(free.any(1), free.argmax(1), -1)
+
+
+def flip_faces_statement(xyz, cells, faces, face_tets):
+    """What tn_flip_count(_tables) + tn_flip_emit compute: ONE round of flips.  xyz float32 [V, 3], cells integer [T, 4], faces
+    integer [F, 3] and face_tets integer [F, 2] (the face table of the cells; a hull face has no second tetrahedron, -1): numpy
+    arrays, or torch tensors (copied to the host).
+
+    For an interior face f: (a, b, c) = faces[f] as stored, t0, t1 = face_tets[f], d / e = the id in the first slot of row t0 / t1
+    that is not one of a, b, c.  O(p, q, r, s) is the sign of orient_det, certain iff |det| > ORIENT_BOUND * permanent.  The face
+    is refused for the first of: ID (t0 or t1 >= T, an id >= V among a, b, c and the two rows, or a row without such a slot: no
+    position is read and the face has no verdict); -- then the verdict of delaunay_face_statement decides whether it is a
+    candidate at all: only VIOLATED faces are --; INVALID (O(a,b,c,d) or O(a,b,c,e) uncertain, or equal); UNCERTAIN (one of o_k =
+    O(x_k, y_k, d, e), (x_k, y_k) = (a,b), (b,c), (c,a), uncertain); UNFLIPPABLE (o_k is good iff it equals O(a,b,c,e); three good:
+    a 2-3 flip of {t0, t1}; two good and the bad k: a 3-2 flip iff one row t2 is the neighbour of t0 and of t1 across their faces
+    opposite the id of (a, b, c) that is not x_k, y_k -- through tet_faces and face_tets -- and holds x_k, y_k, d, e; anything
+    else); LOST (a row it needs is claimed by a flippable candidate with a smaller face id).  Otherwise it is accepted.  Children:
+    (x_k, y_k, d, e) for every good k ascending; child 0 takes t0's place, child 1 t1's, t2's place is deleted, child 2 of a 2-3
+    flip is appended at (T - K32) + its rank among the accepted 2-3 flips in ascending face id.
+
+    Returns a dict of numpy arrays: "cells" int32 [T', 4], "cell_sources" int32 [T', 3] (the old rows whose union holds the new
+    one, -1 = none), "flipped" uint8 [T], "tet_flip" int32 [T] (the accepted face that takes the row, -1), "tet_offsets" uint32
+    [T + 1], "face_flip" int32 [F, 3] = (code, t2, rank), "counters" uint32 [10] (FLIP_COUNTER_NAMES), "face_kind" int64 [F]
+    (FLIP_K_* or the code of a flippable candidate, accepted or lost), "tet_faces" int64 [T, 4]; and the ints "num_23", "num_32",
+    "num_cells" = T' = T + K23 - K32."""
+    xyz = np.ascontiguousarray(_to_numpy(xyz), np.float32).reshape(-1, 3)
+    c = _as_index(_to_numpy(cells)).reshape(-1, 4)
+    f = _as_index(_to_numpy(faces)).reshape(-1, 3)
+    ft = _as_index(_to_numpy(face_tets)).reshape(-1, 2)
+    V, T, F = len(xyz), len(c), len(f)
+    if len(ft) != F:
+        raise ValueError("faces and face_tets must have one row per face")
+    ids = np.arange(F)
+
+    tet_faces = np.full((T, 4), EMPTY, np.int64)
+    for side in (0, 1):
+        at = ids[ft[:, side] < T]
+        t = ft[at, side]
+        slot = _apex_slot(c[t], f[at])
+        tet_faces[t[slot >= 0], slot[slot >= 0]] = at[slot >= 0]
+
+    interior = ft[:, 1] != EMPTY
+    kind = np.where(interior, FLIP_K_ID, FLIP_K_HULL).astype(np.int64)
+    third = np.full(F, EMPTY, np.int64)
+    g = ids[interior & (ft[:, 0] < T) & (ft[:, 1] < T)]
+    c0, c1, fg = c[ft[g, 0]], c[ft[g, 1]], f[g]
+    s0, s1 = _apex_slot(c0, fg), _apex_slot(c1, fg)
+    ok = (s0 >= 0) & (s1 >= 0) & (fg < V).all(1) & (c0 < V).all(1) & (c1 < V).all(1)
+    g, c0, c1, fg, s0, s1 = g[ok], c0[ok], c1[ok], fg[ok], s0[ok], s1[ok]
+    n, r = len(g), np.arange(len(g))
+    t0, t1 = ft[g, 0], ft[g, 1]
+    d, e = c0[r, s0], c1[r, s1]
+    x = xyz.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        new = (c1[:, :, None] != c0[:, None, :]).all(-1)
+        ev = c1[:, 3]
+        for k in (2, 1, 0):
+            ev = np.where(new[:, k], c1[:, k], ev)
+        p = x[c0]
+        ins, ori = insphere_det(p, x[ev]), orient_det(p)
+        certain = (abs(ins[0]) > INSPHERE_BOUND * ins[1]) & (abs(ori[0]) > ORIENT_BOUND * ori[1])
+        inside = (ins[0] > 0) == (ori[0] > 0)
+        pa, pb, pc, pd, pe = x[fg[:, 0]], x[fg[:, 1]], x[fg[:, 2]], x[d], x[e]
+        sd, se = _orient_sign(pa, pb, pc, pd), _orient_sign(pa, pb, pc, pe)
+        o = np.stack([_orient_sign(pa, pb, pd, pe), _orient_sign(pb, pc, pd, pe), _orient_sign(pc, pa, pd, pe)], 1).reshape(n, 3)
+    good = o == se[:, None]
+    flippable = np.where(good.sum(1) == 3, FLIP_23, np.where(good.sum(1) == 2, FLIP_32 + (~good).argmax(1), FLIP_K_UNFLIPPABLE))
+    kg = np.where(~certain, FLIP_K_VERDICT_UNCERTAIN, np.where(~inside, FLIP_K_REGULAR,
+                  np.where((sd == 0) | (se == 0) | (sd == se), FLIP_K_INVALID, np.where((o == 0).any(1), FLIP_K_UNCERTAIN, flippable))))
+
+    # the third row of the 3-2 candidates
+    m = np.nonzero((kg >= FLIP_32) & (kg < FLIP_32 + 3))[0]
+    if len(m):
+        kb = kg[m] - FLIP_32
+        xx, yy, zz = fg[m, kb], fg[m, (kb + 1) % 3], fg[m, (kb + 2) % 3]
+        nb = []
+        for cc, tt in ((c0[m], t0[m]), (c1[m], t1[m])):
+            is_z = cc == zz[:, None]
+            gf = tet_faces[tt, is_z.argmax(1)]
+            okf = is_z.any(1) & (gf < F)
+            gf = np.where(okf, gf, 0)
+            u, w = ft[gf, 0], ft[gf, 1]
+            nb.append(np.where(okf, np.where(u == tt, w, np.where(w == tt, u, EMPTY)), EMPTY))
+        t2 = np.where((nb[0] == nb[1]) & (nb[0] < T) & (nb[0] != t0[m]) & (nb[0] != t1[m]), nb[0], EMPTY)
+        c2 = c[np.where(t2 < T, t2, 0)] if T else np.zeros((len(m), 4), np.int64)
+        have = np.ones(len(m), bool)
+        for want in (xx, yy, d[m], e[m]):
+            have &= (c2 == want[:, None]).any(1)
+        t2 = np.where((t2 != EMPTY) & have, t2, EMPTY)
+        kg[m] = np.where(t2 == EMPTY, FLIP_K_UNFLIPPABLE, kg[m])
+        third[g[m]] = t2
+    kind[g] = kg
+
+    # the claims and the precedence
+    claim = np.full(T, EMPTY, np.int64)
+    cand = ids[kind < FLIP_K_HULL]
+    ct0, ct1, ct2 = ft[cand, 0], ft[cand, 1], third[cand]
+    has2 = ct2 != EMPTY
+    np.minimum.at(claim, ct0, cand)
+    np.minimum.at(claim, ct1, cand)
+    np.minimum.at(claim, ct2[has2], cand[has2])
+    won = (claim[ct0] == cand) & (claim[ct1] == cand) & (~has2 | (claim[np.where(has2, ct2, 0)] == cand)) if len(cand) else np.zeros(0, bool)
+    acc = cand[won]
+    code = np.zeros(F, np.int64)
+    code[acc] = kind[acc]
+    is23 = code == FLIP_23
+    rank = np.concatenate([[0], np.cumsum(is23)]).astype(np.int64)
+    K23, K32 = int(is23.sum()), int((code >= FLIP_32).sum())
+    if T + K23 >= SPLIT_MAX_CELLS:
+        raise ValueError("num_cells + accepted 2-3 flips must be below 2^30")
+    face_flip = np.stack([code, np.where(code >= FLIP_32, third, EMPTY), np.where(is23, rank[:-1], EMPTY)], 1).reshape(F, 3)
+
+    taken = (claim < F) & (code[np.where(claim < F, claim, 0)] != FLIP_NONE) if F else np.zeros(T, bool)
+    owner = np.where(taken, claim, 0)
+    rows = np.arange(T)
+    kept = ~taken | (ft[owner, 0] == rows) | (ft[owner, 1] == rows) if F else np.ones(T, bool)
+    tet_offsets = np.concatenate([[0], np.cumsum(kept)]).astype(np.uint32)
+    T_new = T + K23 - K32
+    out = np.zeros((T_new, 4), np.int64)
+    src = np.full((T_new, 3), EMPTY, np.int64)
+    plain = rows[~taken]
+    out[tet_offsets[plain]] = c[plain]
+    src[tet_offsets[plain], 0] = plain
+    if len(acc):
+        where_g = np.full(F, -1, np.int64)
+        where_g[g] = r
+        ag = where_g[acc]                                                     # accepted faces as rows of the judged arrays
+        fa, da, ea, ka = fg[ag], d[ag], e[ag], code[acc]
+        bad, ra = np.where(ka >= FLIP_32, ka - FLIP_32, 3), np.arange(len(acc))
+        for j in range(3):                                                    # child j: the j-th good k in ascending order
+            k = np.minimum(j + (bad <= j), 2)
+            use = (ka == FLIP_23) if j == 2 else np.ones(len(acc), bool)      # (a 3-2 flip has no third child)
+            row = np.stack([fa[ra, k], fa[ra, (k + 1) % 3], da, ea], 1)
+            pos = (tet_offsets[ft[acc, 0]], tet_offsets[ft[acc, 1]], (T - K32) + rank[acc])[j].astype(np.int64)
+            out[pos[use]] = row[use]
+            src[pos[use], 0], src[pos[use], 1] = ft[acc[use], 0], ft[acc[use], 1]
+            src[pos[use], 2] = np.where(ka[use] >= FLIP_32, third[acc[use]], EMPTY)
+    viol = (kind < FLIP_K_HULL) | (kind >= FLIP_K_INVALID)
+    counters = np.array([interior.sum(), viol.sum(), (kind == FLIP_K_VERDICT_UNCERTAIN).sum(), (kind == FLIP_K_ID).sum(),
+                         (kind == FLIP_K_INVALID).sum(), (kind == FLIP_K_UNCERTAIN).sum(), (kind == FLIP_K_UNFLIPPABLE).sum(),
+                         len(cand) - len(acc), K23, K32], np.uint32)
+    as_i32 = lambda a, shape: np.ascontiguousarray(a.astype(np.int64).astype(np.uint32)).view(np.int32).reshape(shape)   # noqa: E731
+    return {"cells": as_i32(out, (-1, 4)), "cell_sources": as_i32(src, (-1, 3)), "flipped": taken.astype(np.uint8),
+            "tet_flip": as_i32(np.where(taken, claim, EMPTY), (-1,)), "tet_offsets": tet_offsets, "face_flip": as_i32(face_flip, (-1, 3)),
+            "counters": counters, "face_kind": kind, "tet_faces": tet_faces, "num_23": K23, "num_32": K32, "num_cells": T_new}
+
+
+def flip_tet_values_statement(values, cell_sources):
+    """What flip_tet_values computes: per new row the largest value over its sources, by the values' bit patterns as unsigned
+    integers (remap_tet_values_statement's rule).  values float32 [T], cell_sources integer [T', 3] (-1 = none) -> float32 [T']."""
+    bits = np.ascontiguousarray(_to_numpy(values), np.float32).view(np.uint32)
+    s = _as_index(_to_numpy(cell_sources)).reshape(-1, 3)
+    got = np.where(s != EMPTY, bits[np.where(s != EMPTY, s, 0)], 0) if len(bits) else np.zeros(s.shape, np.uint32)
+    return got.astype(np.uint32).max(1).view(np.float32) if len(s) else np.zeros(0, np.float32)
+
+
+def flip_to_delaunay_statement(xyz, cells, face_table, max_rounds=32):
+    """What TetrahedraTracer.flip_to_delaunay computes: rounds of flip_faces_statement until one accepts nothing or max_rounds is
+    reached.  face_table(cells) -> (faces, face_tets) of the cells of every round.  Returns {"cells", "cell_sources" (composed:
+    int64 [T', S] padded with EMPTY, the input rows whose union holds the row), "rounds" (the counters of every round run),
+    "violated", "unflippable" (of the last round run: what is left), "num_rounds" (the rounds that accepted something)}."""
+    cells = np.ascontiguousarray(_to_numpy(cells)).reshape(-1, 4)
+    sources = np.arange(len(cells), dtype=np.int64)[:, None]
+    rounds = []
+    for _ in range(max(int(max_rounds), 0) + 1):
+        faces, face_tets = face_table(cells)
+        out = flip_faces_statement(xyz, cells, faces, face_tets)
+        rounds.append(out["counters"])
+        if out["num_23"] + out["num_32"] == 0 or len(rounds) > max_rounds:
+            break
+        cells = out["cells"]
+        sources = compose_cell_sources(sources, out["cell_sources"])
+    last = rounds[-1]
+    return {"cells": cells, "cell_sources": sources, "rounds": rounds, "violated": int(last[1]), "unflippable": int(last[6]),
+            "num_rounds": len(rounds) - 1}
+
+
+def compose_cell_sources(sources, step):
+    """sources integer [T, S] (EMPTY-padded input rows of every current row), step integer [T', 3] (flip_faces' cell_sources of
+    one round) -> int64 [T', S'] the input rows of every new row: the union over its up to three sources, ascending, without
+    repeats, padded with EMPTY and trimmed to the longest."""
+    s = _as_index(np.asarray(step)).reshape(-1, 3)
+    src = _as_index(np.asarray(sources))
+    got = np.where((s != EMPTY)[:, :, None], src[np.where(s != EMPTY, s, 0)], EMPTY).reshape(len(s), -1)
+    got = np.sort(got, 1)
+    got[:, 1:][got[:, 1:] == got[:, :-1]] = EMPTY
+    got = np.sort(got, 1)
+    width = max(int((got != EMPTY).sum(1).max()) if len(got) else 1, 1)
+    return got[:, :width]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Vertex pruning (csrc/tn_prune_core.h, csrc/tn_prune.hip; DESIGN.md section 4.21), stated in numpy: asked vertices whose every
 # tetrahedron is dead, and which lie on no hull face, are removed, and every per-vertex array is compacted.  No arithmetic: every
 # array is, bit for bit, what the kernels give.

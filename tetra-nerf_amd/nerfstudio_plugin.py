@@ -48,7 +48,8 @@ network in tetrahedra below it, except every `occupancy_refresh_every`-th one, d
 `refit_vertices` (the tracer follows a vertex table an optimiser moves: `_follow_vertices` below) with `vertex_step_fraction`
 (each followed move is first shortened so that no tetrahedron turns inside out: `TetrahedraTracer.limit_vertex_step`) and
 `delaunay_check_every` / `retriangulate_above` (every so many followed iterations the interior faces that stopped being Delaunay
-are counted, and above that fraction of them the vertices get new cells: `_monitor_delaunay` below).
+are counted, and above that fraction of them the vertices get new cells: `_monitor_delaunay` below; with `delaunay_repair =
+"flip"` the violated faces are first flipped on the device and Qhull runs only for what is left above the threshold).
 
 nerfstudio is not installed in this environment: the adapter is duck-typed (it only touches the attribute names listed
 above) and is tested with stand-ins of nerfstudio's MLP / FieldHead / RayBundle (tests/golden/nerfstudio_standins.py).
@@ -279,7 +280,8 @@ def _monitor_delaunay(tracer, model, above, keep_snapshot):
     its `tetrahedra_occupancy` (carried over conservatively: `remap_tet_values`) are replaced, `_tn_retriangulations` counts the
     re-triangulation.  What is keyed by vertex -- the field, its optimiser state -- does not change.  keep_snapshot (the caller's
     vertex_step_fraction is set) decides nothing any more: `_follow_vertices` keeps a snapshot exactly then, and `_adopt_mesh`
-    refreshes the one the tracer keeps.  Returns True after a re-triangulation."""
+    refreshes the one the tracer keeps.  With `config.delaunay_repair = "flip"` (opt-in) flips on the device are tried first and
+    Qhull runs only for what they leave above the threshold (below).  Returns True after a re-triangulation or a repair by flips."""
     counters = tracer.delaunay_check()["counters"]
     _accumulate(model, "_tn_delaunay_counters", counters)
     if above is None:
@@ -288,6 +290,23 @@ def _monitor_delaunay(tracer, model, above, keep_snapshot):
     if interior == 0 or violated <= float(above) * interior:
         return False
     occupancy = getattr(model, "tetrahedra_occupancy", None) if model is not None else None
+    repair = getattr(getattr(model, "config", None), "delaunay_repair", None)
+    if repair is not None:
+        # config.delaunay_repair = "flip" (opt-in; absent or None: the re-triangulation alone, call for call): flips of the violated
+        # faces on the device first (`tracer.flip_to_delaunay`) -- no vertex moves, the occupancy is carried
+        # by `flip_tet_values`, the model adopts the cells and `_tn_flip_repairs` counts the repair --, and Qhull only where the
+        # violated share that flips could not remove is still above the threshold.
+        if repair != "flip":
+            raise ValueError('config.delaunay_repair must be "flip" or absent')
+        if not getattr(tracer, "supports_flip", False):
+            raise RuntimeError('config.delaunay_repair = "flip" needs a tracer with flip_to_delaunay (tetranerf_cpp_extension.TetrahedraTracer)')
+        out = tracer.flip_to_delaunay(tet_values=() if occupancy is None else (occupancy.detach(),))
+        if out["num_rounds"]:
+            _adopt_mesh(model, tracer, out["cells"], occupancy=None if occupancy is None else out["tet_values"][0])
+            model._tn_flip_repairs = getattr(model, "_tn_flip_repairs", 0) + 1
+            occupancy = getattr(model, "tetrahedra_occupancy", None)
+        if out["violated"] <= float(above) * out["rounds"][-1][0]:
+            return bool(out["num_rounds"])
     out = tracer.retriangulate(tracer.tetrahedra_vertices, () if occupancy is None else (occupancy.detach(),))
     _adopt_mesh(model, tracer, out["cells"], occupancy=None if occupancy is None else out["tet_values"][0])
     if model is not None:

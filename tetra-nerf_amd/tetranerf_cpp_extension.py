@@ -410,6 +410,70 @@ class TetrahedraTracer:
             self.load_tetrahedra(out["vertices"], out["cells"], refittable=self._refittable)
             return out
 
+    supports_flip = True
+    FLIP_GRID_LANES = 1024 * 256             # lanes of the flip's kernels at their grid cap (tn_flip.hip: FLIP_BLOCKS * BT)
+
+    def flip_count(self, xyz=None):
+        """The first half of a round of flips, alone: tn_flip_count on the tracer's own cells and face tables (flip_faces' rule).
+        xyz (None: the loaded vertices) f32 [V, 3].  Returns the dict of device arrays "tet_offsets" i32 [T + 1], "tet_flip" i32 [T],
+        "flipped" uint8 [T], "face_flip" i32 [F, 3], "counters" i32 [10].  No synchronisation; the tracer is not touched."""
+        with torch.no_grad():
+            xyz = self._xyz_or_loaded(xyz)
+            V, T, dev = xyz.size(0), self.tetrahedra_cells.numel() // 4, self._device
+            with _on(dev):
+                out = _flip_buffers(T, int(self._lib.tn_num_faces(self._h)), dev)
+                _lib.check(self._lib.tn_flip_count(self._h, V, _ptr(xyz), _ptr(out["tet_offsets"]), _ptr(out["tet_flip"]),
+                                                   _ptr(out["flipped"]), _ptr(out["face_flip"]), _ptr(out["counters"]), _stream(dev)))
+            return out
+
+    def flip_faces(self, xyz=None):
+        """ONE round of flips on the loaded mesh, not loaded: flip_count, the read-back of the counters, tn_flip_emit_loaded.
+        Returns flip_faces' dict (below); with nothing accepted "cells" is the loaded tensor itself.  The tracer is not touched."""
+        with torch.no_grad():
+            count = self.flip_count(xyz)
+            cells = self.tetrahedra_cells.reshape(-1, 4)
+
+            def emit(K23, K32, new_cells, sources):
+                _lib.check(self._lib.tn_flip_emit_loaded(self._h, _ptr(count["tet_offsets"]), _ptr(count["tet_flip"]), _ptr(count["face_flip"]),
+                                                         K23, K32, _ptr(new_cells), _ptr(sources), _stream(self._device)))
+            with _on(self._device):
+                return _flip_emit(cells, count, emit)
+
+    def flip_to_delaunay(self, xyz=None, tet_values=(), max_rounds=32):
+        """Repair the Delaunay property of the LOADED mesh on `xyz` (None: the loaded vertices) by bistellar flips, on the device (no
+        reference counterpart).  Rounds of flip_faces -- every certainly violated face that is flippable
+        and wins its rows is removed by a 2-3 or a 3-2 flip -- until a round accepts nothing or max_rounds rounds have flipped.  No
+        vertex is added or moved: per-vertex arrays (the field, its optimiser's moments) stay as they are.  Every array of
+        `tet_values` (float32 [T] of values >= 0 on the loaded cells: the occupancy) is carried by flip_tet_values: a new row lies
+        inside the union of its sources and takes the largest of their values.  The tracer is loaded with the cells of every round
+        (the next round reads its face table) with refittable = what it was loaded with; when the first round accepts nothing it
+        is not touched.  The precondition is a mesh without inverted tetrahedra (limit_vertex_step keeps it so).
+        Returns {"cells": int32 [T', 4] (borrowed by the tracer from now on), "tet_values": the carried arrays, "cell_sources":
+        int64 [T', S] (the input rows whose union holds the row, ascending, padded with -1), "rounds": the ten counters of every
+        round run, as lists (geometry.FLIP_COUNTER_NAMES; the last round is the one that accepted nothing, or the first not run
+        for max_rounds), "violated" and "unflippable": what that last round counted, "num_rounds": rounds that flipped,
+        "num_tetrahedra": T'}.  BLOCKS per round on two small read-backs -- the counters between the two entries, and the width of
+        the composed sources (compose_cell_sources) -- and on the loads."""
+        with torch.no_grad():
+            xyz = self._xyz_or_loaded(xyz)
+            tet_values = list(self._check_tet_values(tet_values, flat=True))
+            cells = self.tetrahedra_cells                                       # (returned as it is where nothing flips)
+            sources, rounds = torch.arange(cells.numel() // 4, dtype=torch.int64, device=self._device)[:, None], []
+            while True:
+                if len(rounds) >= int(max_rounds):                            # the round that is not run: counted, not emitted
+                    rounds.append(self.flip_count(xyz)["counters"].tolist())
+                    break
+                out = self.flip_faces(xyz)
+                rounds.append(out["counters"].tolist())
+                if out["num_23"] + out["num_32"] == 0:
+                    break
+                cells = out["cells"]
+                tet_values = [flip_tet_values(t.detach(), out["cell_sources"]) for t in tet_values]
+                sources = compose_cell_sources(sources, out["cell_sources"])
+                self.load_tetrahedra(xyz, cells, refittable=self._refittable)
+            return {"cells": cells, "tet_values": tet_values, "cell_sources": sources, "rounds": rounds, "violated": rounds[-1][1],
+                    "unflippable": rounds[-1][6], "num_rounds": len(rounds) - 1, "num_tetrahedra": cells.numel() // 4}
+
     supports_prune = True
     PRUNE_GRID_LANES = 1024 * 256            # lanes of the prune's kernels at their grid cap (tn_prune.hip: PRUNE_BLOCKS * BT)
 
@@ -1538,6 +1602,112 @@ def split_edges(xyz, cells, select, faces, face_tets):
                                                           _ptr(count["bisected"]), _ptr(count["edge_vertices"]), _ptr(count["counters"]),
                                                           _stream(dev)))
         return _edge_split_emit(xyz, cells, count)
+
+
+def _flip_buffers(T, F, dev):
+    """the outputs of the flip's count entries"""
+    return {"tet_offsets": _empty((T + 1,), dtype=torch.int32, device=dev), "tet_flip": _empty((T,), dtype=torch.int32, device=dev),
+            "flipped": _empty((T,), dtype=torch.uint8, device=dev), "face_flip": _empty((F, 3), dtype=torch.int32, device=dev),
+            "counters": _empty((10,), dtype=torch.int32, device=dev)}
+
+
+FLIP_MAX_CELLS = 1 << 30                     # tn_flip_core.h: MAX_CELLS
+
+
+def _flip_emit(cells, count, emit):
+    """The read-back of the counters and the emit entry `emit(K23, K32, cells_out, cell_sources)`: flip_faces' dict (the input
+    cells themselves where nothing is accepted)"""
+    T, dev = cells.size(0), cells.device
+    host = count["counters"].tolist()                                          # the read-back
+    K23, K32 = int(host[8]), int(host[9])
+    _check(T + K23 < FLIP_MAX_CELLS, "flip_faces: num_cells + accepted 2-3 flips must be below 2^30")
+    out = {"counters": count["counters"], "flipped": count["flipped"], "tet_flip": count["tet_flip"], "tet_offsets": count["tet_offsets"],
+           "face_flip": count["face_flip"], "num_23": K23, "num_32": K32, "num_cells": T + K23 - K32}
+    if K23 + K32 == 0:
+        src = torch.full((T, 3), -1, dtype=torch.int32, device=dev)
+        src[:, 0] = torch.arange(T, dtype=torch.int32, device=dev)
+        out.update(cells=cells, cell_sources=src)
+        return out
+    new_cells = _empty((T + K23 - K32, 4), dtype=torch.int32, device=dev)
+    sources = _empty((T + K23 - K32, 3), dtype=torch.int32, device=dev)
+    emit(K23, K32, new_cells, sources)
+    out.update(cells=new_cells, cell_sources=sources)
+    return out
+
+
+def flip_faces(xyz, cells, faces, face_tets):
+    """ONE round of the Delaunay repair by bistellar flips (no reference counterpart; tn_flip_count_tables + tn_flip_emit;
+    statement: geometry.flip_faces_statement, bit for bit; the rule: DESIGN.md section 4.23).  xyz f32 [V, 3], cells i32 [T, 4],
+    faces i32 [F, 3] and face_tets i32 [F, 2] (the cells' face table, -1 = no second tetrahedron: a hull face), all on one device.
+    Every interior face that is CERTAINLY violated (delaunay_check's verdict) is a candidate: for a 2-3 flip where the edge
+    between the two opposite vertices crosses the face, for a 3-2 flip where it passes one edge of the face and a third
+    tetrahedron closes the ring around that edge.  A candidate is refused for an id outside [0, V), for opposite vertices that are
+    not certainly on opposite sides, for an uncertain orientation around the new edge, for an unflippable configuration, or
+    because a tetrahedron it needs goes to a candidate with a smaller face id.  The accepted flips share no tetrahedron: an
+    independent set, not a maximal one -- call again for more.  No vertex is added or moved.
+    Returns {"cells": i32 [T', 4], "cell_sources": i32 [T', 3] (the old rows whose union holds the new row, -1 = none:
+    flip_tet_values carries a per-tetrahedron array), "flipped": uint8 [T], "tet_flip": i32 [T], "tet_offsets": i32 [T + 1],
+    "face_flip": i32 [F, 3] = (code, t2, rank), "counters": i32 [10] on the device (geometry.FLIP_COUNTER_NAMES), "num_23",
+    "num_32", "num_cells": T' = T + num_23 - num_32}.
+    BLOCKS on one small read-back: the counters between the two entries (they size the outputs).  With nothing accepted the
+    second entry is not called: "cells" is the input itself."""
+    for x, name in ((xyz, "xyz"), (cells, "cells"), (faces, "faces"), (face_tets, "face_tets")):
+        _check_input(x, name)
+    dev = xyz.device
+    _check(xyz.dtype == torch.float32 and xyz.dim() == 2 and xyz.size(1) == 3, "xyz must be f32 [V, 3]")
+    _check(cells.dtype == torch.int32 and cells.dim() == 2 and cells.size(1) == 4 and cells.device == dev,
+           "cells must be int32 [num_cells, 4] on the device of xyz")
+    V, T, F = xyz.size(0), cells.size(0), faces.size(0)
+    _check(faces.dtype == torch.int32 and faces.dim() == 2 and faces.size(1) == 3 and faces.device == dev,
+           "faces must be int32 [num_faces, 3] on the device of xyz")
+    _check(face_tets.dtype == torch.int32 and tuple(face_tets.shape) == (F, 2) and face_tets.device == dev,
+           "face_tets must be int32 [num_faces, 2] on the device of xyz")
+    lib = _lib.load()
+    with torch.no_grad(), _on(dev):
+        count = _flip_buffers(T, F, dev)
+        _lib.check(lib.tn_flip_count_tables(dev.index or 0, V, T, _ptr(xyz), _ptr(cells), F, _ptr(faces), _ptr(face_tets),
+                                            _ptr(count["tet_offsets"]), _ptr(count["tet_flip"]), _ptr(count["flipped"]),
+                                            _ptr(count["face_flip"]), _ptr(count["counters"]), _stream(dev)))
+
+        def emit(K23, K32, new_cells, sources):
+            _lib.check(lib.tn_flip_emit(T, _ptr(cells), F, _ptr(faces), _ptr(face_tets), _ptr(count["tet_offsets"]), _ptr(count["tet_flip"]),
+                                        _ptr(count["face_flip"]), K23, K32, _ptr(new_cells), _ptr(sources), _stream(dev)))
+        return _flip_emit(cells, count, emit)
+
+
+def flip_tet_values(values, cell_sources):
+    """Carry a per-tetrahedron array through a round of flips: values f32 [T] (>= 0: the occupancy), cell_sources i32 [T', 3]
+    (flip_faces; -1 = none) -> f32 [T']: per new row the largest value over its sources, by remap_tet_values' rule (the values'
+    bit patterns as unsigned integers; geometry.flip_tet_values_statement).  A new row lies inside the union of its sources, so
+    this is conservative in space, not only over vertex stars.  Plain torch; no synchronisation."""
+    _check(values.dtype == torch.float32 and values.dim() == 1, "values must be float32 [T]")
+    _check(cell_sources.dim() == 2 and cell_sources.size(1) == 3 and cell_sources.device == values.device,
+           "cell_sources must be [T', 3] on the device of values")
+    with torch.no_grad():
+        bits = values.contiguous().view(torch.int32).long() & 0xFFFFFFFF
+        s = cell_sources.long()
+        if bits.numel() == 0:
+            return torch.zeros(s.size(0), dtype=torch.float32, device=values.device)
+        got = torch.where(s >= 0, bits[s.clamp_min(0)], torch.zeros_like(s)).amax(1)
+        return torch.where(got >= (1 << 31), got - (1 << 32), got).to(torch.int32).view(torch.float32)
+
+
+def compose_cell_sources(sources, step):
+    """sources int64 [T, S] (-1-padded input rows of every current row; None: every row is its own source), step i32 [T', 3]
+    (flip_faces' cell_sources of one round) -> int64 [T', S'] the input rows of every new row: the union over its sources,
+    ascending, without repeats, padded with -1 and trimmed to the longest (geometry.compose_cell_sources).  One read-back."""
+    s = step.long()
+    if sources is None:
+        sources = torch.arange(int(s.max().item()) + 1 if s.numel() else 0, dtype=torch.int64, device=s.device)[:, None]
+    big = 1 << 32
+    src = torch.where(sources < 0, torch.full_like(sources, big), sources)
+    got = torch.where((s >= 0)[:, :, None], src[s.clamp_min(0)], torch.full((1, 1, 1), big, dtype=torch.int64, device=s.device))
+    got = got.reshape(s.size(0), -1).sort(1).values
+    got[:, 1:][got[:, 1:] == got[:, :-1]] = big
+    got = got.sort(1).values
+    width = max(int((got != big).sum(1).max().item()) if got.numel() else 1, 1)
+    got = got[:, :width]
+    return torch.where(got == big, torch.full_like(got, -1), got)
 
 
 def _check_prune_masks(dead, vertex_select, T, V, dev):
