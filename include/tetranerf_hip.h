@@ -387,6 +387,28 @@ int tn_flip_emit(size_t num_cells, const uint32_t *cells, size_t num_faces, cons
 int tn_flip_emit_loaded(tn_tracer_t tracer, const uint32_t *tet_offsets, const uint32_t *tet_flip, const uint32_t *face_flip,
                         size_t num_23, size_t num_32, uint32_t *cells_out, uint32_t *cell_sources, void *stream);
 
+/* The face table of any cell rows, on the device and without a tracer: the face-table stage of load_tetrahedra's device build as
+ * an entry of its own (csrc/tn_build.hip; the rule: face_hash_insert / face_is_first / face_emit of csrc/tn_build_core.h, in words
+ * DESIGN.md section 4.24; every output is byte-equal to geometry.face_table_statement and to the table a load of the same cells
+ * builds).  Sighting i = 4 t + j is local face j of row t: the ids cells[t][(j+1)&3], [(j+2)&3], [(j+3)&3].  Sightings are keyed by
+ * their sorted id triple; one sighting is a hull face, two pair up, a third sets FLAG_TRIPLE_FACE.  A face's id is the rank of its
+ * first sighting among the first sightings; its stored ids are its first sighting's, in that order.
+ * tn_face_table_count: partner u32 [4T] = the other sighting of sighting i's face, 0xFFFFFFFF for none; face_index u32 [4T+1] =
+ *   exclusive sums of "sighting i is the first of its face", the total F last; counters u32 [4], zeroed by the call: F, the number
+ *   of hull faces, flag bits (1: an id >= num_vertices -- the table is still defined, only ids are compared; 2: a face with more
+ *   than two sightings -- the table is then unspecified, and still nothing is written outside the buffers), a reserved 0.  The
+ *   hash has the smallest power of two >= 8T + 16 slots; scratch is one stream-ordered allocation.
+ * tn_face_table_emit: given those arrays and num_faces = F (a host value): faces u32 [num_faces,3], face_tets u32 [num_faces,2]
+ *   (first sighting's row, the partner's row or 0xFFFFFFFF), tet_faces u32 [T,4] (may be NULL) = the face id of every sighting.
+ *   A face whose id is >= num_faces is skipped whole (its tet_faces entries too): no store goes to a row >= num_faces.
+ * Both launch on `stream` and read nothing back; the only atomics are the hash's claims and three counter adds per block, so no
+ *   result depends on an order.  T == 0 gives empties and zero counters.  Errors (nothing is touched): a null pointer beside a
+ *   non-zero count; num_cells >= 2^30; num_faces > 4 num_cells. */
+int tn_face_table_count(int device, size_t num_vertices, size_t num_cells, const uint32_t *cells, uint32_t *partner,
+                        uint32_t *face_index, uint32_t *counters, void *stream);
+int tn_face_table_emit(size_t num_cells, const uint32_t *cells, const uint32_t *partner, const uint32_t *face_index, size_t num_faces,
+                       uint32_t *faces, uint32_t *face_tets, uint32_t *tet_faces, void *stream);
+
 /* number of unique faces of the loaded mesh (0 before load) */
 size_t tn_num_faces(tn_tracer_t tracer);
 

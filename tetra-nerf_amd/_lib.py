@@ -43,6 +43,7 @@ SYMBOLS = (
     "tn_prune_count", "tn_prune_count_tables", "tn_prune_emit", "tn_prune_vertex_rows",   # vertex pruning: the reference never changes its mesh
     "tn_edge_split_count", "tn_edge_split_count_tables", "tn_edge_split_emit",   # edge bisection with the whole ring: likewise
     "tn_flip_count", "tn_flip_count_tables", "tn_flip_emit", "tn_flip_emit_loaded",   # Delaunay repair by 2-3 and 3-2 flips: likewise
+    "tn_face_table_count", "tn_face_table_emit",   # the face table of any cell rows, without a tracer
 )
 
 ABI_VERSION = 6          # include/tetranerf_hip.h: TN_ABI_VERSION this binding was written against
@@ -98,6 +99,8 @@ def load():
     lib.tn_flip_count.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_flip_emit.argtypes = [sz, vp, sz, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
     lib.tn_flip_emit_loaded.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+    lib.tn_face_table_count.argtypes = [i32, sz, sz, vp, vp, vp, vp, vp]
+    lib.tn_face_table_emit.argtypes = [sz, vp, vp, vp, sz, vp, vp, vp, vp]
     lib.tn_tet_stats_accumulate.argtypes = [u32, sz, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tn_refit_table_bytes.restype = sz
     lib.tn_refit_table_bytes.argtypes = [vp]

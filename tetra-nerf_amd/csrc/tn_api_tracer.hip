@@ -1014,6 +1014,29 @@ int tn_flip_emit_loaded(tn_tracer_t tracer, const uint32_t *tet_offsets, const u
     });
 }
 
+int tn_face_table_count(int device, size_t V, size_t T, const uint32_t *cells, uint32_t *partner, uint32_t *face_index,
+                        uint32_t *counters, void *stream_) {
+    return guarded([&] {
+        const std::string w("tn_face_table_count");
+        if (T >= ((size_t)1 << 30)) throw tn::Error(w + ": num_cells must be below 2^30");
+        if (!face_index || !counters || (T && (!cells || !partner))) throw tn::Error(w + ": a null pointer beside a non-zero count");
+        DeviceGuard g(device);
+        tn::launch_face_table_count(V, T, cells, partner, face_index, counters, (hipStream_t)stream_);
+    });
+}
+
+int tn_face_table_emit(size_t T, const uint32_t *cells, const uint32_t *partner, const uint32_t *face_index, size_t num_faces,
+                       uint32_t *faces, uint32_t *face_tets, uint32_t *tet_faces, void *stream_) {
+    return guarded([&] {
+        const std::string w("tn_face_table_emit");
+        if (T >= ((size_t)1 << 30)) throw tn::Error(w + ": num_cells must be below 2^30");
+        if (num_faces > 4 * T) throw tn::Error(w + ": num_faces exceeds 4 num_cells (a tetrahedron has four faces)");
+        if ((T && (!cells || !partner || !face_index)) || (num_faces && (!faces || !face_tets)))
+            throw tn::Error(w + ": a null pointer beside a non-zero count");
+        tn::launch_face_table_emit(T, cells, partner, face_index, num_faces, faces, face_tets, tet_faces, (hipStream_t)stream_);
+    });
+}
+
 size_t tn_num_faces(tn_tracer_t tracer) { return tracer && tracer->mesh.loaded ? tracer->mesh.view.F : 0; }
 
 int tn_get_faces(tn_tracer_t tracer, uint32_t *faces_host, uint32_t *face_tets_host) {

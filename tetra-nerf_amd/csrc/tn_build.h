@@ -176,4 +176,17 @@ void launch_flip_emit(size_t T, const uint32_t *cells, size_t F, const uint32_t 
                       const uint32_t *tet_offsets, const uint32_t *tet_flip, const uint32_t *face_flip, size_t num_23, size_t num_32,
                       uint32_t *cells_out, uint32_t *cell_sources, hipStream_t s);
 
+// The face table of any cell rows, without a tracer (tn_build.hip: the face-table stage of device_build on its own; the rule:
+// face_hash_insert / face_is_first / face_emit of tn_build_core.h, in words DESIGN.md section 4.24).  Both enqueue on `s` and
+// return: no read-back.  launch_face_table_count: partner u32 [4T] = the other sighting of sighting i's face or 0xFFFFFFFF;
+// face_index u32 [4T + 1] = exclusive sums of "sighting i is the first of its face", the total F last; counters u32 [4] zeroed and
+// then = F, hull faces, FLAG_CELL_OOB | FLAG_TRIPLE_FACE, 0; one stream-ordered allocation (hash slots: the smallest power of two
+// >= 8T + 16).  launch_face_table_emit: the caller read F back and passes it as num_faces, which bounds every store to faces u32
+// [num_faces, 3] and face_tets u32 [num_faces, 2]; tet_faces u32 [T, 4] may be null (then one stream-ordered allocation).  The
+// entries (tn_api_tracer.hip) have checked the arguments.
+void launch_face_table_count(size_t V, size_t T, const uint32_t *cells, uint32_t *partner, uint32_t *face_index, uint32_t *counters,
+                             hipStream_t s);
+void launch_face_table_emit(size_t T, const uint32_t *cells, const uint32_t *partner, const uint32_t *face_index, size_t num_faces,
+                            uint32_t *faces, uint32_t *face_tets, uint32_t *tet_faces, hipStream_t s);
+
 }  // namespace tn

@@ -533,4 +533,75 @@ void device_build(size_t V, size_t T, const float *xyz, const uint32_t *cells, h
     }
 }
 
+// ------------------------------------------------------------------ the face table alone (tn_face_table_count / tn_face_table_emit)
+// The face-table stage of the build above as an entry of its own: k_face_hash and k_face_first as they are, then the counters and
+// a bounded emit.  Nothing is read back; the caller reads the counters and passes F to the second half.
+namespace {
+
+constexpr unsigned FACE_BLOCKS = 2048;   // grid cap of the two kernels below (grid-stride beyond; tn_mesh_ops.h)
+
+// after k_face_hash: counters[0] += first sightings (= faces), counters[1] += sightings without a partner (= hull faces), one add
+// per block and counter; counters[2] |= FLAG_CELL_OOB where an id is >= V, one atomic per wave that saw one
+__global__ __launch_bounds__(BT) void k_face_table_counters(size_t n4, const uint32_t *__restrict__ cells, uint64_t V,
+                                                            const uint32_t *__restrict__ partner, uint32_t *counters) {
+    uint32_t n[2] = {0u, 0u};
+    bool oob = false;
+    for (size_t i = gid(); i < n4; i += stride<BT>()) {
+        n[0] += core::face_is_first((uint32_t)i, partner) ? 1u : 0u;
+        n[1] += partner[i] == TN_EMPTY ? 1u : 0u;
+        oob |= (uint64_t)cells[i] >= V;
+    }
+    if (__ballot(oob) != 0ull && (threadIdx.x & 63) == 0) atomicOr(counters + 2, core::FLAG_CELL_OOB);
+    block_count<BT, 2>(n, counters);
+}
+
+// k_face_emit behind the caller's bound: a first sighting whose face id is below num_faces writes its row (and the tet_face of
+// its one or two sightings); a partner that is no sighting index (a buffer changed between the two entries) writes nothing
+__global__ __launch_bounds__(BT) void k_face_table_emit(size_t n4, const uint32_t *__restrict__ cells, const uint32_t *__restrict__ partner,
+                                                        const uint32_t *__restrict__ fidx, uint32_t num_faces, uint32_t *faces,
+                                                        uint32_t *face_tets, uint32_t *tet_face) {
+    for (size_t i = gid(); i < n4; i += stride<BT>()) {
+        const uint32_t p = partner[i];
+        if (p != TN_EMPTY && (p >= n4 || p <= i)) continue;   // not a first sighting, or not a sighting at all
+        const uint32_t f = fidx[i];
+        if (f < num_faces) core::face_emit((uint32_t)i, f, cells, partner, faces, face_tets, tet_face);
+    }
+}
+
+}  // namespace
+
+void launch_face_table_count(size_t V, size_t T, const uint32_t *cells, uint32_t *partner, uint32_t *face_index, uint32_t *counters,
+                             hipStream_t s) {
+    TN_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(uint32_t), s));
+    const size_t n4 = 4 * T, n = n4 + 1;   // the flag of a last, empty sighting: its exclusive sum is the total F
+    size_t cap = 16;
+    while (cap < 8 * T + 16) cap <<= 1;
+    const size_t tmp_bytes = scan_bytes<const uint32_t *>(n, s);
+    const size_t slot_bytes = align256(cap * sizeof(uint32_t)), first_bytes = align256(n * sizeof(uint32_t));
+    // the hash slots | "is first sighting" | rocprim's scratch
+    AsyncBytes all(slot_bytes + first_bytes + tmp_bytes, s);
+    uint32_t *slot = all.at<uint32_t>(), *first = all.at<uint32_t>(slot_bytes);
+    TN_HIP(hipMemsetAsync(slot, 0xFF, cap * sizeof(uint32_t), s));
+    TN_HIP(hipMemsetAsync(first + n4, 0, sizeof(uint32_t), s));
+    if (T) {
+        TN_HIP(hipMemsetAsync(partner, 0xFF, n4 * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_face_hash, dim3(grid_for(n4)), dim3(BT), 0, s, n4, cells, slot, (uint64_t)(cap - 1), partner, counters + 2);
+        hipLaunchKernelGGL(k_face_first, dim3(grid_for(n4)), dim3(BT), 0, s, n4, (const uint32_t *)partner, first);
+        hipLaunchKernelGGL(k_face_table_counters, dim3(grid_for<BT, FACE_BLOCKS>(n4)), dim3(BT), 0, s, n4, cells, (uint64_t)V,
+                           (const uint32_t *)partner, counters);
+        TN_HIP(hipGetLastError());
+    }
+    scan(all.at<void>(slot_bytes + first_bytes), tmp_bytes, (const uint32_t *)first, face_index, n, s);
+}
+
+void launch_face_table_emit(size_t T, const uint32_t *cells, const uint32_t *partner, const uint32_t *face_index, size_t num_faces,
+                            uint32_t *faces, uint32_t *face_tets, uint32_t *tet_faces, hipStream_t s) {
+    if (T == 0) return;
+    const size_t n4 = 4 * T;
+    AsyncBytes own(tet_faces ? 0 : n4 * sizeof(uint32_t), s);   // face_emit always writes tet_face: a null one gets scratch
+    hipLaunchKernelGGL(k_face_table_emit, dim3(grid_for<BT, FACE_BLOCKS>(n4)), dim3(BT), 0, s, n4, cells, partner, face_index,
+                       (uint32_t)num_faces, faces, face_tets, tet_faces ? tet_faces : own.at<uint32_t>());
+    TN_HIP(hipGetLastError());
+}
+
 }  // namespace tn

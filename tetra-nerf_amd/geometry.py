@@ -1043,6 +1043,69 @@ def compose_cell_sources(sources, step):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The face table of any cell rows (csrc/tn_build_core.h: face_hash_insert / face_is_first / face_emit; csrc/tn_build.hip:
+# tn_face_table_count / tn_face_table_emit), stated in numpy.  No arithmetic: every array is, byte for
+# byte, what the entries and a load of the same cells give.
+
+FACE_TABLE_COUNTER_NAMES = ("faces", "hull_faces", "flags", "reserved")
+FACE_TABLE_FLAG_CELL_OOB, FACE_TABLE_FLAG_TRIPLE_FACE = 1, 2     # tn_build_core.h: FLAG_CELL_OOB, FLAG_TRIPLE_FACE
+
+
+def face_sightings_statement(cells):
+    """The first half of the face table (tn_face_table_count).  Sighting i = 4 t + j is local face j of row t, the ids
+    cells[t, (j+1)&3], cells[t, (j+2)&3], cells[t, (j+3)&3] (face_of_tet).  Sightings are keyed by their sorted id triple: a key seen
+    once is a hull face, a key seen twice pairs its two sightings, a key seen three times or more is the build's "shared by more
+    than two tetrahedra" (then the two smallest sightings are paired here and the others stand alone; the device leaves it open
+    which two pair).  Rows need not be tetrahedra of a mesh: a row that repeats an id pairs its own sightings by the same rule.
+    Returns (triples uint32 [4T, 3], partner uint32 [4T] -- the other sighting of the face, EMPTY for none --, face_index uint32
+    [4T + 1] -- exclusive sums of "sighting i is the first of its face", the total F last --, triple: bool)."""
+    c = _as_index(_to_numpy(cells)).reshape(-1, 4)
+    n4, j = 4 * len(c), np.arange(4)
+    tri = np.stack([c[:, (j + 1) & 3], c[:, (j + 2) & 3], c[:, (j + 3) & 3]], -1).reshape(n4, 3)
+    key = np.sort(tri, 1)
+    order = np.lexsort((np.arange(n4), key[:, 2], key[:, 1], key[:, 0]))        # by key, then by sighting
+    sk = key[order]
+    new = np.ones(n4, bool)
+    new[1:] = (sk[1:] != sk[:-1]).any(1)
+    start = np.flatnonzero(new)
+    size = np.diff(np.append(start, n4))
+    partner = np.full(n4, EMPTY, np.int64)
+    a, b = order[start[size >= 2]], order[start[size >= 2] + 1]
+    partner[a], partner[b] = b, a
+    first = (partner == EMPTY) | (np.arange(n4) < partner)
+    face_index = np.zeros(n4 + 1, np.uint32)
+    face_index[1:] = np.cumsum(first)
+    return tri.astype(np.uint32), partner.astype(np.uint32), face_index, bool((size >= 3).any())
+
+
+def face_table_statement(cells, num_vertices=None):
+    """What tn_face_table_count + tn_face_table_emit compute, and what load_tetrahedra builds: the face table of cells integer
+    [T, 4] (numpy, or a torch tensor copied to the host; int32 ids are read as the uint32 they stand for).  With
+    face_sightings_statement's pairs: a face is a pair or a lone sighting; its id is the rank of its first (smaller) sighting among
+    the first sightings, so faces come in order of first sighting 4 t + j; its stored ids are its first sighting's, as face_of_tet
+    orders them.
+    Returns (faces uint32 [F, 3], face_tets uint32 [F, 2] = (row of the first sighting, row of its partner or EMPTY: a hull
+    face), tet_faces uint32 [T, 4] = the face id of every sighting, counters uint32 [4] = F, hull faces, flag bits
+    (FACE_TABLE_FLAG_CELL_OOB: an id >= num_vertices, never set with num_vertices None; FACE_TABLE_FLAG_TRIPLE_FACE: the table is
+    then unspecified on the device), 0)."""
+    tri, partner, face_index, triple = face_sightings_statement(cells)
+    n4, F = len(partner), int(face_index[-1])
+    fs = np.flatnonzero(face_index[1:] != face_index[:-1])                     # the first sightings, ascending
+    p = partner[fs]
+    faces = tri[fs].reshape(F, 3)
+    face_tets = np.stack([fs >> 2, np.where(p == EMPTY, EMPTY, p >> 2)], 1).astype(np.uint32).reshape(F, 2)
+    tet_faces = np.zeros(n4, np.uint32)
+    ids = np.arange(F, dtype=np.uint32)
+    tet_faces[fs] = ids
+    tet_faces[p[p != EMPTY]] = ids[p != EMPTY]
+    flags = FACE_TABLE_FLAG_TRIPLE_FACE if triple else 0
+    if num_vertices is not None and n4 and int(tri.max()) >= int(num_vertices):
+        flags |= FACE_TABLE_FLAG_CELL_OOB
+    counters = np.array([F, int((partner == EMPTY).sum()), flags, 0], np.uint32)
+    return faces, face_tets, tet_faces.reshape(-1, 4), counters
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Vertex pruning (csrc/tn_prune_core.h, csrc/tn_prune.hip; DESIGN.md section 4.21), stated in numpy: asked vertices whose every
 # tetrahedron is dead, and which lie on no hull face, are removed, and every per-vertex array is compacted.  No arithmetic: every
 # array is, bit for bit, what the kernels give.

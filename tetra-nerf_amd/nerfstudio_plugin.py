@@ -300,7 +300,17 @@ def _monitor_delaunay(tracer, model, above, keep_snapshot):
             raise ValueError('config.delaunay_repair must be "flip" or absent')
         if not getattr(tracer, "supports_flip", False):
             raise RuntimeError('config.delaunay_repair = "flip" needs a tracer with flip_to_delaunay (tetranerf_cpp_extension.TetrahedraTracer)')
-        out = tracer.flip_to_delaunay(tet_values=() if occupancy is None else (occupancy.detach(),))
+        # config.delaunay_repair_reload = "once" (opt-in; absent or None: the call below with exactly the arguments it had): the
+        # rounds read face tables built from the cells alone and the tracer is loaded once at the end
+        reload = getattr(model.config, "delaunay_repair_reload", None)
+        if reload is not None:
+            if reload not in ("round", "once"):
+                raise ValueError('config.delaunay_repair_reload must be "round", "once" or absent')
+            if not getattr(tracer, "supports_face_table", False):
+                raise RuntimeError("config.delaunay_repair_reload needs a tracer whose flip_to_delaunay takes reload= "
+                                   "(tetranerf_cpp_extension.TetrahedraTracer)")
+        tet_values = () if occupancy is None else (occupancy.detach(),)
+        out = tracer.flip_to_delaunay(tet_values=tet_values) if reload is None else tracer.flip_to_delaunay(tet_values=tet_values, reload=reload)
         if out["num_rounds"]:
             _adopt_mesh(model, tracer, out["cells"], occupancy=None if occupancy is None else out["tet_values"][0])
             model._tn_flip_repairs = getattr(model, "_tn_flip_repairs", 0) + 1

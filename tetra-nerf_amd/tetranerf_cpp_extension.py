@@ -439,7 +439,9 @@ class TetrahedraTracer:
             with _on(self._device):
                 return _flip_emit(cells, count, emit)
 
-    def flip_to_delaunay(self, xyz=None, tet_values=(), max_rounds=32):
+    supports_face_table = True               # flip_to_delaunay(reload="once"), cpp.face_table, cpp.flip_to_delaunay
+
+    def flip_to_delaunay(self, xyz=None, tet_values=(), max_rounds=32, reload="round"):
         """Repair the Delaunay property of the LOADED mesh on `xyz` (None: the loaded vertices) by bistellar flips, on the device (no
         reference counterpart).  Rounds of flip_faces -- every certainly violated face that is flippable
         and wins its rows is removed by a 2-3 or a 3-2 flip -- until a round accepts nothing or max_rounds rounds have flipped.  No
@@ -453,10 +455,33 @@ class TetrahedraTracer:
         round run, as lists (geometry.FLIP_COUNTER_NAMES; the last round is the one that accepted nothing, or the first not run
         for max_rounds), "violated" and "unflippable": what that last round counted, "num_rounds": rounds that flipped,
         "num_tetrahedra": T'}.  BLOCKS per round on two small read-backs -- the counters between the two entries, and the width of
-        the composed sources (compose_cell_sources) -- and on the loads."""
+        the composed sources (compose_cell_sources) -- and on the loads.
+        reload (keyword): "round" -- the above.  "once" -- the first round reads the tracer's own tables, every later round a face
+        table built from that round's cells alone (tn_face_table_count / tn_face_table_emit; the free
+        function flip_to_delaunay's loop), and the tracer is loaded exactly once, at the end, iff a round flipped: the same
+        returned dict and borrow rules, the same two read-backs per round, one load's worth of Morton sort, walk records, hull
+        tree and face BVH instead of one per round.  While the rounds run, and if one raises, the tracer holds the mesh it was
+        called with."""
+        _check(reload in ("round", "once"), 'reload must be "round" or "once"')
         with torch.no_grad():
             xyz = self._xyz_or_loaded(xyz)
             tet_values = list(self._check_tet_values(tet_values, flat=True))
+            if reload == "once":
+                loaded = self.tetrahedra_cells
+                with _on(self._device):
+                    count = self.flip_count(xyz)
+
+                    def emit(K23, K32, new_cells, sources):
+                        _lib.check(self._lib.tn_flip_emit_loaded(self._h, _ptr(count["tet_offsets"]), _ptr(count["tet_flip"]),
+                                                                 _ptr(count["face_flip"]), K23, K32, _ptr(new_cells), _ptr(sources),
+                                                                 _stream(self._device)))
+                    out = _flip_rounds(xyz, loaded.reshape(-1, 4), int(self._lib.tn_num_faces(self._h)), count, emit, tet_values,
+                                       max_rounds)
+                if out["num_rounds"] == 0:
+                    out["cells"] = loaded                                       # (returned as it is where nothing flips)
+                else:
+                    self.load_tetrahedra(xyz, out["cells"], refittable=self._refittable)
+                return out
             cells = self.tetrahedra_cells                                       # (returned as it is where nothing flips)
             sources, rounds = torch.arange(cells.numel() // 4, dtype=torch.int64, device=self._device)[:, None], []
             while True:
@@ -1708,6 +1733,144 @@ def compose_cell_sources(sources, step):
     width = max(int((got != big).sum(1).max().item()) if got.numel() else 1, 1)
     got = got[:, :width]
     return torch.where(got == big, torch.full_like(got, -1), got)
+
+
+FACE_TABLE_MAX_CELLS = 1 << 30               # tn_face_table_count: num_cells must be below 2^30
+FACE_TABLE_FLAG_CELL_OOB, FACE_TABLE_FLAG_TRIPLE_FACE = 1, 2   # tn_build_core.h: FLAG_CELL_OOB, FLAG_TRIPLE_FACE (geometry.py has them too)
+
+
+def _check_cell_rows(cells):
+    _check_input(cells, "cells")
+    _check(cells.dtype == torch.int32 and cells.dim() == 2 and cells.size(1) == 4, "cells must be int32 [num_cells, 4]")
+    _check(cells.size(0) < FACE_TABLE_MAX_CELLS, "face_table: num_cells must be below 2^30")
+
+
+def _face_table_count(cells, V):
+    """tn_face_table_count on checked cells: (partner i32 [4T], face_index i32 [4T + 1], counters i32 [4]); no synchronisation"""
+    T, dev = cells.size(0), cells.device
+    partner = _empty((4 * T,), dtype=torch.int32, device=dev)
+    face_index = _empty((4 * T + 1,), dtype=torch.int32, device=dev)
+    counters = _empty((4,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().tn_face_table_count(dev.index or 0, V, T, _ptr(cells), _ptr(partner), _ptr(face_index), _ptr(counters),
+                                               _stream(dev)))
+    return partner, face_index, counters
+
+
+def _face_table_emit(cells, partner, face_index, F, tet_faces=True, exact=True):
+    """tn_face_table_emit for the host value F: (faces i32 [F, 3], face_tets i32 [F, 2], tet_faces i32 [T, 4] or None).  exact: F
+    is the count's own total, read back; otherwise face_tets starts as -1, so that rows a smaller total leaves out are hull faces
+    (which no mesh operation reads further), never unwritten memory."""
+    T, dev = cells.size(0), cells.device
+    faces = _empty((F, 3), dtype=torch.int32, device=dev)
+    face_tets = _empty((F, 2), dtype=torch.int32, device=dev) if exact else torch.full((F, 2), -1, dtype=torch.int32, device=dev)
+    tf = _empty((T, 4), dtype=torch.int32, device=dev) if tet_faces else None
+    _lib.check(_lib.load().tn_face_table_emit(T, _ptr(cells), _ptr(partner), _ptr(face_index), F, _ptr(faces), _ptr(face_tets), _ptr(tf),
+                                              _stream(dev)))
+    return faces, face_tets, tf
+
+
+def _check_face_table_counters(host, num_faces=None):
+    """the build's own errors for the flag bits of a read-back [F, hull faces, flags, 0]; num_faces: the F the caller emitted with"""
+    _check(not host[2] & FACE_TABLE_FLAG_CELL_OOB, "cells contains a vertex index that is out of bounds")
+    _check(not host[2] & FACE_TABLE_FLAG_TRIPLE_FACE, "A triangle is shared by more than two tetrahedra!")
+    _check(num_faces is None or host[0] == num_faces,
+           f"internal: the face table has {host[0]} faces where the flips of the last round leave {num_faces}")
+
+
+def face_table(cells, num_vertices=None):
+    """The face table of any cell rows on the device, without a tracer (tn_face_table_count + tn_face_table_emit: the face-table
+    stage of load_tetrahedra's device build as an entry of its own; statement: geometry.face_table_statement, byte for byte; the
+    rule: DESIGN.md section 4.24).  cells i32 [T, 4]; num_vertices: None, or V -- then an id outside [0, V) raises the load's own
+    error.  Returns {"faces": i32 [F, 3] (in order of first sighting 4 t + local face, ids as the first sighting's row orders
+    them), "face_tets": i32 [F, 2] (-1 = no second tetrahedron: a hull face), "tet_faces": i32 [T, 4] (the face of every local
+    face), "counters": i32 [4] on the device (geometry.FACE_TABLE_COUNTER_NAMES), "num_faces": F, "num_hull_faces"}: what
+    flip_faces, split_edges and prune_vertices take as `faces` / `face_tets`, and what TetrahedraTracer.face_tables() reports after
+    a load of the same cells.  Raises "A triangle is shared by more than two tetrahedra!" like the load.
+    BLOCKS on one small read-back: the counters between the two entries (they size the outputs)."""
+    _check_cell_rows(cells)
+    dev = cells.device
+    with torch.no_grad(), _on(dev):
+        # without V no id is out of bounds: every uint32 id is below 2^32
+        partner, face_index, counters = _face_table_count(cells, 1 << 32 if num_vertices is None else int(num_vertices))
+        host = [h & 0xFFFFFFFF for h in counters.tolist()]                      # the read-back
+        _check_face_table_counters(host)
+        faces, face_tets, tet_faces = _face_table_emit(cells, partner, face_index, host[0])
+    return {"faces": faces, "face_tets": face_tets, "tet_faces": tet_faces, "counters": counters, "num_faces": host[0],
+            "num_hull_faces": host[1]}
+
+
+def _flip_count_tables(xyz, cells, faces, face_tets):
+    """tn_flip_count_tables on checked arrays -> (the count buffers, flip_faces' emit closure); no synchronisation"""
+    lib, dev = _lib.load(), xyz.device
+    V, T, F = xyz.size(0), cells.size(0), faces.size(0)
+    count = _flip_buffers(T, F, dev)
+    _lib.check(lib.tn_flip_count_tables(dev.index or 0, V, T, _ptr(xyz), _ptr(cells), F, _ptr(faces), _ptr(face_tets),
+                                        _ptr(count["tet_offsets"]), _ptr(count["tet_flip"]), _ptr(count["flipped"]),
+                                        _ptr(count["face_flip"]), _ptr(count["counters"]), _stream(dev)))
+
+    def emit(K23, K32, new_cells, sources):
+        _lib.check(lib.tn_flip_emit(T, _ptr(cells), F, _ptr(faces), _ptr(face_tets), _ptr(count["tet_offsets"]), _ptr(count["tet_flip"]),
+                                    _ptr(count["face_flip"]), K23, K32, _ptr(new_cells), _ptr(sources), _stream(dev)))
+    return count, emit
+
+
+def _flip_rounds(xyz, cells, F, count, emit, tet_values, max_rounds):
+    """The loop of flip_to_delaunay on face tables built by tn_face_table_count / tn_face_table_emit.
+    (count, emit): the first round's count buffers on `cells` and its emit closure (_flip_emit's), F the face count of that round's
+    table.  After a round's read-back K23 and K32 are host values, so the next table's F' = F + 2 K23 - 2 K32 is known without
+    another one (a 2-3 flip removes one face and adds three, a 3-2 flip removes three and adds one): the next round's table is
+    emitted with F', its flips are counted on it, and its counters (F, flag bits) come back in the SAME read-back as that round's
+    flip counters, before anything is emitted from that table.  Two small read-backs per round, like the loop that reloads: this
+    one, and the width of the composed sources.  Returns TetrahedraTracer.flip_to_delaunay's dict."""
+    dev, V = xyz.device, xyz.size(0)
+    tet_values = list(tet_values)
+    sources, rounds, table_counters = torch.arange(cells.size(0), dtype=torch.int64, device=dev)[:, None], [], None
+    while True:
+        if table_counters is None:
+            host = count["counters"].tolist()                                   # the read-back
+        else:
+            host = torch.cat((count["counters"], table_counters)).tolist()      # the read-back, with the table's counters
+            _check_face_table_counters([h & 0xFFFFFFFF for h in host[10:]], F)
+        rounds.append(host[:10])
+        K23, K32 = int(host[8]), int(host[9])
+        if K23 + K32 == 0 or len(rounds) > int(max_rounds):                     # nothing accepted, or the round that is not run
+            break
+        T = cells.size(0)
+        _check(T + K23 < FLIP_MAX_CELLS, "flip_faces: num_cells + accepted 2-3 flips must be below 2^30")
+        new_cells = _empty((T + K23 - K32, 4), dtype=torch.int32, device=dev)
+        step = _empty((T + K23 - K32, 3), dtype=torch.int32, device=dev)
+        emit(K23, K32, new_cells, step)
+        cells, F = new_cells, F + 2 * K23 - 2 * K32
+        tet_values = [flip_tet_values(t.detach(), step) for t in tet_values]
+        sources = compose_cell_sources(sources, step)
+        partner, face_index, table_counters = _face_table_count(cells, V)
+        faces, face_tets, _ = _face_table_emit(cells, partner, face_index, F, tet_faces=False, exact=False)
+        count, emit = _flip_count_tables(xyz, cells, faces, face_tets)
+    return {"cells": cells, "tet_values": tet_values, "cell_sources": sources, "rounds": rounds, "violated": rounds[-1][1],
+            "unflippable": rounds[-1][6], "num_rounds": len(rounds) - 1, "num_tetrahedra": cells.size(0)}
+
+
+def flip_to_delaunay(xyz, cells, tet_values=(), max_rounds=32):
+    """TetrahedraTracer.flip_to_delaunay without a tracer: repair the Delaunay property of `cells` on `xyz` by rounds of bistellar
+    flips (flip_faces' rule), every round's face table built on the device by face_table's two entries
+    (section 4.24) -- nothing is loaded.  xyz f32 [V, 3], cells i32 [T, 4] on its device (a mesh without inverted tetrahedra,
+    ids in [0, V)), tet_values: float32 [T] arrays of values >= 0, carried by flip_tet_values.  Returns the tracer method's dict
+    ("cells" is the input itself where nothing flips); its rounds, counters, cell_sources and carried values are the same.
+    BLOCKS once on the first table's counters, then per round on two small read-backs: the flip's counters with the next table's,
+    and the width of the composed sources."""
+    _check_input(xyz, "xyz")
+    _check(xyz.dtype == torch.float32 and xyz.dim() == 2 and xyz.size(1) == 3, "xyz must be f32 [V, 3]")
+    _check_cell_rows(cells)
+    _check(cells.device == xyz.device, "cells must be on the device of xyz")
+    tet_values = tuple(tet_values)
+    for t in tet_values:
+        _check_input(t, "tet_values")
+        _check(t.dtype == torch.float32 and t.dim() == 1 and t.size(0) == cells.size(0) and t.device == xyz.device,
+               "tet_values must be float32 [T] arrays over the cells, on the device of xyz")
+    with torch.no_grad(), _on(xyz.device):
+        table = face_table(cells, xyz.size(0))
+        count, emit = _flip_count_tables(xyz, cells, table["faces"], table["face_tets"])
+        return _flip_rounds(xyz, cells, table["num_faces"], count, emit, tet_values, max_rounds)
 
 
 def _check_prune_masks(dead, vertex_select, T, V, dev):
